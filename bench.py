@@ -14,6 +14,11 @@ A "step" is one pass of the hot path over one batch of synthetic input already r
   --mode train            one training step (forward + CE + backward + Adam) of cfg 3/4 with ONE RCCL
                           all-reduce of the flat 6.45 MB gradient bucket per step when N > 1.
 Rank 0 prints ONE JSON line.  `value` = graphs processed by all ranks / max-over-ranks wall time.
+
+A plain run sets up, warms up, times the K steps and prints the line: `ms_per_step` = the timed wall time / K.
+--full adds everything else the line can carry (one-forward latency, hand-over rates, rooflines, the CPU baseline, the
+other configurations' sub-records); the --no-* switches trim that set.  --dump-outputs DIR writes what the last
+timed step returned as DIR/<name>.npy (fwd: pred_cls, bbox; train: loss and every parameter after the step).
 """
 import argparse
 import json
@@ -38,10 +43,15 @@ def parse():
     ap.add_argument("--warmup", type=int, default=50)
     ap.add_argument("--mode", default="fwd", choices=["fwd", "train"])
     ap.add_argument("--config", default=None, help="cfg id 1..5 (default: 2 for fwd, 3 for train)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure everything beside the headline: latency, hand-over rates, "
+                         "rooflines, CPU baseline, sub-records (minutes; a plain run does none of it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned to DIR/<name>.npy (float32 / float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the op tables and rooflines")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the sub-records (multi_stream, floorplans_sized, train_dp)")
+                    help="with --full: skip the sub-records (multi_stream, floorplans_sized, train_dp, other configs)")
     ap.add_argument("--keep-csr", action="store_true", help="re-use the CSR across steps (fwd mode)")
     ap.add_argument("--graphs", action="store_true",
                     help="fwd mode: replay a captured hipGraph per stream instead of launching every kernel "
@@ -64,6 +74,23 @@ def to_device(data):
     for k in ("x", "edge", "e_attr", "bbox_idx", "bbox", "labels"):
         data[k] = data[k].cuda()
     return data
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: one DIR/<name>.npy per returned tensor, float64 kept, every other dtype as float32."""
+    host = {}
+    for name, t in arrays.items():
+        t = t.detach()
+        host[name] = (t if t.dtype == torch.float64 else t.float()).cpu().numpy()
+    total = sum(a.nbytes for a in host.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit("--dump-outputs: %d bytes of outputs exceed the %d-byte limit" % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in host.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -1097,7 +1124,7 @@ def main():
             if not args.keep_csr:
                 data._yolat_stage = None          # rebuild CSR / segments from the raw COO list
             with torch.cuda.stream(stream), torch.no_grad():
-                return model(data, slices)[0]
+                return model(data, slices)
 
         def step():
             # every step is one complete forward (COO -> CSR -> ... -> logits) of one graph; consecutive
@@ -1131,7 +1158,7 @@ def main():
     barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        last = step()
     barrier()
     elapsed = time.perf_counter() - t0
     dist_proof = None
@@ -1140,11 +1167,24 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:
+        # before any further step: an eval plan's output may live in its stream's workspace
+        if args.mode == "fwd":
+            dump_outputs(args.dump_outputs, {"pred_cls": last[0], "bbox": last[1]})
+        else:
+            outs = {"loss": last}
+            outs.update(("param." + k, p) for k, p in model.named_parameters())
+            dump_outputs(args.dump_outputs, outs)
+
+    # everything below the headline runs with --full only
+    full = args.full
+    roofline = full and not args.no_roofline
+    extras = full and not args.no_extras
 
     if use_graphs:
         model.use_hip_graphs(False)       # latency / per-stage profiling below use direct launches
     latency_ms = None
-    if args.mode == "fwd":
+    if args.mode == "fwd" and full:
         # ms/forward: latency of ONE forward with nothing else in flight (single stream)
         nlat = min(args.steps, 100)
         for _ in range(5):
@@ -1159,7 +1199,7 @@ def main():
     h2d_inclusive = None
     csr_mode = None
     coo_loader = None
-    if args.mode == "fwd" and rank == 0:
+    if args.mode == "fwd" and rank == 0 and full:
         # PCIe-inclusive rate (never `value`): the batch starts as CPU tensors, goes through
         # data.collate_to_device (one pinned staging buffer, one async H2D copy, offset fix-up on the device)
         # and one forward; one batch at a time.
@@ -1255,10 +1295,10 @@ def main():
     roof = None
     op_table = None
     nprof = min(args.steps, 50)
-    if args.mode == "train" and world > 1 and rank != 0 and not args.no_roofline:
+    if args.mode == "train" and world > 1 and rank != 0 and roofline:
         for _ in range(nprof):           # the train step contains a collective: every rank must take part
             step()                       # in rank 0's profiling steps
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and roofline:
         if args.mode == "fwd":
             op_table = plan_profile(step_single, nprof)
         else:
@@ -1272,25 +1312,25 @@ def main():
                         "this workload)")
 
     agg = edge_roof = fusion_roof = None
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and roofline:
         agg = aggregation_roofline()
         edge_roof = edge_layer_roofline()
         if op_table is not None and args.mode == "fwd":
             fusion_roof = fusion_stage_roofline(op_table, str(cfg), args.precision)
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:      # reported at N=1 only
+    if rank == 0 and world == 1 and full and not args.no_cpu_baseline:      # reported at N=1 only
         cpu = cpu_baseline(cfg, optkw, args.mode)
 
     multi = floor = train_dp = None
-    if args.mode == "fwd" and rank == 0 and not args.no_extras:
+    if args.mode == "fwd" and rank == 0 and extras:
         # serving-style throughput with many forwards in flight, over >= 512 forwards whatever --steps is
         multi = multi_stream_throughput(model, data, slices, n_graphs, n_streams=max(args.streams, 1),
                                         forwards=1024 if (N < 50000) else 256, keep_csr=args.keep_csr)
         if world == 1 and str(cfg) == "2" and args.precision == "fp32":
             floor = floorplans_sized_record(yv, gu, cpu=not args.no_cpu_baseline)
     more = {}
-    if rank == 0 and world == 1 and not args.no_extras and args.mode == "fwd" and str(cfg) == "2" \
+    if rank == 0 and world == 1 and extras and args.mode == "fwd" and str(cfg) == "2" \
             and args.precision == "fp32":
         # the other BASELINE.json configurations, bounded to a few seconds each, so that the driver's N = 1 line
         # carries them: configs[2] (cfg 3 train step), configs[4] (cfg 5, fp32 and bf16 storage), predict(), and the
@@ -1313,7 +1353,7 @@ def main():
         guarded("proposals", lambda: proposals_record(yv))
         guarded("nms", lambda: nms_record(yv))
         guarded("train_dp_single_rank_nccl", lambda: single_rank_nccl_dp_record(yv, gu))
-    if world > 1 and not args.no_extras:
+    if world > 1 and extras:
         # the data-parallel training step (north_star: RCCL all-reduce of gradients over xGMI) next to the replicas
         train_dp = train_dp_record(yv, gu, rank, world, steps=max(min(args.steps, 50), 10), warmup=args.warmup)
 

@@ -223,7 +223,7 @@ def test_bench_train_dp_record_with_two_ranks_carries_both_exchange_layouts():
         env.pop(k, None)
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                         "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.join(root, "bench.py"),
-                        "--gpus", "2", "--steps", "20", "--warmup", "5", "--no-cpu-baseline", "--no-roofline"],
+                        "--gpus", "2", "--steps", "20", "--warmup", "5", "--full", "--no-cpu-baseline", "--no-roofline"],
                        env=env, cwd=root, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
