@@ -762,8 +762,10 @@ int yolat_forward_eval_bf16_csr(const yolat_model_eval_bf16* m, const float* x, 
  *   yolat_train_model: pointers into ONE flat parameter buffer (param_base) and its gradient twin (grad_base, same
  *     offsets: trainer.FlatParams); BatchNorm running statistics / counters are updated in place.
  *   Shapes: n_filters C = 64, n_blocks_out = 2, biases and BatchNorm on every layer, no dropout, E >= N; `half` != 0:
- *     bfloat16 storage of the per-edge tensors where E >= 2 N.  Anything else: YOLAT_E_UNSUPPORTED (the caller keeps its
- *     own schedule).
+ *     bfloat16 storage of the per-edge tensors where E >= 2 N; bit 2 of `half` (half = 3) additionally selects the
+ *     "bf16_dense" head (fusion_block, fusion_block_super, prediction_cls.0 / .1 on the yolat_bt_* / _bf16 entry points;
+ *     F % 64 == 0, H1 % 32 == 0, H2 % 32 == 0, 16-byte aligned weights of those layers).  Anything else:
+ *     YOLAT_E_UNSUPPORTED (the caller keeps its own schedule).
  *   Batch: the collated COO arrays (edge / e_attr / bbox_idx; the destination-sorted form is built inside the call), or a
  *     prepared graph g.  labels [P] int64.  logits [P, ld_logits] and loss [1] are written; *status as yolat_graph_prepare.
  *   phases (bit mask): 1 = graph + forward + loss + backward of the classifier and the fusion blocks — on return every
@@ -1071,6 +1073,40 @@ int yolat_proposals_assemble(const yolat_proposals* p, const double* pos, const 
                              int64_t* new_edge_super, double* new_e_attr_super, int64_t* labels, int64_t* has_obj,
                              int64_t* bbox_idx, double* bbox_targets, double* stat);
 void yolat_proposals_free(yolat_proposals* p);
+
+/* ------------------------------------------------------------------------------------------
+ * "bf16_dense" training precision (bf16_train.hip, fusion_train.hip): the dense layers behind the conv stack on bf16
+ * MFMA — every operand rounded to nearest even from fp32 inside the kernel, fp32 accumulation; bias, BatchNorm
+ * statistics, column sums and split-K sums in fp32 in a fixed order (deterministic).  No weight image outlives a call.
+ *   yolat_bt_linear_fwd     Y [M,N] = pro(A) [M,K] . W [N,K]^T + bias; stats (nullable): BatchNorm partials as
+ *                           yolat_linear_fwd writes them (yolat_bn_stats_elems(M, N)).  K % 32 == 0.
+ *   yolat_bt_linear_fwd_wt  Y [M,N] (+)= A [M,K] . Wt [K,N].  K % 32 == 0, N % 8 == 0.
+ *   yolat_bt_linear_bwd_w   dW [N,K] = dY [M,N]^T . pro(A) [M,K], db [N] (nullable) = fp32 column sums of dY;
+ *                           work: yolat_bt_linear_bwd_w_work_elems(M, N, K) floats.  N % 8 == 0, K % 8 == 0.
+ * pro(A) = relu?(a_scale[k] a + a_shift[k]) when a_scale / a_shift are given.  All pointers 16-byte aligned, leading
+ * dimensions % 4 == 0; anything else returns YOLAT_E_UNSUPPORTED (the caller reports it: there is no fp32 fall-back).
+ * yolat_fusion_pool_train_fwd_bf16 / _bwd_parts_bf16: yolat_fusion_pool_train_fwd / _bwd_parts with the fusion GEMM
+ * (extreme-of-z key epilogue) and the sparse dA GEMM on bf16 operands; statistics and dW as in fp32.  K == 128,
+ * F % 64 == 0.                                                                                                        */
+int yolat_bt_linear_fwd(const float* A, int64_t lda, int64_t M, int64_t K, const float* a_scale, const float* a_shift,
+                        int a_relu, const float* W, int64_t ldw, const float* bias, int64_t N, float* Y, int64_t ldy,
+                        float* stats, yolat_stream_t stream);
+int yolat_bt_linear_fwd_wt(const float* A, int64_t lda, int64_t M, int64_t K, const float* Wt, int64_t ldw, int64_t N,
+                           float* Y, int64_t ldy, int accumulate, yolat_stream_t stream);
+size_t yolat_bt_linear_bwd_w_work_elems(int64_t M, int64_t N, int64_t K);
+int yolat_bt_linear_bwd_w(const float* dY, int64_t ldd, int64_t M, int64_t N, const float* A, int64_t lda, int64_t K,
+                          const float* a_scale, const float* a_shift, int a_relu, float* dW, int64_t lddw, float* db,
+                          float* work, yolat_stream_t stream);
+int yolat_fusion_pool_train_fwd_bf16(const float* A, int64_t lda, int64_t N, int64_t K, const float* W,
+                                     const float* bias, int64_t F, const float* gamma, const float* beta,
+                                     float* running_mean, float* running_var, float momentum, float eps,
+                                     const int32_t* node_seg, int64_t P, float* Z, int64_t ldz, float* coef,
+                                     float* saved, float* work, yolat_stream_t stream);
+int yolat_fusion_pool_train_bwd_parts_bf16(const float* A, int64_t lda, int64_t N, int64_t K, const float* W,
+                                           const float* gamma, int64_t F, const float* coef, const float* saved,
+                                           const int32_t* node_seg, const int32_t* seg_ptr, int64_t P, const float* gZ,
+                                           int64_t ldg, float* dW, float* dbias, float* dgamma, float* dbeta, float* dA,
+                                           int64_t ldda, float* work, int parts, yolat_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -149,6 +149,16 @@ SIGNATURES = {
                                              c_i64, c_p, c_p, c_p, c_p, c_p, c_i64, c_p, c_p]),
     "yolat_fusion_pool_train_bwd_parts": (c_int, [c_p, c_i64, c_i64, c_i64, c_p, c_p, c_i64, c_p, c_p, c_p, c_p, c_i64, c_p,
                                                    c_i64, c_p, c_p, c_p, c_p, c_p, c_i64, c_p, c_int, c_p]),
+    # "bf16_dense" training precision (bf16_train.hip)
+    "yolat_fusion_pool_train_fwd_bf16": (c_int, [c_p, c_i64, c_i64, c_i64, c_p, c_p, c_i64, c_p, c_p, c_p, c_p, c_f, c_f,
+                                                  c_p, c_i64, c_p, c_i64, c_p, c_p, c_p, c_p]),
+    "yolat_fusion_pool_train_bwd_parts_bf16": (c_int, [c_p, c_i64, c_i64, c_i64, c_p, c_p, c_i64, c_p, c_p, c_p, c_p, c_i64,
+                                                        c_p, c_i64, c_p, c_p, c_p, c_p, c_p, c_i64, c_p, c_int, c_p]),
+    "yolat_bt_linear_fwd": (c_int, [c_p, c_i64, c_i64, c_i64, c_p, c_p, c_int, c_p, c_i64, c_p, c_i64, c_p, c_i64, c_p, c_p]),
+    "yolat_bt_linear_fwd_wt": (c_int, [c_p, c_i64, c_i64, c_i64, c_p, c_i64, c_i64, c_p, c_i64, c_int, c_p]),
+    "yolat_bt_linear_bwd_w_work_elems": (c_sz, [c_i64, c_i64, c_i64]),
+    "yolat_bt_linear_bwd_w": (c_int, [c_p, c_i64, c_i64, c_i64, c_p, c_i64, c_i64, c_p, c_p, c_int, c_p, c_i64, c_p, c_p,
+                                       c_p]),
     "yolat_expand_ranges": (c_int, [c_p, c_p, c_i64, c_i64, c_p, c_p]),
     "yolat_subgraph_work_elems": (c_sz, [c_i64, c_i64]),
     "yolat_subgraph_reindex": (c_int, [c_p, c_i64, c_i64, c_p, c_i64, c_i64, c_p, c_i64, c_p, c_p, c_p, c_p, c_p, c_p]),

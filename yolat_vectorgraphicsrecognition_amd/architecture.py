@@ -375,12 +375,21 @@ class SparseCADGCN(nn.Module):
         return self
 
     def set_train_precision(self, precision="fp32"):
-        """Storage precision of the training step's per-edge tensors: "fp32" (default, the parity mode) or "bf16" —
-        the [E,64] activations of the edge MLP and their gradients are stored as bfloat16 (fp32 accumulation,
-        statistics, parameters, optimizer); used where the factorised edge layer applies (E >= 2 N).  Gradients agree
-        with the fp32 step to ~1e-2 (tests/test_gpu_bf16.py)."""
-        if precision not in ("fp32", "bf16"):
-            raise ValueError("precision must be 'fp32' or 'bf16'")
+        """Precision of the training step.
+
+        "fp32" (default, the parity mode).
+        "bf16": storage precision of the per-edge tensors — the [E,64] activations of the edge MLP and their gradients
+            are stored as bfloat16 (fp32 accumulation, statistics, parameters, optimizer); used where the factorised edge
+            layer applies (E >= 2 N).  Gradients agree with the fp32 step to ~1e-2 (tests/test_gpu_bf16.py).
+        "bf16_dense": "bf16", plus the dense layers behind the conv stack on bf16 operands with fp32 accumulation
+            (csrc/bf16_train.hip): fusion_block (forward GEMM with the per-proposal extreme epilogue, the dA GEMM of its
+            sparse backward), fusion_block_super and prediction_cls.0 / .1 (forward with the BatchNorm-statistics
+            epilogue, dX, dW).  Operands are rounded to nearest even from fp32; BatchNorm statistics, every reduction,
+            parameters, gradients and Adam state, the fusion block's sparse dW, prediction_cls.2 and the conv stack stay
+            as in "bf16".  Needs fusion_dims = 128 and feature counts that are multiples of 32 (fusion_block: of 64);
+            other shapes raise ValueError at the first step.  Numerics contract: INTEGRATION.md."""
+        if precision not in ("fp32", "bf16", "bf16_dense"):
+            raise ValueError("precision must be 'fp32', 'bf16' or 'bf16_dense'")
         self.__dict__["_yolat_train_precision"] = precision
         return self
 

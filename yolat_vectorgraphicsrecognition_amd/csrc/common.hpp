@@ -843,6 +843,10 @@ int yl_node3_smallk(const NodeUv& a, hipStream_t st, YlGate gate = YlGate{nullpt
 int yl_fusion_rows_x6_key64(const float* A, long lda, long N, long K, const float* W, const float* bias, long F,
                             const float* sgn, const int* node_seg, unsigned long long* keys, uint16_t* wsplit,
                             yolat_stream_t stream);
+// the same on bf16 operands ("bf16_dense" training precision, bf16_train.hip): K == 128; wimg = F * K bfloat16
+int yl_fusion_rows_bf16_key64(const float* A, long lda, long N, long K, const float* W, const float* bias, long F,
+                              const float* sgn, const int* node_seg, unsigned long long* keys, uint16_t* wimg,
+                              yolat_stream_t stream);
 // ------------------------------------------------------------------------------------------------
 // Pooling prologue as a RIDER of other launches (small graphs, where a launch of its own is ~5 us of latency):
 // the parts of k_pool_prepare (segment.hip) done by `blocks` extra workgroups appended to a kernel whose own

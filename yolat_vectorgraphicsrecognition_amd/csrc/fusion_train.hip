@@ -238,17 +238,19 @@ extern "C" size_t yolat_fusion_pool_train_work_elems(int64_t N, int64_t K, int64
   return (fwd > bwd ? fwd : bwd) + 64;
 }
 
-extern "C" int yolat_fusion_pool_train_fwd(const float* A, int64_t lda, int64_t N, int64_t K, const float* W,
-                                           const float* bias, int64_t F, const float* gamma, const float* beta,
-                                           float* running_mean, float* running_var, float momentum, float eps,
-                                           const int32_t* node_seg, int64_t P, float* Z, int64_t ldz, float* coef,
-                                           float* saved, float* work, yolat_stream_t stream) {
+// bf16 != 0: the "bf16_dense" training precision — step 4 on bf16 operands (bf16_train.hip), K = 128 and F % 64 == 0
+// only (no fall-back: anything else is YOLAT_E_UNSUPPORTED); steps 1-3 (the statistics) are the fp32 ones
+static int fus_train_fwd(const float* A, int64_t lda, int64_t N, int64_t K, const float* W, const float* bias, int64_t F,
+                         const float* gamma, const float* beta, float* running_mean, float* running_var, float momentum,
+                         float eps, const int32_t* node_seg, int64_t P, float* Z, int64_t ldz, float* coef, float* saved,
+                         float* work, int bf16, yolat_stream_t stream) {
   if (N <= 0 || K <= 0 || F <= 0 || P <= 0 || !A || !W || !gamma || !beta || !node_seg || !Z || !coef || !saved ||
       !work)
     return YOLAT_E_INVALID;
   if (lda < K || ldz < F || N >= (1LL << 31) || (running_mean == nullptr) != (running_var == nullptr))
     return YOLAT_E_INVALID;
   if (K % 4 != 0 || lda % 4 != 0) return YOLAT_E_UNSUPPORTED;
+  if (bf16 && (K != 128 || F % 64 != 0 || bias == nullptr || !yl_aligned16(A))) return YOLAT_E_UNSUPPORTED;
   hipStream_t st = (hipStream_t)stream;
   FusSaved sv = fus_saved(saved, K, F, P);
   float* colpart = work;
@@ -308,7 +310,11 @@ extern "C" int yolat_fusion_pool_train_fwd(const float* A, int64_t lda, int64_t 
   // split lives behind the keys in `work`)
   const int use_x6 = yl_strict_fp32() ? 0 : 1;
   int x6rc = YOLAT_E_UNSUPPORTED;
-  if (use_x6 && bias != nullptr) {
+  if (bf16) {
+    uint16_t* wimg = reinterpret_cast<uint16_t*>(((uintptr_t)(keys + (size_t)P * F) + 15) & ~(uintptr_t)15);
+    x6rc = yl_fusion_rows_bf16_key64(A, lda, N, K, W, bias, F, coef, node_seg, keys, wimg, stream);
+    if (x6rc != 0) return x6rc;
+  } else if (use_x6 && bias != nullptr) {
     uint16_t* wsplit = reinterpret_cast<uint16_t*>(((uintptr_t)(keys + (size_t)P * F) + 15) & ~(uintptr_t)15);
     x6rc = yl_fusion_rows_x6_key64(A, lda, N, K, W, bias, F, coef, node_seg, keys, wsplit, stream);
     if (x6rc != 0 && x6rc != YOLAT_E_UNSUPPORTED) return x6rc;
@@ -332,6 +338,24 @@ extern "C" int yolat_fusion_pool_train_fwd(const float* A, int64_t lda, int64_t 
     YL_LAUNCH_CHECK();
   }
   return 0;
+}
+
+extern "C" int yolat_fusion_pool_train_fwd(const float* A, int64_t lda, int64_t N, int64_t K, const float* W,
+                                           const float* bias, int64_t F, const float* gamma, const float* beta,
+                                           float* running_mean, float* running_var, float momentum, float eps,
+                                           const int32_t* node_seg, int64_t P, float* Z, int64_t ldz, float* coef,
+                                           float* saved, float* work, yolat_stream_t stream) {
+  return fus_train_fwd(A, lda, N, K, W, bias, F, gamma, beta, running_mean, running_var, momentum, eps, node_seg, P, Z,
+                       ldz, coef, saved, work, 0, stream);
+}
+
+extern "C" int yolat_fusion_pool_train_fwd_bf16(const float* A, int64_t lda, int64_t N, int64_t K, const float* W,
+                                                const float* bias, int64_t F, const float* gamma, const float* beta,
+                                                float* running_mean, float* running_var, float momentum, float eps,
+                                                const int32_t* node_seg, int64_t P, float* Z, int64_t ldz, float* coef,
+                                                float* saved, float* work, yolat_stream_t stream) {
+  return fus_train_fwd(A, lda, N, K, W, bias, F, gamma, beta, running_mean, running_var, momentum, eps, node_seg, P, Z,
+                       ldz, coef, saved, work, 1, stream);
 }
 
 // =================================================================================================
@@ -626,7 +650,17 @@ static __global__ void k_wt_split2(const float* __restrict__ W, int F, int K, un
   WTm[i] = (unsigned short)(__float_as_uint(r) >> 16);
 }
 
-template <int CH>
+// WT [K][F] bf16 = W[c][k] rounded to nearest even (the "bf16_dense" training precision: one image, one product)
+static __global__ void k_wt_bf16(const float* __restrict__ W, int F, int K, unsigned short* __restrict__ WT) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;          // (k, c), c fastest
+  if (i >= F * K) return;
+  const int k = i / F, c = i - k * F;
+  WT[i] = (unsigned short)(yl_pack_bf16(W[(long)c * K + k], 0.f) & 0xFFFFu);
+}
+
+// ONE = true ("bf16_dense"): WTh is the single round-to-nearest image of k_wt_bf16 (WTm unused), the A operand is rounded
+// the same way and each 16 columns take ONE product a b instead of three
+template <int CH, bool ONE = false>
 static __global__ void __launch_bounds__(512, (CH == 32 ? 4 : 2)) k_fus_da_mfma(const unsigned short* __restrict__ WTh,
                                                           const unsigned short* __restrict__ WTm, int F,
                                                           const int* __restrict__ node_seg, int P,
@@ -634,9 +668,10 @@ static __global__ void __launch_bounds__(512, (CH == 32 ? 4 : 2)) k_fus_da_mfma(
                                                           int N, float* dA, long ldda) {
   constexpr int RS = CH + 8;                              // CH columns per LDS chunk, row stride (bf16)
   constexpr int NPL = 32, PS = CH + 4;                    // proposals whose arg / GM chunk is staged in LDS, row stride
-  constexpr int WPT = 2 * 128 * (CH / 8) / 512;           // 16-byte W^T pieces per thread (2 planes x 128 k rows)
+  constexpr int NPL_W = ONE ? 1 : 2;                      // planes of W^T
+  constexpr int WPT = NPL_W * 128 * (CH / 8) / 512;       // 16-byte W^T pieces per thread (planes x 128 k rows)
   constexpr int SQN = CH / 4;                             // arg / GM staging: column quads per proposal
-  __shared__ __attribute__((aligned(16))) unsigned short Ws[2][2][128 * RS];     // [buffer][plane][k row][c]
+  __shared__ __attribute__((aligned(16))) unsigned short Ws[2][NPL_W][128 * RS];     // [buffer][plane][k row][c]
   __shared__ __attribute__((aligned(16))) int argS[2][NPL * PS];
   __shared__ __attribute__((aligned(16))) float gmS[2][NPL * PS];
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, l31 = lane & 31, lhi = lane >> 5;
@@ -714,6 +749,20 @@ static __global__ void __launch_bounds__(512, (CH == 32 ? 4 : 2)) k_fus_da_mfma(
       }
       const int av[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
       const float gv[8] = {g0.x, g0.y, g0.z, g0.w, g1.x, g1.y, g1.z, g1.w};
+      if constexpr (ONE) {
+        unsigned pr[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+          pr[i] = yl_pack_bf16(av[2 * i] == myrow ? gv[2 * i] : 0.f, av[2 * i + 1] == myrow ? gv[2 * i + 1] : 0.f);
+        const ft_u32x4 qr = {pr[0], pr[1], pr[2], pr[3]};
+        const ft_bf16x8 Ar = __builtin_bit_cast(ft_bf16x8, qr);
+        const unsigned short* br = &Ws[buf][0][l31 * RS + 16 * ks + 8 * lhi];
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Ar, *reinterpret_cast<const ft_bf16x8*>(br + 32 * j * RS), acc[j],
+                                                          0, 0, 0);
+        continue;
+      }
       unsigned ph[4], pm[4];
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
@@ -726,7 +775,7 @@ static __global__ void __launch_bounds__(512, (CH == 32 ? 4 : 2)) k_fus_da_mfma(
       const ft_u32x4 qh = {ph[0], ph[1], ph[2], ph[3]}, qm = {pm[0], pm[1], pm[2], pm[3]};
       const ft_bf16x8 Ah = __builtin_bit_cast(ft_bf16x8, qh), Am = __builtin_bit_cast(ft_bf16x8, qm);
       const unsigned short* bh = &Ws[buf][0][l31 * RS + 16 * ks + 8 * lhi];
-      const unsigned short* bm = &Ws[buf][1][l31 * RS + 16 * ks + 8 * lhi];
+      const unsigned short* bm = &Ws[buf][NPL_W - 1][l31 * RS + 16 * ks + 8 * lhi];
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const ft_bf16x8 Bh = *reinterpret_cast<const ft_bf16x8*>(bh + 32 * j * RS);
@@ -800,12 +849,13 @@ extern "C" int yolat_fusion_pool_train_bwd(const float* A, int64_t lda, int64_t 
 // The same backward in parts (bit mask), for a caller that runs the weight gradient beside the input gradient on a second
 // stream: YOLAT_FUS_BWD_COLS (the per-column reductions: dgamma, dbeta and the coefficient vectors both other parts read)
 // must be complete — stream order or an event — before _DW and _DA, which write disjoint regions of `work`.
-extern "C" int yolat_fusion_pool_train_bwd_parts(const float* A, int64_t lda, int64_t N, int64_t K, const float* W,
-                                                 const float* gamma, int64_t F, const float* coef, const float* saved,
-                                                 const int32_t* node_seg, const int32_t* seg_ptr, int64_t P,
-                                                 const float* gZ, int64_t ldg, float* dW, float* dbias, float* dgamma,
-                                                 float* dbeta, float* dA, int64_t ldda, float* work, int parts,
-                                                 yolat_stream_t stream) {
+// bf16 != 0 ("bf16_dense"): the sparse scatter term of dA on ONE round-to-nearest bf16 image of W^T (k_wt_bf16,
+// k_fus_da_mfma<32, true>); F % 64 == 0 only.  Everything else is the fp32 backward.
+static int fus_train_bwd_parts(const float* A, int64_t lda, int64_t N, int64_t K, const float* W, const float* gamma,
+                               int64_t F, const float* coef, const float* saved, const int32_t* node_seg,
+                               const int32_t* seg_ptr, int64_t P, const float* gZ, int64_t ldg, float* dW, float* dbias,
+                               float* dgamma, float* dbeta, float* dA, int64_t ldda, float* work, int parts, int bf16,
+                               yolat_stream_t stream) {
   (void)gamma; (void)seg_ptr;
   if ((parts & ~YOLAT_FUS_BWD_ALL) != 0 || parts == 0) return YOLAT_E_INVALID;
   if (N <= 0 || K <= 0 || F <= 0 || P <= 0 || !A || !W || !coef || !saved || !node_seg || !gZ || !dW || !dgamma ||
@@ -814,6 +864,7 @@ extern "C" int yolat_fusion_pool_train_bwd_parts(const float* A, int64_t lda, in
   if (lda < K || ldg < F || ldda < K || N >= (1LL << 31)) return YOLAT_E_INVALID;
   if (K != 128 || F % 32 != 0 || lda % 4 != 0 || ldda % 4 != 0 || ((uintptr_t)dA & 15) != 0)
     return YOLAT_E_UNSUPPORTED;
+  if (bf16 && (F % 64 != 0 || F < 64)) return YOLAT_E_UNSUPPORTED;
   hipStream_t st = (hipStream_t)stream;
   FusSaved sv = fus_saved(const_cast<float*>(saved), K, F, P);
   const int PB = yl_cdiv(P, FB_PROWS);
@@ -857,7 +908,13 @@ extern "C" int yolat_fusion_pool_train_bwd_parts(const float* A, int64_t lda, in
   // the matrix-core form splits the operands into TWO bf16 terms (three products, 2^-16 per product): not under
   // YOLAT_STRICT_FP32, which promises fp32 arithmetic / IEEE propagation for every GEMM of the fp32 mode
   const int da_mfma = yl_strict_fp32() ? 0 : 1, da_ch = 32;
-  if (da_mfma && F % 64 == 0 && F >= 64) {
+  if (bf16) {
+    unsigned short* WT = reinterpret_cast<unsigned short*>(take((size_t)F * K / 2 + 8));
+    hipLaunchKernelGGL(k_wt_bf16, dim3(yl_cdiv(F * K, 256)), dim3(256), 0, st, W, (int)F, (int)K, WT);
+    YL_LAUNCH_CHECK();
+    hipLaunchKernelGGL((k_fus_da_mfma<32, true>), dim3(yl_cdiv(N, 256)), dim3(512), 0, st, WT, WT, (int)F, node_seg, (int)P,
+                       GM, sv.arg, (int)N, dA, (long)ldda);
+  } else if (da_mfma && F % 64 == 0 && F >= 64) {
     unsigned short* WTh = reinterpret_cast<unsigned short*>(take((size_t)F * K / 2 + 8));
     unsigned short* WTm = reinterpret_cast<unsigned short*>(take((size_t)F * K / 2 + 8));
     hipLaunchKernelGGL(k_wt_split2, dim3(yl_cdiv(F * K, 256)), dim3(256), 0, st, W, (int)F, (int)K, WTh, WTm);
@@ -886,4 +943,24 @@ extern "C" int yolat_fusion_pool_train_bwd_parts(const float* A, int64_t lda, in
   YL_TRY(yolat_linear_fwd(A, lda, N, K, sv.ones, sv.negmean, 0, nQ, K, nu, K, nullptr, nullptr, 0, dA, ldda, 1, nullptr,
                           stream));
   return 0;
+}
+
+extern "C" int yolat_fusion_pool_train_bwd_parts(const float* A, int64_t lda, int64_t N, int64_t K, const float* W,
+                                                 const float* gamma, int64_t F, const float* coef, const float* saved,
+                                                 const int32_t* node_seg, const int32_t* seg_ptr, int64_t P,
+                                                 const float* gZ, int64_t ldg, float* dW, float* dbias, float* dgamma,
+                                                 float* dbeta, float* dA, int64_t ldda, float* work, int parts,
+                                                 yolat_stream_t stream) {
+  return fus_train_bwd_parts(A, lda, N, K, W, gamma, F, coef, saved, node_seg, seg_ptr, P, gZ, ldg, dW, dbias, dgamma, dbeta,
+                             dA, ldda, work, parts, 0, stream);
+}
+
+extern "C" int yolat_fusion_pool_train_bwd_parts_bf16(const float* A, int64_t lda, int64_t N, int64_t K, const float* W,
+                                                      const float* gamma, int64_t F, const float* coef, const float* saved,
+                                                      const int32_t* node_seg, const int32_t* seg_ptr, int64_t P,
+                                                      const float* gZ, int64_t ldg, float* dW, float* dbias, float* dgamma,
+                                                      float* dbeta, float* dA, int64_t ldda, float* work, int parts,
+                                                      yolat_stream_t stream) {
+  return fus_train_bwd_parts(A, lda, N, K, W, gamma, F, coef, saved, node_seg, seg_ptr, P, gZ, ldg, dW, dbias, dgamma, dbeta,
+                             dA, ldda, work, parts, 1, stream);
 }

@@ -11,8 +11,11 @@
 //
 // Covered: the reference recipe's shapes on the default schedule of engine.py — n_filters 64, n_blocks_out 2 (fusion dims
 // 128: the fused fusion block), Linear biases and BatchNorm everywhere, no dropout, softmax classifier, E >= N (the
-// factorised backward of the first edge Linear) — fp32 and bf16 storage of the per-edge tensors.  Anything else returns
-// YOLAT_E_UNSUPPORTED and the caller keeps the Python schedule (trainer.Trainer does).
+// factorised backward of the first edge Linear) — fp32 and bf16 storage of the per-edge tensors, and the "bf16_dense"
+// precision (half bit 2: fusion_block, fusion_block_super and prediction_cls.0 / .1 on the bf16-operand kernels of
+// bf16_train.hip and the _bf16 fusion entry points, as engine.py issues them for that mode; needs F % 64 == 0,
+// H1 % 32 == 0, H2 % 32 == 0 and 16-byte aligned weights of those layers).  Anything else returns YOLAT_E_UNSUPPORTED
+// and the caller keeps the Python schedule (trainer.Trainer does).
 //
 // Streams.  `side` != NULL: the weight gradients and the node branches run on it beside the dX chain, forked behind an
 // event on `stream` at every hand-over and joined in front of the classifier, before the head bucket is declared complete
@@ -74,6 +77,7 @@ struct TrainBuf {
   float* d2; float* d1; float* dZ; float* d_fsup; float* d_feats;
   float* w3; float* w2bn; float* w2w; uint16_t* p2; float* x2w; float* w1bn; float* w1w; uint16_t* p1; float* x1w;
   float* wfsbn; float* wfsw;
+  float* bt_w2; float* bt_w1; float* bt_wfs;     // "bf16_dense": split-K / column-sum scratch of the three dW GEMMs
   size_t bytes;
 };
 
@@ -153,6 +157,11 @@ TrainBuf carve(const yolat_train_model* m, long N, long E, long P, void* ws) {
   b.p1 = c.take<uint16_t>(yolat_gemm_x6_packed_elems(ZW, m->H1));
   b.x1w = c.take<float>(yolat_gemm_x6_work_elems(P, ZW, m->H1) + 1);
   b.wfsbn = c.take<float>(yolat_bn_bwd_work_elems(P, F)); b.wfsw = c.take<float>(yolat_linear_bwd_w_work_elems(P, F, D));
+  if (m->half & 2) {
+    b.bt_w2 = c.take<float>(yolat_bt_linear_bwd_w_work_elems(P, m->H2, m->H1));
+    b.bt_w1 = c.take<float>(yolat_bt_linear_bwd_w_work_elems(P, m->H1, ZW));
+    b.bt_wfs = c.take<float>(yolat_bt_linear_bwd_w_work_elems(P, F, D));
+  }
   b.bytes = c.off + 256;
   return b;
 }
@@ -162,6 +171,8 @@ int model_ok(const yolat_train_model* m) {
   if (m->n_blocks < 1 || m->n_blocks > TP_MAXL || m->n_blocks_out < 1 || m->n_blocks_out > m->n_blocks || m->n_classes < 1)
     return YOLAT_E_INVALID;
   if (m->C != 64 || m->n_blocks_out != 2 || m->F <= 0 || m->F % 4 != 0 || m->H1 <= 0 || m->H2 <= 0) return YOLAT_E_UNSUPPORTED;
+  if ((m->half & ~3) != 0) return YOLAT_E_INVALID;
+  if ((m->half & 2) && (m->F % 64 != 0 || m->H1 % 32 != 0 || m->H2 % 32 != 0)) return YOLAT_E_UNSUPPORTED;
   auto lin_ok = [](const yolat_train_lin& l) { return l.W != nullptr && l.b != nullptr; };
   auto bn_ok = [](const yolat_train_bn& b) { return b.gamma != nullptr && b.beta != nullptr; };
   for (int l = 0; l < m->n_blocks; ++l) {
@@ -296,6 +307,9 @@ extern "C" int yolat_train_step(const yolat_train_model* m, const float* x, int6
   for (long l = 0; l < L; ++l)
     if ((((uintptr_t)m->conv[l].nn3.W) & 15) != 0) return YOLAT_E_UNSUPPORTED;
   if ((((uintptr_t)m->fus.W) & 15) != 0) return YOLAT_E_UNSUPPORTED;
+  // "bf16_dense": the bf16-operand GEMMs read the weights in 16-byte pieces (ops._bt_aligned copies an unaligned view)
+  const bool dense = (m->half & 2) != 0;
+  if (dense && ((((uintptr_t)m->fus_s.W) | ((uintptr_t)m->c1.W) | ((uintptr_t)m->c2.W)) & 15) != 0) return YOLAT_E_UNSUPPORTED;
 
   Streams S;
   S.main = (hipStream_t)stream;
@@ -336,9 +350,11 @@ extern "C" int yolat_train_step(const yolat_train_model* m, const float* x, int6
     // their results are first needed, on the main stream; same kernels, same operands.)
     {
       hipStream_t ss = S.fork();
-      if (x6_fwd(b.Z, ZW, P, ZW, H1, false, true, true)) TP_TRY(yolat_gemm_x6_pack(m->c1.W, ZW, H1, ZW, nullptr, b.c1pack, ss));
-      if (x6_wt(b.d2, H2, P, H2, H1, false)) TP_TRY(yolat_gemm_x6_pack_t(m->c2.W, H1, H1, H2, b.p2, ss));
-      if (x6_wt(b.d1, H1, P, H1, ZW, false)) TP_TRY(yolat_gemm_x6_pack_t(m->c1.W, ZW, ZW, H1, b.p1, ss));
+      if (!dense) {      // (bf16_dense: the classifier GEMMs read the fp32 weights and round them themselves)
+        if (x6_fwd(b.Z, ZW, P, ZW, H1, false, true, true)) TP_TRY(yolat_gemm_x6_pack(m->c1.W, ZW, H1, ZW, nullptr, b.c1pack, ss));
+        if (x6_wt(b.d2, H2, P, H2, H1, false)) TP_TRY(yolat_gemm_x6_pack_t(m->c2.W, H1, H1, H2, b.p2, ss));
+        if (x6_wt(b.d1, H1, P, H1, ZW, false)) TP_TRY(yolat_gemm_x6_pack_t(m->c1.W, ZW, ZW, H1, b.p1, ss));
+      }
       for (long l = 0; l < L; ++l)
         if (!b.cv[l].fact_fwd) TP_TRY(yolat_conv_split_w1(m->conv[l].nn0.W, m->conv[l].Cin, C, b.cv[l].wuv_b, b.cv[l].wc4_b, ss));
       // CSC by source + 1 / deg for the backward (ops.Graph.ensure_csc / inv_deg)
@@ -404,19 +420,28 @@ extern "C" int yolat_train_step(const yolat_train_model* m, const float* x, int6
       float* sup = b.Z + 2 * F + D;
       TP_TRY(yolat_segment_max_fwd(b.feats, D, D, nullptr, nullptr, 0, seg_ptr, P, N, b.Z + F, ZW, b.arg_feat, ss));
       TP_TRY(yolat_segment_mean_fwd(b.fsup, D, D, b.sup_coef, b.sup_coef + D, 1, seg_ptr, P, sup, ZW, ss));
-      TP_TRY(lin_fwd(sup, ZW, P, D, nullptr, nullptr, 0, m->fus_s.W, m->fus_s.b, F, b.fs_y, F, b.fs_st, nullptr, false, ss));
+      if (dense)
+        TP_TRY(yolat_bt_linear_fwd(sup, ZW, P, D, nullptr, nullptr, 0, m->fus_s.W, D, m->fus_s.b, F, b.fs_y, F, b.fs_st, ss));
+      else
+        TP_TRY(lin_fwd(sup, ZW, P, D, nullptr, nullptr, 0, m->fus_s.W, m->fus_s.b, F, b.fs_y, F, b.fs_st, nullptr, false, ss));
       TP_TRY(finalize(b.fs_st, P, F, m->fus_s_bn, b.fs_c, b.fs_c + F, b.fs_c + 2 * F, b.fs_c + 3 * F, ss));
       TP_TRY(yolat_scale_shift_relu(b.fs_y, F, P, F, b.fs_c, b.fs_c + F, 1, b.Z + F + D, ZW, ss));
     }
     // fusion block over nodes + per-proposal max (arch:61-63,122): fused, no [N, F] activation
-    TP_TRY(yolat_fusion_pool_train_fwd(b.feats, D, N, D, m->fus.W, m->fus.b, F, m->fus_bn.gamma, m->fus_bn.beta,
-                                       m->fus_bn.running_mean, m->fus_bn.running_var, m->fus_bn.momentum, m->fus_bn.eps, node_seg,
-                                       P, b.Z, ZW, b.fus_coef, b.fus_saved, b.fus_work, st));
+    TP_TRY((dense ? yolat_fusion_pool_train_fwd_bf16 : yolat_fusion_pool_train_fwd)(
+        b.feats, D, N, D, m->fus.W, m->fus.b, F, m->fus_bn.gamma, m->fus_bn.beta, m->fus_bn.running_mean, m->fus_bn.running_var,
+        m->fus_bn.momentum, m->fus_bn.eps, node_seg, P, b.Z, ZW, b.fus_coef, b.fus_saved, b.fus_work, st));
     S.join();                          // Z is complete: node branches, pooled rows, fusion_block_super, the weight packs
     // classifier (arch:91-93,128)
-    TP_TRY(lin_fwd(b.Z, ZW, P, ZW, nullptr, nullptr, 0, m->c1.W, m->c1.b, H1, b.c1y, H1, b.c1st, b.c1pack, true, st));
+    if (dense)
+      TP_TRY(yolat_bt_linear_fwd(b.Z, ZW, P, ZW, nullptr, nullptr, 0, m->c1.W, ZW, m->c1.b, H1, b.c1y, H1, b.c1st, st));
+    else
+      TP_TRY(lin_fwd(b.Z, ZW, P, ZW, nullptr, nullptr, 0, m->c1.W, m->c1.b, H1, b.c1y, H1, b.c1st, b.c1pack, true, st));
     TP_TRY(finalize(b.c1st, P, H1, m->c1_bn, b.c1c, b.c1c + H1, b.c1c + 2 * H1, b.c1c + 3 * H1, st));
-    TP_TRY(lin_fwd(b.c1y, H1, P, H1, b.c1c, b.c1c + H1, 1, m->c2.W, m->c2.b, H2, b.c2y, H2, b.c2st, nullptr, false, st));
+    if (dense)
+      TP_TRY(yolat_bt_linear_fwd(b.c1y, H1, P, H1, b.c1c, b.c1c + H1, 1, m->c2.W, H1, m->c2.b, H2, b.c2y, H2, b.c2st, st));
+    else
+      TP_TRY(lin_fwd(b.c1y, H1, P, H1, b.c1c, b.c1c + H1, 1, m->c2.W, m->c2.b, H2, b.c2y, H2, b.c2st, nullptr, false, st));
     TP_TRY(finalize(b.c2st, P, H2, m->c2_bn, b.c2c, b.c2c + H2, b.c2c + 2 * H2, b.c2c + 3 * H2, st));
     TP_TRY(yolat_linear_fwd(b.c2y, H2, P, H2, b.c2c, b.c2c + H2, 1, m->c3.W, H2, m->c3.b, K, nullptr, nullptr, 0, logits, ld_logits,
                             0, nullptr, st));
@@ -442,15 +467,27 @@ extern "C" int yolat_train_step(const yolat_train_model* m, const float* x, int6
     // prediction_cls.1
     TP_TRY(yolat_bn_relu_bwd(b.d2, H2, b.c2y, H2, P, H2, m->c2_bn.gamma, b.c2c + 2 * H2, b.c2c + 3 * H2, b.c2c, b.c2c + H2, 1,
                              grad_of(m, m->c2_bn.gamma), grad_of(m, m->c2_bn.beta), 0, b.d2, H2, b.w2bn, st));
-    TP_TRY(yolat_linear_bwd_w(b.d2, H2, P, H2, b.c1y, H1, H1, b.c1c, b.c1c + H1, 1, grad_of(m, m->c2.W), H1, grad_of(m, m->c2.b), 0,
-                              b.w2w, S.fork()));
-    TP_TRY(lin_wt(b.d2, H2, P, H2, m->c2.W, H1, b.d1, H1, 0, b.p2, true, b.x2w, st));
+    if (dense) {
+      TP_TRY(yolat_bt_linear_bwd_w(b.d2, H2, P, H2, b.c1y, H1, H1, b.c1c, b.c1c + H1, 1, grad_of(m, m->c2.W), H1,
+                                   grad_of(m, m->c2.b), b.bt_w2, S.fork()));
+      TP_TRY(yolat_bt_linear_fwd_wt(b.d2, H2, P, H2, m->c2.W, H1, H1, b.d1, H1, 0, st));
+    } else {
+      TP_TRY(yolat_linear_bwd_w(b.d2, H2, P, H2, b.c1y, H1, H1, b.c1c, b.c1c + H1, 1, grad_of(m, m->c2.W), H1, grad_of(m, m->c2.b),
+                                0, b.w2w, S.fork()));
+      TP_TRY(lin_wt(b.d2, H2, P, H2, m->c2.W, H1, b.d1, H1, 0, b.p2, true, b.x2w, st));
+    }
     // prediction_cls.0
     TP_TRY(yolat_bn_relu_bwd(b.d1, H1, b.c1y, H1, P, H1, m->c1_bn.gamma, b.c1c + 2 * H1, b.c1c + 3 * H1, b.c1c, b.c1c + H1, 1,
                              grad_of(m, m->c1_bn.gamma), grad_of(m, m->c1_bn.beta), 0, b.d1, H1, b.w1bn, st));
-    TP_TRY(yolat_linear_bwd_w(b.d1, H1, P, H1, b.Z, ZW, ZW, nullptr, nullptr, 0, grad_of(m, m->c1.W), ZW, grad_of(m, m->c1.b), 0,
-                              b.w1w, S.fork()));
-    TP_TRY(lin_wt(b.d1, H1, P, H1, m->c1.W, ZW, b.dZ, ZW, 0, b.p1, true, b.x1w, st));
+    if (dense) {
+      TP_TRY(yolat_bt_linear_bwd_w(b.d1, H1, P, H1, b.Z, ZW, ZW, nullptr, nullptr, 0, grad_of(m, m->c1.W), ZW, grad_of(m, m->c1.b),
+                                   b.bt_w1, S.fork()));
+      TP_TRY(yolat_bt_linear_fwd_wt(b.d1, H1, P, H1, m->c1.W, ZW, ZW, b.dZ, ZW, 0, st));
+    } else {
+      TP_TRY(yolat_linear_bwd_w(b.d1, H1, P, H1, b.Z, ZW, ZW, nullptr, nullptr, 0, grad_of(m, m->c1.W), ZW, grad_of(m, m->c1.b),
+                                0, b.w1w, S.fork()));
+      TP_TRY(lin_wt(b.d1, H1, P, H1, m->c1.W, ZW, b.dZ, ZW, 0, b.p1, true, b.x1w, st));
+    }
     // fusion_block_super: input sup = Z[:, 2F+D:], post-activation output Z[:, F+D:2F+D].  Its whole backward and the
     // per-proposal mean's feed nothing but the node branches' backward chain, which lives on the side stream: so do they,
     // beside the fusion block's backward (their columns of dZ are disjoint from the ones the main stream reads)
@@ -460,18 +497,24 @@ extern "C" int yolat_train_step(const yolat_train_model* m, const float* x, int6
       float* dz_fs = b.dZ + F + D;
       TP_TRY(yolat_bn_relu_bwd(dz_fs, ZW, b.fs_y, F, P, F, m->fus_s_bn.gamma, b.fs_c + 2 * F, b.fs_c + 3 * F, b.fs_c, b.fs_c + F, 1,
                                grad_of(m, m->fus_s_bn.gamma), grad_of(m, m->fus_s_bn.beta), 0, dz_fs, ZW, b.wfsbn, ss));
-      TP_TRY(yolat_linear_bwd_w(dz_fs, ZW, P, F, b.Z + 2 * F + D, ZW, D, nullptr, nullptr, 0, grad_of(m, m->fus_s.W), D,
-                                grad_of(m, m->fus_s.b), 0, b.wfsw, ss));
-      TP_TRY(yolat_linear_fwd_wt(dz_fs, ZW, P, F, m->fus_s.W, D, D, d_sup, ZW, 1, ss));
+      if (dense) {
+        TP_TRY(yolat_bt_linear_bwd_w(dz_fs, ZW, P, F, b.Z + 2 * F + D, ZW, D, nullptr, nullptr, 0, grad_of(m, m->fus_s.W), D,
+                                     grad_of(m, m->fus_s.b), b.bt_wfs, ss));
+        TP_TRY(yolat_bt_linear_fwd_wt(dz_fs, ZW, P, F, m->fus_s.W, D, D, d_sup, ZW, 1, ss));
+      } else {
+        TP_TRY(yolat_linear_bwd_w(dz_fs, ZW, P, F, b.Z + 2 * F + D, ZW, D, nullptr, nullptr, 0, grad_of(m, m->fus_s.W), D,
+                                  grad_of(m, m->fus_s.b), 0, b.wfsw, ss));
+        TP_TRY(yolat_linear_fwd_wt(dz_fs, ZW, P, F, m->fus_s.W, D, D, d_sup, ZW, 1, ss));
+      }
       TP_TRY(yolat_segment_mean_bwd(d_sup, ZW, D, seg_ptr, node_seg, N, b.d_fsup, D, ss));
     }
     // fusion_block + max pooling
     TP_TRY(yolat_segment_max_bwd(b.dZ + F, ZW, D, b.arg_feat, node_seg, N, b.d_feats, D, st));
     auto fus_part = [&](int mask, hipStream_t s) {
-      return yolat_fusion_pool_train_bwd_parts(b.feats, D, N, D, m->fus.W, m->fus_bn.gamma, F, b.fus_coef, b.fus_saved, node_seg,
-                                               seg_ptr, P, b.dZ, ZW, grad_of(m, m->fus.W), grad_of(m, m->fus.b),
-                                               grad_of(m, m->fus_bn.gamma), grad_of(m, m->fus_bn.beta), b.d_feats, D, b.fus_work,
-                                               mask, s);
+      return (dense ? yolat_fusion_pool_train_bwd_parts_bf16 : yolat_fusion_pool_train_bwd_parts)(
+          b.feats, D, N, D, m->fus.W, m->fus_bn.gamma, F, b.fus_coef, b.fus_saved, node_seg, seg_ptr, P, b.dZ, ZW,
+          grad_of(m, m->fus.W), grad_of(m, m->fus.b), grad_of(m, m->fus_bn.gamma), grad_of(m, m->fus_bn.beta), b.d_feats, D,
+          b.fus_work, mask, s);
     };
     // (column reductions both halves read, then the weight gradient on the side stream beside the input gradient)
     TP_TRY(fus_part(1, st));

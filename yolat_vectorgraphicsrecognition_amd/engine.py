@@ -124,14 +124,25 @@ def _bn_eval(bn, dev):
 # Linear (+ BatchNorm1d + ReLU)
 # ---------------------------------------------------------------------------------------------
 
-def lbr_fwd(a, lin, bn, relu, training, out=None, coef_out=None):
+def lbr_fwd(a, lin, bn, relu, training, out=None, coef_out=None, dense=False):
     """a: Lazy input [M,K].  Returns (Lazy output, saved).  ``out`` optionally names the [M,C]
-    destination (may be a column slice of a wider buffer)."""
+    destination (may be a column slice of a wider buffer).  dense: the training GEMMs of this layer (forward, dX, dW)
+    on bf16 operands ("bf16_dense" training precision, ops.bt_*)."""
     A = a.t
     M, dev = A.shape[0], A.device
     C = lin.out_features
     y = _empty(M, C, dev) if out is None else out
     sv = {"a": a, "lin": lin, "bn": bn, "relu": relu, "y": y}
+    if dense:
+        if not training or bn is None or lin.bias is None:
+            raise ValueError("bf16_dense covers training-mode Linear + BatchNorm layers with a bias")
+        if M == 0:
+            raise ValueError("BatchNorm1d in training mode needs at least one row")
+        stats = ops.stats_buffer(M, C, dev)
+        ops.bt_linear_fwd(A, lin.weight, lin.bias, y, a_pro=a.pro, a_relu=a.relu, stats=stats)
+        coef = _bn_train(stats, M, bn, dev, coef_out)
+        sv.update(coef=coef, dense=True)
+        return Lazy(y, coef[0], coef[1], relu), sv
     if bn is None:
         ops.linear_fwd(A, lin.weight, lin.bias, y, a_pro=a.pro, a_relu=a.relu, o_relu=relu)
         return Lazy(y), sv
@@ -326,11 +337,13 @@ def lbr_bwd(sv, dz, sink, dx_out=None, dx_accumulate=False, need_dx=True, dz_inp
         dy = dz
     db = sink.get(lin.bias) if lin.bias is not None else None
     dW = sink.get(lin.weight)
-    _on_side(lambda: ops.linear_bwd_w(dy, a.t, dW, db, a_pro=a.pro, a_relu=a.relu), (dy, a.t, a.scale, a.shift))
+    dense = sv.get("dense", False)
+    bwd_w = ops.bt_linear_bwd_w if dense else ops.linear_bwd_w
+    _on_side(lambda: bwd_w(dy, a.t, dW, db, a_pro=a.pro, a_relu=a.relu), (dy, a.t, a.scale, a.shift))
     if not need_dx:
         return None
     dx = _empty(M, lin.in_features, dev) if dx_out is None else dx_out
-    ops.linear_fwd_wt(dy, lin.weight, dx, accumulate=dx_accumulate)
+    (ops.bt_linear_fwd_wt if dense else ops.linear_fwd_wt)(dy, lin.weight, dx, accumulate=dx_accumulate)
     return dx
 
 
@@ -483,6 +496,30 @@ def model_convs(net):
     return [net.head.gconv] + [blk.body.gconv for blk in net.backbone]
 
 
+def check_bf16_dense_shapes(model):
+    """The shapes the "bf16_dense" training kernels take (csrc/bf16_train.hip); anything else raises ValueError naming
+    the shape — there is no silent fp32 fall-back for these layers."""
+    net = model.cls_net
+    convs = model_convs(net)
+    C = convs[0].nn[0].out_features
+    D = C * net.n_blocks_out
+    fus, sup = net.fusion_block[0], net.fusion_block_super[0]
+    m1, m2 = model.prediction_cls[0], model.prediction_cls[1]
+    F = fus.out_features
+    if D != 128 or not FUSED_FUSION_TRAIN or not fus.weight.is_contiguous():
+        raise ValueError("bf16_dense training covers fusion_dims = 128 on the fused fusion path only: fusion_block is "
+                         "[%d -> %d] (n_filters * n_blocks_out = %d)" % (D, F, D))
+    if F % 64 != 0 or fus.bias is None:
+        raise ValueError("bf16_dense training needs fusion_block out_features %% 64 == 0 with a bias: got %d" % F)
+    for name, blk in (("fusion_block_super", net.fusion_block_super), ("prediction_cls.0", m1), ("prediction_cls.1", m2)):
+        lin = blk[0]
+        if len(blk) < 2 or not isinstance(blk[1], torch.nn.BatchNorm1d) or lin.bias is None:
+            raise ValueError("bf16_dense training covers %s only as Linear + BatchNorm1d with a bias" % name)
+        if lin.in_features % 32 != 0 or lin.out_features % 32 != 0:
+            raise ValueError("bf16_dense training needs %s features %% 32 == 0: got [%d -> %d]"
+                             % (name, lin.in_features, lin.out_features))
+
+
 def model_fwd(model, g, x, training):
     """SparseCADGCN.forward on device tensors.  Returns (logits [P,K], saved-or-None)."""
     net = model.cls_net
@@ -493,8 +530,13 @@ def model_fwd(model, g, x, training):
     P = g.P
     C = convs[0].nn[0].out_features
     F = net.fusion_block[0].out_features
-    half = model.__dict__.get("_yolat_train_precision", "fp32") == "bf16"
+    precision = model.__dict__.get("_yolat_train_precision", "fp32")
+    half = precision in ("bf16", "bf16_dense")
     D = C * n_out                       # fusion_dims
+    # "bf16_dense": fusion_block, fusion_block_super and classifier layers 0 / 1 on bf16 operands (csrc/bf16_train.hip)
+    dense = training and precision == "bf16_dense"
+    if dense:
+        check_bf16_dense_shapes(model)
 
     feats = _empty(N, D, dev)           # cat of the last n_out conv outputs          (arch:60)
     fsup = _empty(N, D, dev)            # cat of the last n_out node-branch outputs   (arch:65)
@@ -518,7 +560,7 @@ def model_fwd(model, g, x, training):
     if training and FUSED_FUSION_TRAIN and D == 128 and net.fusion_block[0].weight.is_contiguous():
         # no [N,F] activation: batch statistics from the Gram matrix of feats, extreme-of-z GEMM epilogue,
         # sparse backward (csrc/fusion_train.hip)
-        sv_fus = ops.fusion_pool_train_fwd(feats, net.fusion_block[0], net.fusion_block[1], g, Z[:, 0:F])
+        sv_fus = ops.fusion_pool_train_fwd(feats, net.fusion_block[0], net.fusion_block[1], g, Z[:, 0:F], bf16=dense)
         sv_fus["fused"] = True
         if net.fusion_block[1].num_batches_tracked is not None:
             _PENDING_NBT.append(net.fusion_block[1].num_batches_tracked)
@@ -535,13 +577,13 @@ def model_fwd(model, g, x, training):
     else:
         ops.segment_mean_fwd(fsup, g, sup)
     fs, sv_fs = lbr_fwd(Lazy(sup), net.fusion_block_super[0], net.fusion_block_super[1], True, training,
-                        out=(None if training else Z[:, F + D:2 * F + D]))
+                        out=(None if training else Z[:, F + D:2 * F + D]), dense=dense)
     if training:
         ops.scale_shift_relu(fs.t, fs.scale, fs.shift, True, Z[:, F + D:2 * F + D])
     # classifier                                                                      (arch:91-93,128)
     m1, m2, m3 = model.prediction_cls[0], model.prediction_cls[1], model.prediction_cls[2]
-    c1, sv1 = lbr_fwd(Lazy(Z), m1[0], m1[1], True, training)
-    c2, sv2 = lbr_fwd(c1, m2[0], m2[1], True, training)
+    c1, sv1 = lbr_fwd(Lazy(Z), m1[0], m1[1], True, training, dense=dense)
+    c2, sv2 = lbr_fwd(c1, m2[0], m2[1], True, training, dense=dense)
     p_drop = _drop_p(m2) if training else 0.0                     # arch:92: only prediction_cls.1 carries dropout
     sv_drop = None
     if p_drop > 0:

@@ -358,6 +358,58 @@ def linear_fwd_wt(A, Wt, Y, accumulate=False):
     return Y
 
 
+# ---- "bf16_dense" training precision: the classifier / fusion_block_super GEMMs on bf16 operands (bf16_train.hip) ----
+# every operand is rounded to nearest even inside the kernel, fp32 accumulation, no fall-back: a shape the kernels do not
+# take raises ValueError
+
+def _bt_aligned(t):
+    """a weight view of the flat parameter buffer need not start on 16 bytes: the kernels read 16-byte pieces"""
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
+def _bt_check(rc, what, shape):
+    if rc == -2:
+        raise ValueError("bf16_dense training: %s does not take %s" % (what, shape))
+    check(rc, what)
+
+
+def bt_linear_fwd(A, W, bias, Y, a_pro=None, a_relu=False, stats=None):
+    """Y = pro(A) @ W.T + bias on bf16 operands; stats: BatchNorm partials (stats_buffer(M, Nout))."""
+    M, K = A.shape
+    Nout = W.shape[0]
+    asc, ash = (a_pro if a_pro is not None else (None, None))
+    W = _bt_aligned(W)
+    _bt_check(lib.yolat_bt_linear_fwd(_f(A, "A"), _ld(A), M, K, _f(asc, "a_scale", True), _f(ash, "a_shift", True),
+                                      int(a_relu), _f(W, "W"), _ld(W), _f(bias, "bias", True), Nout, _f(Y, "Y"), _ld(Y),
+                                      _f(stats, "stats", True), _stream()), "yolat_bt_linear_fwd",
+              "[%d, %d] x [%d, %d]^T" % (M, K, Nout, K))
+    return Y
+
+
+def bt_linear_fwd_wt(A, Wt, Y, accumulate=False):
+    """Y (+)= A @ Wt on bf16 operands (Wt: [K, Nout] row-major, e.g. dX = dY @ W)."""
+    M, K = A.shape
+    Nout = Wt.shape[1]
+    Wt = _bt_aligned(Wt)
+    _bt_check(lib.yolat_bt_linear_fwd_wt(_f(A, "A"), _ld(A), M, K, _f(Wt, "Wt"), _ld(Wt), Nout, _f(Y, "Y"), _ld(Y),
+                                         int(accumulate), _stream()), "yolat_bt_linear_fwd_wt",
+              "[%d, %d] x [%d, %d]" % (M, K, K, Nout))
+    return Y
+
+
+def bt_linear_bwd_w(dY, A, dW, db=None, a_pro=None, a_relu=False):
+    """dW = dY.T @ pro(A) on bf16 operands; db = fp32 column sums of dY."""
+    M, Nout = dY.shape
+    K = A.shape[1]
+    asc, ash = (a_pro if a_pro is not None else (None, None))
+    work = torch.empty(int(lib.yolat_bt_linear_bwd_w_work_elems(M, Nout, K)), dtype=torch.float32, device=dY.device)
+    _bt_check(lib.yolat_bt_linear_bwd_w(_f(dY, "dY"), _ld(dY), M, Nout, _f(A, "A"), _ld(A), K, _f(asc, "a_scale", True),
+                                        _f(ash, "a_shift", True), int(a_relu), _f(dW, "dW"), _ld(dW), _f(db, "db", True),
+                                        work.data_ptr(), _stream()), "yolat_bt_linear_bwd_w",
+              "[%d, %d]^T x [%d, %d]" % (M, Nout, M, K))
+    return dW
+
+
 def linear_bwd_w(dY, A, dW, db=None, a_pro=None, a_relu=False, accumulate=False):
     M, Nout = dY.shape
     K = A.shape[1]
@@ -818,9 +870,10 @@ def extract_subgraph(data_cls, dev_batch, pos_s, pos_e, edge_s, edge_e, slice_bb
 # training-mode fusion block + per-proposal max pooling (csrc/fusion_train.hip)
 # ---------------------------------------------------------------------------------------------
 
-def fusion_pool_train_fwd(A, lin, bn, g, Z):
+def fusion_pool_train_fwd(A, lin, bn, g, Z, bf16=False):
     """Z[P,F] <- scatter_max(relu(bn(lin(A)))) with batch statistics, without materialising [N,F].
-    Returns the state the backward needs."""
+    Returns the state the backward needs.  bf16: the GEMM (and, in the backward, the sparse dA GEMM) on bf16 operands
+    ("bf16_dense" training precision); the statistics stay fp32."""
     N, K = A.shape
     F = lin.out_features
     dev = A.device
@@ -834,12 +887,16 @@ def fusion_pool_train_fwd(A, lin, bn, g, Z):
         raise ValueError("fusion_block weight must be contiguous")
     if track:
         bump_weight_epoch()
-    check(lib.yolat_fusion_pool_train_fwd(_f(A, "A"), _ld(A), N, K, _f(W), _f(lin.bias, "bias", True), F,
-                                          _f(bn.weight), _f(bn.bias), _f(bn.running_mean if track else None, "rm", True),
-                                          _f(bn.running_var if track else None, "rv", True), mom, float(bn.eps),
-                                          g.node_seg.data_ptr(), g.P, _f(Z), _ld(Z), _f(coef), _f(saved), _f(work),
-                                          _stream()), "yolat_fusion_pool_train_fwd")
-    return {"A": A, "lin": lin, "bn": bn, "coef": coef, "saved": saved, "work": work}
+    fn, name = ((lib.yolat_fusion_pool_train_fwd_bf16, "yolat_fusion_pool_train_fwd_bf16") if bf16 else
+                (lib.yolat_fusion_pool_train_fwd, "yolat_fusion_pool_train_fwd"))
+    rc = fn(_f(A, "A"), _ld(A), N, K, _f(W), _f(lin.bias, "bias", True), F, _f(bn.weight), _f(bn.bias),
+            _f(bn.running_mean if track else None, "rm", True), _f(bn.running_var if track else None, "rv", True), mom,
+            float(bn.eps), g.node_seg.data_ptr(), g.P, _f(Z), _ld(Z), _f(coef), _f(saved), _f(work), _stream())
+    if bf16:
+        _bt_check(rc, name, "fusion_block [%d, %d] -> %d" % (N, K, F))
+    else:
+        check(rc, name)
+    return {"A": A, "lin": lin, "bn": bn, "coef": coef, "saved": saved, "work": work, "bf16": bool(bf16)}
 
 
 def fusion_pool_train_bwd(sv, g, gZ, dW, dbias, dgamma, dbeta, dA, side=None):
@@ -849,12 +906,16 @@ def fusion_pool_train_bwd(sv, g, gZ, dW, dbias, dgamma, dbeta, dA, side=None):
     N, K = A.shape
     F = lin.out_features
 
+    fn = lib.yolat_fusion_pool_train_bwd_parts_bf16 if sv.get("bf16") else lib.yolat_fusion_pool_train_bwd_parts
+
     def part(mask):
-        check(lib.yolat_fusion_pool_train_bwd_parts(_f(A), _ld(A), N, K, _f(lin.weight), _f(sv["bn"].weight), F,
-                                                    _f(sv["coef"]), _f(sv["saved"]), g.node_seg.data_ptr(),
-                                                    g.seg_ptr.data_ptr(), g.P, _f(gZ, "gZ"), _ld(gZ), _f(dW),
-                                                    _f(dbias, "dbias", True), _f(dgamma), _f(dbeta), _f(dA), _ld(dA),
-                                                    _f(sv["work"]), mask, _stream()), "yolat_fusion_pool_train_bwd")
+        rc = fn(_f(A), _ld(A), N, K, _f(lin.weight), _f(sv["bn"].weight), F, _f(sv["coef"]), _f(sv["saved"]),
+                g.node_seg.data_ptr(), g.seg_ptr.data_ptr(), g.P, _f(gZ, "gZ"), _ld(gZ), _f(dW), _f(dbias, "dbias", True),
+                _f(dgamma), _f(dbeta), _f(dA), _ld(dA), _f(sv["work"]), mask, _stream())
+        if sv.get("bf16"):
+            _bt_check(rc, "yolat_fusion_pool_train_bwd_parts_bf16", "fusion_block [%d, %d] -> %d" % (N, K, F))
+        else:
+            check(rc, "yolat_fusion_pool_train_bwd")
     if side is None:
         part(7)
         return

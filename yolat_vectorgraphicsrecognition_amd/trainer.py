@@ -328,7 +328,8 @@ class TrainPlan(object):
         convs = engine.model_convs(net)
         d = TrainModel()
         d.n_blocks, d.n_blocks_out, d.n_classes = net.n_blocks, net.n_blocks_out, m.n_classes
-        d.half = 1 if m.__dict__.get("_yolat_train_precision", "fp32") == "bf16" else 0
+        # value 1: bf16 storage of the per-edge tensors; bit 2 on top (3): the bf16_dense head (csrc/train_plan.hip)
+        d.half = {"bf16": 1, "bf16_dense": 3}.get(m.__dict__.get("_yolat_train_precision", "fp32"), 0)
         d.C = convs[0].nn[0].out_features
         d.F = net.fusion_block[0].out_features
         d.H1, d.H2 = m.prediction_cls[0][0].out_features, m.prediction_cls[1][0].out_features
