@@ -205,7 +205,9 @@ def test_bf16_dense_cfg5_full_size_vs_fp64_oracle(cfg5_oracle):
     so it moves by whole entries wherever a gate flips.  The bf16 fusion GEMM rounds both operands of 128 products per
     entry, which moves z near the gate more than the oracle's probe (2^-9 noise on the input, damped through four
     BatchNorm'd layers) does.  Measured (first run of this test): err 8.34e-7, sens 5.65e-8, rms 5.12e-7, i.e. 14.6 x the
-    sensitivity after the 2e-2 rms term; held to 16 x here.  Every other tensor meets the factor 4."""
+    sensitivity after the 2e-2 rms term; held to 16 x here.  Every other tensor meets the factor 4.  The fusion kernels
+    meet their bf16 contract at the op level (tests/test_gpu_fusion_pool.py, at the fp32 bound of 2e-4), so the widened
+    bound comes from routing: gates and arg rows that the rounded z moves."""
     yv = _yv()
     data, slices, optkw, l64, g64, g64p = cfg5_oracle
     ld, gd, bd = _train_once(yv, optkw, data, 55, "bf16_dense", slices)

@@ -137,6 +137,84 @@ static __global__ void __launch_bounds__(256) k_pool_finish(const unsigned long 
   arg[p * F + c] = a;
 }
 
+// scale == 0 (gamma == +-0): every row of a proposal has the activation relu(shift), so torch_scatter's first occurrence
+// is the proposal's FIRST row, whichever row the GEMM epilogue's key holds (the epilogues order z as for scale > 0).  Runs
+// after k_pool_finish and rewrites (arg, z*) of those columns only: arg = the first row (binary search of node_seg),
+// z* = A[arg] . W[c] + b[c] in fp32, k ascending (on the bf16 round-to-nearest images of A and W when `bf16`, as the
+// bf16 GEMM forms z); pooled values do not depend on z there, and only dgamma reads z*.  A workgroup = 64 columns x
+// proposal tiles of 64 (a 64 x 64 x K product through LDS, 4 x 4 outputs per thread); a workgroup whose 64 columns hold no
+// zero scale returns at once — the common case, one short launch.
+constexpr int PZ_T = 64, PZ_KC = 32;
+static __global__ void __launch_bounds__(256) k_pool_zero_scale(const float* __restrict__ scale, long P, int F, int N,
+                                                         const int32_t* __restrict__ node_seg,
+                                                         const float* __restrict__ A, long lda, int K,
+                                                         const float* __restrict__ W, const float* bias, int bf16,
+                                                         float* zstar, int* arg) {
+  __shared__ float As[PZ_T][PZ_KC + 1], Ws[PZ_T][PZ_KC + 1];
+  __shared__ int rows[PZ_T];
+  const int tid = threadIdx.x, c0 = blockIdx.x * PZ_T;
+  const bool zc = tid < PZ_T && c0 + tid < F && scale[c0 + tid] == 0.f;
+  if (!__syncthreads_or(zc)) return;
+  const int tr = tid >> 4, tc = tid & 15;      // outputs: proposals 4 tr .. 4 tr + 3, columns 4 tc .. 4 tc + 3
+  const long ntiles = (P + PZ_T - 1) / PZ_T;
+  auto rnd = [&](float x) { return bf16 ? yl_bf16_lo(yl_pack_bf16(x, 0.f)) : x; };
+  for (long pt = blockIdx.y; pt < ntiles; pt += gridDim.y) {
+    const long q0 = pt * PZ_T;
+    if (tid < PZ_T) {
+      const long q = q0 + tid;
+      int r = -1;
+      if (q < P) {
+        int lo = 0, hi = N;                    // first row with node_seg >= q
+        while (lo < hi) {
+          const int mid = (int)(((unsigned)lo + (unsigned)hi) >> 1);
+          if (node_seg[mid] < q) lo = mid + 1; else hi = mid;
+        }
+        if (lo < N && node_seg[lo] == q) r = lo;   // else: empty proposal (k_pool_finish wrote arg = N, z* = 0)
+      }
+      rows[tid] = r;
+    }
+    float acc[4][4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) acc[i][j] = 0.f;
+    for (int k0 = 0; k0 < K; k0 += PZ_KC) {
+      __syncthreads();                         // rows[] written / the previous chunk's readers done
+      for (int e = tid; e < PZ_T * PZ_KC; e += 256) {
+        const int i = e / PZ_KC, kk = e % PZ_KC, k = k0 + kk;
+        const int r = rows[i];
+        As[i][kk] = (r >= 0 && k < K) ? rnd(A[(long)r * lda + k]) : 0.f;
+        Ws[i][kk] = (c0 + i < F && k < K) ? rnd(W[(long)(c0 + i) * K + k]) : 0.f;
+      }
+      __syncthreads();
+      for (int kk = 0; kk < PZ_KC; ++kk) {
+        float a[4], w[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) { a[i] = As[4 * tr + i][kk]; w[i] = Ws[4 * tc + i][kk]; }
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+          for (int j = 0; j < 4; ++j) acc[i][j] = fmaf(a[i], w[j], acc[i][j]);
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int r = rows[4 * tr + i];
+      const long q = q0 + 4 * tr + i;
+      if (r < 0) continue;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int c = c0 + 4 * tc + j;
+        if (c < F && scale[c] == 0.f) {
+          zstar[q * F + c] = acc[i][j] + (bias != nullptr ? bias[c] : 0.f);
+          arg[q * F + c] = r;
+        }
+      }
+    }
+    __syncthreads();                           // rows[] of this tile read by every thread before the next tile's
+  }
+}
+
 
 // partial[s] [128][128] = sum over the rows of slab s of (a_r + negmean)(a_r + negmean)^T,  A [N, 128] fp32.
 // 256 threads = 2 x 2 waves, each wave a 64 x 64 quadrant (4 accumulators); per 32-row stage the centered tile goes to
@@ -249,8 +327,10 @@ static int fus_train_fwd(const float* A, int64_t lda, int64_t N, int64_t K, cons
     return YOLAT_E_INVALID;
   if (lda < K || ldz < F || N >= (1LL << 31) || (running_mean == nullptr) != (running_var == nullptr))
     return YOLAT_E_INVALID;
-  if (K % 4 != 0 || lda % 4 != 0) return YOLAT_E_UNSUPPORTED;
-  if (bf16 && (K != 128 || F % 64 != 0 || bias == nullptr || !yl_aligned16(A))) return YOLAT_E_UNSUPPORTED;
+  // A 16-byte aligned: the backward (k_fus_dw_sparse) reads A's rows as float4, so the forward declines what its
+  // backward could not take, before it enqueues anything
+  if (K % 4 != 0 || lda % 4 != 0 || !yl_aligned16(A)) return YOLAT_E_UNSUPPORTED;
+  if (bf16 && (K != 128 || F % 64 != 0 || bias == nullptr)) return YOLAT_E_UNSUPPORTED;
   hipStream_t st = (hipStream_t)stream;
   FusSaved sv = fus_saved(saved, K, F, P);
   float* colpart = work;
@@ -271,7 +351,7 @@ static int fus_train_fwd(const float* A, int64_t lda, int64_t N, int64_t K, cons
                      sv.negmean);
   YL_LAUNCH_CHECK();
   // 2. centered Gram matrix G = (A - mean)^T (A - mean)
-  if (K == 128 && yl_aligned16(A)) {
+  if (K == 128) {
     // dedicated kernel: one workgroup owns a slab of rows and the WHOLE 128 x 128 product (the tile is loaded once per
     // 32 rows and feeds 64 MFMAs per wave between barriers; the generic TN GEMM — 64 x 64 output tiles, 16 MFMAs per
     // wave and stage — was latency bound: 234 us at N = 174 k)
@@ -337,6 +417,11 @@ static int fus_train_fwd(const float* A, int64_t lda, int64_t N, int64_t K, cons
                        (int)F, coef, coef + F, (int)N, Z + p0 * ldz, (long)ldz, sv.zstar + p0 * F, sv.arg + p0 * F);
     YL_LAUNCH_CHECK();
   }
+  // 6. columns with scale == 0: arg = the proposal's first row, z* recomputed there
+  const long pz_tiles = yl_cdiv(P, PZ_T);
+  hipLaunchKernelGGL(k_pool_zero_scale, dim3(yl_cdiv(F, PZ_T), (unsigned)(pz_tiles < 64 ? pz_tiles : 64)), dim3(256), 0, st,
+                     coef, (long)P, (int)F, (int)N, node_seg, A, (long)lda, (int)K, W, bias, bf16, sv.zstar, sv.arg);
+  YL_LAUNCH_CHECK();
   return 0;
 }
 
@@ -862,7 +947,7 @@ static int fus_train_bwd_parts(const float* A, int64_t lda, int64_t N, int64_t K
       !dbeta || !dA || !work)
     return YOLAT_E_INVALID;
   if (lda < K || ldg < F || ldda < K || N >= (1LL << 31)) return YOLAT_E_INVALID;
-  if (K != 128 || F % 32 != 0 || lda % 4 != 0 || ldda % 4 != 0 || ((uintptr_t)dA & 15) != 0)
+  if (K != 128 || F % 32 != 0 || lda % 4 != 0 || ldda % 4 != 0 || !yl_aligned16(A) || !yl_aligned16(dA))
     return YOLAT_E_UNSUPPORTED;
   if (bf16 && (F % 64 != 0 || F < 64)) return YOLAT_E_UNSUPPORTED;
   hipStream_t st = (hipStream_t)stream;

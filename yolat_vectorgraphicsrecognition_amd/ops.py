@@ -870,6 +870,19 @@ def extract_subgraph(data_cls, dev_batch, pos_s, pos_e, edge_s, edge_e, slice_bb
 # training-mode fusion block + per-proposal max pooling (csrc/fusion_train.hip)
 # ---------------------------------------------------------------------------------------------
 
+def _fus_check(rc, what, A, F, bf16):
+    """YOLAT_E_UNSUPPORTED of the training fusion entry points -> ValueError naming the shape and A's alignment.  The
+    alignment and shape checks at entry (A 16-byte aligned, row stride % 4 == 0, K / F of the path) decline before anything
+    is enqueued; the bf16 forward's GEMM can still decline an extreme N (N * F >= 2^32) after the statistics ran."""
+    shape = "fusion_block A [%d, %d] (row stride %d, base address %% 16 = %d) -> %d" % (
+        A.shape[0], A.shape[1], _ld(A), A.data_ptr() % 16, F)
+    if bf16:
+        _bt_check(rc, what, shape)
+    elif rc == -2:
+        raise ValueError("%s does not take %s" % (what, shape))
+    check(rc, what)
+
+
 def fusion_pool_train_fwd(A, lin, bn, g, Z, bf16=False):
     """Z[P,F] <- scatter_max(relu(bn(lin(A)))) with batch statistics, without materialising [N,F].
     Returns the state the backward needs.  bf16: the GEMM (and, in the backward, the sparse dA GEMM) on bf16 operands
@@ -892,10 +905,7 @@ def fusion_pool_train_fwd(A, lin, bn, g, Z, bf16=False):
     rc = fn(_f(A, "A"), _ld(A), N, K, _f(W), _f(lin.bias, "bias", True), F, _f(bn.weight), _f(bn.bias),
             _f(bn.running_mean if track else None, "rm", True), _f(bn.running_var if track else None, "rv", True), mom,
             float(bn.eps), g.node_seg.data_ptr(), g.P, _f(Z), _ld(Z), _f(coef), _f(saved), _f(work), _stream())
-    if bf16:
-        _bt_check(rc, name, "fusion_block [%d, %d] -> %d" % (N, K, F))
-    else:
-        check(rc, name)
+    _fus_check(rc, name, A, F, bf16)
     return {"A": A, "lin": lin, "bn": bn, "coef": coef, "saved": saved, "work": work, "bf16": bool(bf16)}
 
 
@@ -912,10 +922,8 @@ def fusion_pool_train_bwd(sv, g, gZ, dW, dbias, dgamma, dbeta, dA, side=None):
         rc = fn(_f(A), _ld(A), N, K, _f(lin.weight), _f(sv["bn"].weight), F, _f(sv["coef"]), _f(sv["saved"]),
                 g.node_seg.data_ptr(), g.seg_ptr.data_ptr(), g.P, _f(gZ, "gZ"), _ld(gZ), _f(dW), _f(dbias, "dbias", True),
                 _f(dgamma), _f(dbeta), _f(dA), _ld(dA), _f(sv["work"]), mask, _stream())
-        if sv.get("bf16"):
-            _bt_check(rc, "yolat_fusion_pool_train_bwd_parts_bf16", "fusion_block [%d, %d] -> %d" % (N, K, F))
-        else:
-            check(rc, "yolat_fusion_pool_train_bwd")
+        _fus_check(rc, "yolat_fusion_pool_train_bwd_parts_bf16" if sv.get("bf16") else "yolat_fusion_pool_train_bwd",
+                   A, F, sv.get("bf16"))
     if side is None:
         part(7)
         return
