@@ -844,6 +844,46 @@ size_t yolat_nms_work_bytes(int64_t n);
 int yolat_nms(const float* boxes, const float* scores, int64_t n, float iou_threshold, int64_t* keep,
               int32_t* num_keep, void* work, size_t work_bytes, yolat_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Batched detection post-processing of one evaluation batch (csrc/detect.hip): every image of the batch in one
+ * call per stage, nothing read back inside a call.  image_ptr / gt_ptr are DEVICE int32 [B + 1], non-decreasing
+ * (rows of image i = [image_ptr[i], image_ptr[i + 1])); entries are clamped to the array sizes before use.
+ *
+ * yolat_detect_scores: the `pred` rows of the reference's loop (cad_recognition/train.py:423-433).  logits [R, K]
+ *   (leading dimension ld), boxes [R, 4], scale [B, 4] -> pred_out [R, 4 + K] =
+ *   (box * scale[image], 1 - p[K-1], p[0], ..., p[K-2]) with p = softmax(logits row) in fp32, the row maximum
+ *   subtracted (softmax != 0), or p = the logits themselves (softmax == 0: the classifier already applied a sigmoid).
+ *   K >= 2.  A NaN logit gives NaN scores, which are no candidates below.
+ *
+ * yolat_nms_batched: non_max_suppression(prediction, conf_thres, iou_thres, classes=None, agnostic, labels=()) of
+ *   train.py:34-121 per image.  pred [R, 5 + nc] contiguous = (x1, y1, x2, y2, obj, cls...).  Candidates: one per
+ *   (row, class) with obj > conf_thres and obj * cls > conf_thres, row-major; per image a stable descending sort by
+ *   obj * cls, the strongest 30 000 enter, boxes shifted by class * 4096 unless agnostic, greedy suppression with
+ *   yolat_nms's predicate (IoU > iou_thres, strict).  det_out [B, 300, 6] = (x1, y1, x2, y2, conf, cls) with the
+ *   unshifted box, descending conf, rows beyond det_count[image] zero; det_count [B] DEVICE int32 (<= 300).
+ *   work: yolat_nms_batched_work_bytes(R, nc, B) bytes, 256-byte aligned: linear in the R * nc candidates (24 bytes
+ *   each + the radix sort's temporary storage), no n x n mask.  nc in [1, 4096], B in [1, 65536], R * nc <= 2^27,
+ *   else the query returns 0 and the call YOLAT_E_UNSUPPORTED.
+ *
+ * yolat_detect_match: the true-positive walk of get_batch_statistics (utils/det_util.py:154-202) for every
+ *   (image, threshold) pair.  det / det_count as written by yolat_nms_batched; gt_boxes [G, 4], gt_labels [G] fp32
+ *   (class ids), targets of image i = [gt_ptr[i], gt_ptr[i + 1]); thresholds [T] fp32.  Detections in order; stop
+ *   once every target of the image is claimed; a detection whose label no target has is skipped; IoU with the
+ *   +1-pixel box sizes of bbox_iou; among the same-label targets with IoU >= threshold the largest IoU (first index
+ *   on ties) — a true positive iff that target is unclaimed, which then is claimed.  tp_out [T, B, 300] uint8.
+ *   G <= 262144, T <= 65535.
+ * ------------------------------------------------------------------------------------------ */
+int yolat_detect_scores(const float* logits, int64_t R, int64_t K, int64_t ld, const float* boxes,
+                        const int32_t* image_ptr, int64_t B, const float* scale, int softmax, float* pred_out,
+                        yolat_stream_t stream);
+size_t yolat_nms_batched_work_bytes(int64_t R, int64_t nc, int64_t B);
+int yolat_nms_batched(const float* pred, int64_t R, int64_t nc, const int32_t* image_ptr, int64_t B,
+                      float conf_thres, float iou_thres, int agnostic, float* det_out, int32_t* det_count,
+                      void* work, size_t work_bytes, yolat_stream_t stream);
+int yolat_detect_match(const float* det, const int32_t* det_count, int64_t B, const float* gt_boxes,
+                       const float* gt_labels, int64_t G, const int32_t* gt_ptr, const float* thresholds, int64_t T,
+                       uint8_t* tp_out, yolat_stream_t stream);
+
 /* Stage profiler of yolat_forward_eval: when enabled, a hipEvent pair is recorded on `stream` around
  * every stage (each stage = the launch(es) of one kernel family); totals accumulate across calls until
  * reset.  yolat_profile_get must be called after the stream has been synchronised.  `flops` / `bytes`

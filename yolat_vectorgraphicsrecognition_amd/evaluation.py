@@ -9,14 +9,19 @@ import numpy as np
 import torch
 
 from .data import fixup_offsets
-from .postprocess import non_max_suppression, get_batch_statistics, ap_per_class
+from . import ops
+from .postprocess import (non_max_suppression, get_batch_statistics, ap_per_class, detect_post_device,
+                          non_max_suppression_batched)
 
 
 def evaluate_batch(model, criterion, data, slices, classifier="softmax", iou_thresholds=None, conf_thres=0.0,
-                   iou_thres=0.5, fixup=True):
+                   iou_thres=0.5, fixup=True, device_post=False):
     """One iteration of the loop (train.py:343-460).  Returns a dict: per-threshold ``sample_metrics`` (lists of
     [true_positives, scores, labels] per image), the ground-truth ``labels`` list, ``loss`` dict, ``n_true`` /
-    ``n_total`` of the top-1 accuracy, ``y_pred`` / ``y_true``."""
+    ``n_total`` of the top-1 accuracy, ``y_pred`` / ``y_true``.
+    device_post=True: scores, NMS and the true-positive walk of ALL images and thresholds run as three device calls
+    (postprocess.detect_post_device, csrc/detect.hip) between one upload and one read-back, instead of per image from
+    Python; same detections and flags, the softmax may differ from torch's in the last bit."""
     if iou_thresholds is None:
         iou_thresholds = np.linspace(0.5, 0.95, 10)
     if fixup:
@@ -37,6 +42,21 @@ def evaluate_batch(model, criterion, data, slices, classifier="softmax", iou_thr
            "n_total": int(pred_label.shape[0]), "y_pred": pred_label.cpu().numpy(), "y_true": data.labels.cpu().numpy(),
            "sample_metrics": [[] for _ in iou_thresholds], "labels": []}
     image_ptr, label_ptr = slices["bbox"], slices["gt_labels"]
+    if device_post:
+        scales, gts = [], []
+        for i in range(len(image_ptr) - 1):
+            w, h = float(data.width[i]), float(data.height[i])
+            scale = torch.tensor([w, h, w, h], dtype=torch.float32)
+            gt = data.gt_bbox[int(label_ptr[i]):int(label_ptr[i + 1])].float() * scale
+            gl = data.gt_labels[int(label_ptr[i]):int(label_ptr[i + 1])]
+            rep["labels"] += gl.tolist()
+            scales.append(scale)
+            gts.append(torch.cat((gl.float().unsqueeze(1), gt), 1))
+        rep["sample_metrics"] = detect_post_device(
+            pred_cls.detach().float(), pred_coord.float().contiguous(), image_ptr, torch.stack(scales).numpy(),
+            torch.cat(gts, 0).numpy(), label_ptr, iou_thresholds, softmax=classifier == "softmax", conf_thres=conf_thres,
+            iou_thres=iou_thres)
+        return rep
     for i in range(len(image_ptr) - 1):
         pc = pred_cls[image_ptr[i]:image_ptr[i + 1]]
         pb = pred_coord[image_ptr[i]:image_ptr[i + 1]]
@@ -56,6 +76,30 @@ def evaluate_batch(model, criterion, data, slices, classifier="softmax", iou_thr
     return rep
 
 
+def detect_batch(model, data, slices, conf_thres=0.25, iou_thres=0.45, classifier="softmax", agnostic=False, fixup=True):
+    """Inference on one collated batch, the loop of the reference's detect.py: ``model.predict``, then scores and the
+    class-aware NMS of all images as two device calls (ops.detect_scores, postprocess.non_max_suppression_batched).
+    Returns one device tensor [k, 6] = (x1, y1, x2, y2, conf, cls) per image, boxes in pixels of the image
+    (``data.width`` / ``data.height``; without them the boxes stay in the model's unit square)."""
+    if fixup:
+        fixup_offsets(data, slices)
+    if not hasattr(data, "edge_control"):
+        data.edge_control = None
+    with torch.no_grad():
+        out = model.predict(data, slices)
+    logits, boxes, image_ptr = out[0].detach().float(), out[1].detach().float().contiguous(), out[4]
+    B = len(image_ptr) - 1
+    scales = np.ones((B, 4), dtype=np.float32)
+    if hasattr(data, "width") and hasattr(data, "height"):
+        for i in range(B):
+            scales[i] = (float(data.width[i]), float(data.height[i])) * 2
+    dev = logits.device
+    ptr = torch.as_tensor([int(v) for v in image_ptr], dtype=torch.int32)
+    up = torch.from_numpy(np.concatenate([ptr.numpy(), scales.reshape(-1).view(np.int32)])).to(dev)
+    pred = ops.detect_scores(logits, boxes, up[:B + 1], up[B + 1:].view(torch.float32).view(B, 4), classifier == "softmax")
+    return non_max_suppression_batched(pred, ptr, conf_thres=conf_thres, iou_thres=iou_thres, agnostic=agnostic)
+
+
 def test(model, test_loader, criterion, opt):
     """train.py:324-508.  Returns the mean AP at the last IoU threshold (None when nothing was detected), like the
     reference; the per-threshold mAPs, MAP@ALL, top-1 accuracy and mean losses are left in ``opt.test_report``."""
@@ -67,7 +111,7 @@ def test(model, test_loader, criterion, opt):
     with torch.no_grad():
         for data, slices in test_loader:
             rep = evaluate_batch(model, criterion, data, slices, classifier=getattr(opt, "classifier", "softmax"),
-                                 iou_thresholds=ths)
+                                 iou_thresholds=ths, device_post=bool(getattr(opt, "device_postprocess", False)))
             for t in range(steps):
                 metrics[t] += rep["sample_metrics"][t]
             labels += rep["labels"]

@@ -992,3 +992,90 @@ def nms(boxes, scores, iou_threshold):
     check(lib.yolat_nms(b.data_ptr(), s.data_ptr(), n, float(iou_threshold), keep.data_ptr(), cnt.data_ptr(),
                         work.data_ptr(), work.numel(), _stream()), "yolat_nms")
     return keep[:int(cnt.item())]          # D2H sync, as torchvision's sized result implies
+
+
+MAX_DET = 300          # rows of one image in det / tp (csrc/detect.hip DET_MAX_DET; train.py:45)
+
+
+def _dense2(t, name, cols=None):
+    """data_ptr of a contiguous 2-D fp32 CUDA tensor (optionally with a fixed number of columns)."""
+    p = _f(t, name)
+    if t.dim() != 2 or (cols is not None and t.shape[1] != cols) or (t.numel() > 0 and not t.is_contiguous()):
+        raise ValueError("%s must be a contiguous [n, %s] tensor" % (name, "k" if cols is None else cols))
+    return p
+
+
+def detect_scores(logits, boxes, image_ptr, scale, softmax=True, out=None):
+    """yolat_detect_scores (csrc/detect.hip): logits [R, K], boxes [R, 4], image_ptr [B + 1] int32, scale [B, 4] ->
+    the evaluation loop's pred rows [R, 4 + K] = (box * scale[image], 1 - p[K-1], p[0 .. K-2]), p = softmax(logits)
+    (softmax=True) or the logits themselves.  All CUDA tensors; nothing is read back."""
+    lp = _f(logits, "logits")
+    if logits.dim() != 2 or logits.shape[1] < 2:
+        raise ValueError("detect_scores expects logits [R, K] with K >= 2")
+    R, K = int(logits.shape[0]), int(logits.shape[1])
+    bp = _dense2(boxes, "boxes", 4)
+    ip, sp = _i(image_ptr, torch.int32, "image_ptr"), _dense2(scale, "scale", 4)
+    B = int(image_ptr.shape[0]) - 1
+    if boxes.shape[0] != R or B < 1 or scale.shape[0] != B:
+        raise ValueError("detect_scores expects boxes [R, 4], image_ptr [B + 1] and scale [B, 4]")
+    if out is None:
+        out = torch.empty((R, 4 + K), dtype=torch.float32, device=logits.device)
+    check(lib.yolat_detect_scores(lp, R, K, _ld(logits), bp, ip, B, sp, int(bool(softmax)), _dense2(out, "out", 4 + K),
+                                  _stream()), "yolat_detect_scores")
+    return out
+
+
+def nms_batched_work_bytes(R, nc, B):
+    """Workspace of nms_batched in bytes (0: shape not supported): linear in the R * nc candidates."""
+    return int(lib.yolat_nms_batched_work_bytes(int(R), int(nc), int(B)))
+
+
+def nms_batched(pred, image_ptr, conf_thres=0.25, iou_thres=0.45, agnostic=False, det=None, det_count=None):
+    """yolat_nms_batched (csrc/detect.hip): the class-aware non_max_suppression of every image of a batch in one call.
+    pred [R, 5 + nc] = (x1, y1, x2, y2, obj, cls...), image_ptr [B + 1] int32 -> (det [B, 300, 6], det_count [B] int32),
+    both on the device; rows beyond det_count[i] are zero.  Nothing is read back."""
+    pp = _dense2(pred, "pred")
+    if pred.shape[1] < 6:
+        raise ValueError("nms_batched expects pred [R, 5 + nc] with nc >= 1")
+    R, nc = int(pred.shape[0]), int(pred.shape[1]) - 5
+    ip = _i(image_ptr, torch.int32, "image_ptr")
+    B = int(image_ptr.shape[0]) - 1
+    if B < 1:
+        raise ValueError("nms_batched expects image_ptr [B + 1] with B >= 1")
+    need = nms_batched_work_bytes(R, nc, B)
+    if need == 0:
+        raise ValueError("nms_batched supports nc <= 4096, B <= 65536 and R * nc <= 2^27")
+    dev = pred.device
+    work = torch.empty(need, dtype=torch.uint8, device=dev)
+    if det is None:
+        det = torch.empty((B, MAX_DET, 6), dtype=torch.float32, device=dev)
+    if det_count is None:
+        det_count = torch.empty(B, dtype=torch.int32, device=dev)
+    if tuple(det.shape) != (B, MAX_DET, 6) or not det.is_contiguous() or tuple(det_count.shape) != (B,):
+        raise ValueError("nms_batched expects det [B, 300, 6] and det_count [B]")
+    check(lib.yolat_nms_batched(pp, R, nc, ip, B, float(conf_thres), float(iou_thres), int(bool(agnostic)), _f(det, "det"),
+                                _i(det_count, torch.int32, "det_count"), work.data_ptr(), work.numel(), _stream()),
+          "yolat_nms_batched")
+    return det, det_count
+
+
+def detect_match(det, det_count, gt_boxes, gt_labels, gt_ptr, thresholds, out=None):
+    """yolat_detect_match (csrc/detect.hip): true-positive flags of get_batch_statistics for every (image, threshold)
+    pair.  det [B, 300, 6] / det_count [B] as returned by nms_batched, gt_boxes [G, 4], gt_labels [G] fp32, gt_ptr [B + 1]
+    int32, thresholds [T] fp32 -> tp [T, B, 300] uint8 on the device."""
+    dp = _f(det, "det")
+    if det.dim() != 3 or tuple(det.shape[1:]) != (MAX_DET, 6) or not det.is_contiguous():
+        raise ValueError("detect_match expects det [B, 300, 6]")
+    B, G, T = int(det.shape[0]), int(gt_boxes.shape[0]), int(thresholds.shape[0])
+    gp, lp, tp_ = _dense2(gt_boxes, "gt_boxes", 4), _f(gt_labels, "gt_labels"), _f(thresholds, "thresholds")
+    if gt_labels.dim() != 1 or gt_labels.shape[0] != G or thresholds.dim() != 1 or T < 1:
+        raise ValueError("detect_match expects gt_labels [G] and thresholds [T]")
+    if tuple(det_count.shape) != (B,) or tuple(gt_ptr.shape) != (B + 1,):
+        raise ValueError("detect_match expects det_count [B] and gt_ptr [B + 1]")
+    if out is None:
+        out = torch.empty((T, B, MAX_DET), dtype=torch.uint8, device=det.device)
+    if tuple(out.shape) != (T, B, MAX_DET) or out.dtype != torch.uint8 or not out.is_cuda or not out.is_contiguous():
+        raise ValueError("detect_match expects out [T, B, 300] uint8 on the device")
+    check(lib.yolat_detect_match(dp, _i(det_count, torch.int32, "det_count"), B, gp, lp, G, _i(gt_ptr, torch.int32, "gt_ptr"),
+                                 tp_, T, out.data_ptr(), _stream()), "yolat_detect_match")
+    return out

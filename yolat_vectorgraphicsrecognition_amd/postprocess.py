@@ -60,6 +60,93 @@ def non_max_suppression(prediction, conf_thres=0.25, iou_thres=0.45, classes=Non
     return out
 
 
+def _ptr_array(ptr, name):
+    """A host int32 offset array [B + 1] from a list / numpy array / tensor, checked to be non-decreasing from 0."""
+    if torch.is_tensor(ptr):
+        ptr = ptr.detach().cpu().numpy()
+    arr = np.asarray([int(v) for v in ptr], dtype=np.int64)
+    if arr.ndim != 1 or arr.shape[0] < 2 or arr[0] != 0 or (np.diff(arr) < 0).any():
+        raise ValueError("%s must hold B + 1 non-decreasing offsets starting at 0" % name)
+    return arr.astype(np.int32)
+
+
+def non_max_suppression_batched(pred_rows, image_ptr, conf_thres=0.25, iou_thres=0.45, agnostic=False):
+    """The images of a batch through ``non_max_suppression`` in ONE device call (ops.nms_batched, csrc/detect.hip).
+    pred_rows [R, 5 + nc] = the rows of all images back to back, image_ptr [B + 1] their offsets (list, array or tensor)
+    -> list of B device tensors [k, 6] = (x1, y1, x2, y2, conf, cls), each equal to
+    ``non_max_suppression(pred_rows[image_ptr[i]:image_ptr[i + 1]][None], conf_thres, iou_thres, agnostic=agnostic)[0]``.
+    Per image the sorted candidates are tested against the kept list only and the walk ends at the 300th detection, so
+    the work space is linear in the candidates.  The one host read is the B detection counts.
+    ``classes=`` and ``labels=`` are not offered here: use the per-image ``non_max_suppression`` for them."""
+    ptr = _ptr_array(image_ptr, "image_ptr")
+    if int(ptr[-1]) != int(pred_rows.shape[0]):
+        raise ValueError("image_ptr ends at %d, pred_rows has %d rows" % (int(ptr[-1]), int(pred_rows.shape[0])))
+    dptr = torch.from_numpy(ptr).to(pred_rows.device)
+    det, cnt = ops.nms_batched(pred_rows.detach().to(torch.float32).contiguous(), dptr, conf_thres, iou_thres, agnostic)
+    return [det[i, :k] for i, k in enumerate(cnt.tolist())]
+
+
+def _unpack_statistics(cnt, det, tp):
+    """Host arrays cnt [B], det [B, 300, 6], tp [T, B, 300] -> per threshold the per-image
+    [true_positives (np.float64), pred_scores, pred_labels] lists of ``get_batch_statistics``."""
+    det_t = torch.from_numpy(det)
+    return [[[tp[t, i, :k].astype(np.float64), det_t[i, :k, 4], det_t[i, :k, 5]] for i, k in enumerate(cnt.tolist())]
+            for t in range(tp.shape[0])]
+
+
+def get_batch_statistics_batched(det, det_count, targets, gt_ptr, iou_thresholds):
+    """``get_batch_statistics`` for every image and every IoU threshold in ONE device call (ops.detect_match).
+    det [B, 300, 6] / det_count [B]: device tensors as ops.nms_batched returns them; targets [G, 6] =
+    (image, label, x1, y1, x2, y2) like the per-image function, grouped by image: rows gt_ptr[i]:gt_ptr[i + 1] belong to
+    image i (column 0 is not read).  Returns a list over the thresholds; entry t is the list over the images of
+    [true_positives (np.float64 [k]), pred_scores, pred_labels] — what ``get_batch_statistics(outputs, targets_i, th)``
+    returns for each image.  Thresholds are compared in fp32, as torch compares an fp32 IoU with a Python float."""
+    dev = det.device
+    ptr = _ptr_array(gt_ptr, "gt_ptr")
+    tg = torch.as_tensor(targets, dtype=torch.float32).reshape(-1, 6)
+    if int(ptr[-1]) != tg.shape[0] or ptr.shape[0] != det.shape[0] + 1:
+        raise ValueError("gt_ptr must hold B + 1 offsets ending at the number of targets")
+    tg = tg.to(dev)
+    th = torch.from_numpy(np.asarray(iou_thresholds, dtype=np.float32).reshape(-1)).to(dev)
+    tp = ops.detect_match(det, det_count, tg[:, 2:6].contiguous(), tg[:, 1].contiguous(), torch.from_numpy(ptr).to(dev), th)
+    return _unpack_statistics(det_count.cpu().numpy(), det.cpu().numpy(), tp.cpu().numpy())
+
+
+def detect_post_device(logits, boxes, image_ptr, scales, gt, gt_ptr, iou_thresholds, softmax=True, conf_thres=0.0,
+                       iou_thres=0.5):
+    """The post-processing of one evaluation batch on the device (evaluation.evaluate_batch(device_post=True)):
+    scores -> batched NMS -> true-positive flags at every threshold.  logits [R, K] / boxes [R, 4]: device tensors;
+    image_ptr [B + 1], scales [B, 4], gt [G, 5] = (label, box in pixels), gt_ptr [B + 1], iou_thresholds [T]: host
+    values, uploaded in ONE copy; the (det_count, det, tp) results come back in ONE copy.  Returns
+    ``_unpack_statistics``'s per-threshold lists."""
+    dev = logits.device
+    iptr, gptr = _ptr_array(image_ptr, "image_ptr"), _ptr_array(gt_ptr, "gt_ptr")
+    B, T = iptr.shape[0] - 1, len(iou_thresholds)
+    gt = np.ascontiguousarray(np.asarray(gt, dtype=np.float32).reshape(-1, 5))
+    G = gt.shape[0]
+    parts = [iptr, gptr, np.asarray(scales, dtype=np.float32).reshape(B, 4), np.ascontiguousarray(gt[:, 1:5]),
+             np.ascontiguousarray(gt[:, 0]), np.asarray(iou_thresholds, dtype=np.float32)]
+    up = torch.from_numpy(np.concatenate([p.reshape(-1).view(np.int32) for p in parts])).to(dev)
+    views, o = [], 0
+    for p in parts:
+        views.append(up[o:o + p.size])
+        o += p.size
+    d_iptr, d_gptr = views[0], views[1]
+    d_scale, d_gbox = views[2].view(torch.float32).view(B, 4), views[3].view(torch.float32).view(G, 4)
+    d_glab, d_th = views[4].view(torch.float32), views[5].view(torch.float32)
+    n_cnt, n_det = 4 * B, 4 * B * MAX_DET * 6
+    down = torch.empty(n_cnt + n_det + T * B * MAX_DET, dtype=torch.uint8, device=dev)
+    d_cnt = down[:n_cnt].view(torch.int32)
+    d_det = down[n_cnt:n_cnt + n_det].view(torch.float32).view(B, MAX_DET, 6)
+    d_tp = down[n_cnt + n_det:].view(T, B, MAX_DET)
+    pred = ops.detect_scores(logits, boxes, d_iptr, d_scale, softmax)
+    ops.nms_batched(pred, d_iptr, conf_thres, iou_thres, False, det=d_det, det_count=d_cnt)
+    ops.detect_match(d_det, d_cnt, d_gbox, d_glab, d_gptr, d_th, out=d_tp)
+    host = down.cpu().numpy()
+    return _unpack_statistics(host[:n_cnt].view(np.int32), host[n_cnt:n_cnt + n_det].view(np.float32).reshape(B, MAX_DET, 6),
+                              host[n_cnt + n_det:].reshape(T, B, MAX_DET))
+
+
 # ---------------------------------------------------------------------------------------------
 # utils/det_util.py:71-202 — host-side metric code (numpy), same conventions (+1 pixel box sizes in bbox_iou)
 # ---------------------------------------------------------------------------------------------
