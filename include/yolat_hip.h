@@ -123,6 +123,15 @@ int yolat_graph_prepare(const int64_t* edge, int64_t stride_e, int64_t stride_c,
                         int32_t* seg_ptr, int32_t* node_seg, int32_t* work, int32_t* status,
                         yolat_stream_t stream);
 
+/* The launch plan yolat_graph_prepare takes for a graph of N nodes and E edges when `other_wgs` further workgroups
+ * (proposal segments: ceil((N + 1) / 1024) with bbox_idx; node side of the first conv layer: ceil(N / 256)) ride in the
+ * launch.  Pure host arithmetic, no GPU needed.  Returns 1 for the one-launch form (*rows = destination rows per CSR
+ * workgroup, *csr_wgs = ceil(N / rows)), 0 for the four-launch form (*rows = *csr_wgs = 0).  One launch needs
+ * E <= 98304, rows <= 256, rows * E / N <= 2048 (half a workgroup's 4096 list slots at uniform degree; one row is the
+ * floor) and csr_wgs + other_wgs <= 250; within that, rows = 100 where the grid allows it, else the fewest rows that fit.
+ * YOLAT_PREP_R / YOLAT_PREP_SMALL are honoured as in the launch itself. */
+int yolat_graph_prepare_plan(int64_t N, int64_t E, int64_t other_wgs, int32_t* rows, int32_t* csr_wgs);
+
 /* dst[r, 0:width] = src[idx[r], 0:width]  (e_attr -> CSR order; fp32)                           */
 int yolat_gather_rows(const float* src, int64_t ld_src, const int32_t* idx, int64_t rows,
                       int64_t width, float* dst, int64_t ld_dst, yolat_stream_t stream);

@@ -26,12 +26,12 @@ def main(path, skip_first=0):
     tot = sum(a[1] for a in agg.values())
     print("# %d dispatches, %d distinct kernels, GPU-busy %.3f ms over a %.3f ms window" %
           (len(rows), len(agg), tot / 1e6, (t1 - t0) / 1e6))
-    print("%-100s %7s %10s %9s %9s %9s %6s %9s %6s %5s %6s" % ("kernel", "calls", "total_us", "avg_us", "min_us", "max_us",
-                                                                "pct", "grid_x", "grid_y", "vgpr", "lds"))
+    print("%-100s %7s %10s %9s %9s %9s %6s %9s %6s %5s %6s %5s" % ("kernel", "calls", "total_us", "avg_us", "min_us", "max_us",
+                                                                "pct", "grid_x", "grid_y", "vgpr", "lds", "wg_x"))
     for (name, gx, gy), a in sorted(agg.items(), key=lambda kv: -kv[1][1]):
-        print("%-100s %7d %10.1f %9.2f %9.2f %9.2f %6.2f %9d %6d %5d %6d" % (name[:100], a[0], a[1] / 1e3, a[1] / a[0] / 1e3,
+        print("%-100s %7d %10.1f %9.2f %9.2f %9.2f %6.2f %9d %6d %5d %6d %5d" % (name[:100], a[0], a[1] / 1e3, a[1] / a[0] / 1e3,
                                                                            a[2] / 1e3, a[3] / 1e3, 100.0 * a[1] / tot, gx, gy,
-                                                                           a[6] + a[7], a[8]))
+                                                                           a[6] + a[7], a[8], a[5]))
 
 
 if __name__ == "__main__":

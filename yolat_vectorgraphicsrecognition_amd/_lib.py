@@ -185,6 +185,7 @@ SIGNATURES = {
     "yolat_graph_work_elems": (c_sz, [c_i64, c_i64]),
     "yolat_graph_prepare": (c_int, [c_p, c_i64, c_i64, c_p, c_p, c_i64, c_i64, c_i64, c_p, c_p, c_p, c_p, c_p,
                                     c_p, c_p, c_p, c_p, c_p]),
+    "yolat_graph_prepare_plan": (c_int, [c_i64, c_i64, c_i64, c_p, c_p]),
     "yolat_gather_rows": (c_int, [c_p, c_i64, c_p, c_i64, c_i64, c_p, c_i64, c_p]),
     "yolat_bn_stats_elems": (c_sz, [c_i64, c_i64]),
     "yolat_linear_fwd": (c_int, [c_p, c_i64, c_i64, c_i64, c_p, c_p, c_int,

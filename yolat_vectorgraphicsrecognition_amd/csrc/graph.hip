@@ -485,7 +485,9 @@ __global__ void __launch_bounds__(256) k_prep_rows_node3(const int* local, const
 #define PS_RMAX 256
 #define PS_CAP 4096
 #define PS_PF 8
+#ifndef PS_NODE_ITERS
 #define PS_NODE_ITERS 2
+#endif
 struct PrepSmall {
   const int64_t* edge; long se, sc; const float4* attr; const int64_t* bbox; long P;
   int E, N, R, nprep, nseg;
@@ -687,17 +689,45 @@ __global__ void __launch_bounds__(PS_T) k_prep_small(PrepSmall g, NodeUv a, int 
   }
 }
 
-// rows per workgroup of k_prep_small, or 0 when the four-launch form is the one to use.  Every workgroup reads all E
-// edges: worth it while that is a few microseconds per workgroup and the whole grid is resident at once.
-static int prep_small_rows(int64_t N, int64_t E, int other_blocks) {
+// The plan of k_prep_small: destination rows per CSR workgroup, or 0 when the four-launch form is the one to use.
+// Every CSR workgroup walks all E edges through its own L1 (~4 us at E = 40 k, whatever it owns), so the walk is paid
+// once per WORKGROUP and a workgroup holds 16 waves and 80 KB of LDS of its CU meanwhile.  With one forward in flight
+// that is free; with 32 in flight it is what the launch costs ("The loaded regime").  The plan:
+//   rows per workgroup = min(PS_PLAN_ROWS, the rows that hold PS_PLAN_EDGES = PS_CAP / 2 edges at uniform degree)
+// (100 workgroups at cfg 2, N = 10 k, E = 40 k: measured — 40 / 64 are faster still under load and 1.5 / 0.7 us slower
+// one at a time, 200 is what "fill 250 CUs" gave until then), and when that grid with the segment / node-side
+// workgroups is more than one round of PS_PLAN_GRID CUs, fewer and fatter workgroups in what is left of the round, as
+// long as they keep R <= PS_RMAX and the edge headroom.
+// YOLAT_PREP_R=<1..PS_RMAX> (read once per process; tests and measurements) forces the rows per workgroup of every graph
+// within the E limit, whatever the grid then is.
+#define PS_PLAN_ROWS 100
+#define PS_PLAN_EDGES (PS_CAP / 2)
+#define PS_PLAN_GRID 250
+static int prep_small_rows(int64_t N, int64_t E, int64_t other_blocks) {
   static const bool on = []() { const char* e = getenv("YOLAT_PREP_SMALL"); return !(e && e[0] == '0'); }();
-  if (!on || E > 98304) return 0;
-  const int wgs = 250 - other_blocks;            // one workgroup per CU (16 waves), the whole grid resident at once
-  if (wgs < 16) return 0;
-  int R = yl_cdiv(N, wgs);
-  if (R < 16) R = 16;
-  if (R > PS_RMAX) return 0;
-  return R;
+  static const int forced = []() { const char* e = getenv("YOLAT_PREP_R"); const int r = e ? atoi(e) : 0;
+                                   return (r >= 1 && r <= PS_RMAX) ? r : 0; }();
+  if (!on || N <= 0 || E < 0 || E > 98304) return 0;
+  if (forced) return forced;
+  int64_t r_edges = E > 0 ? (int64_t)PS_PLAN_EDGES * N / E : PS_RMAX;      // R E / N <= PS_PLAN_EDGES
+  if (r_edges < 1) r_edges = 1;                                            // degree > PS_PLAN_EDGES: one row is the floor
+  int64_t R = PS_PLAN_ROWS;
+  if (R > r_edges) R = r_edges;
+  if (R > N) R = N;
+  if ((N + R - 1) / R + other_blocks > PS_PLAN_GRID) {
+    const int64_t room = PS_PLAN_GRID - other_blocks;
+    if (room < 1) return 0;
+    R = (N + room - 1) / room;
+    if (R > PS_RMAX || R > r_edges) return 0;
+  }
+  return (int)R;
+}
+
+extern "C" int yolat_graph_prepare_plan(int64_t N, int64_t E, int64_t other_wgs, int32_t* rows, int32_t* csr_wgs) {
+  const int R = (other_wgs < 0) ? 0 : prep_small_rows(N, E, other_wgs);
+  if (rows) *rows = R;
+  if (csr_wgs) *csr_wgs = R > 0 ? (int32_t)((N + R - 1) / R) : 0;
+  return R > 0 ? 1 : 0;
 }
 
 extern "C" size_t yolat_graph_work_elems(int64_t N, int64_t E) {
