@@ -286,8 +286,14 @@ extern "C" int yolat_debug_edge_stamps(long long* out, int n) {
 #else
 #define EDGE_STAMP(k) do { } while (0)
 #endif
-template <int NG>
-__global__ void __launch_bounds__(256) k_edge_uv_mlp2_mean(const float* __restrict__ UV, long ld_uv,
+// NEXT (NG == 1 only): the instance that also carries the next layer's node side (EdgeNext).  The last conv layer's
+// launch has none, and its instance must not pay the 32 B-fragment registers for it.
+// Registers: an NG == 1 workgroup is one wave per SIMD, and what decides how many of them share a CU is the register
+// file (512 per lane per SIMD), before LDS (4 x 32.6 KB) and wave slots: both NG == 1 instances are bound to 4 waves per
+// SIMD, i.e. <= 128 unified VGPRs, and reach it without scratch (tests/test_kernel_resources_host.py).  NG == 4 keeps
+// the open bound: it spills at 128.
+template <int NG, bool NEXT>
+__global__ void __launch_bounds__(256, NG == 1 ? 4 : 1) k_edge_uv_mlp2_mean(const float* __restrict__ UV, long ld_uv,
                                                            const int* __restrict__ src,
                                                            const int* __restrict__ dst,
                                                            const float* __restrict__ attr,
@@ -312,7 +318,7 @@ __global__ void __launch_bounds__(256) k_edge_uv_mlp2_mean(const float* __restri
   __shared__ int rp[16 * NG + 1];
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int wm = wave >> 1, wn = wave & 1, l31 = lane & 31, lhi = lane >> 5;
-  if ((int)blockIdx.x >= tiles) {
+  if (NEXT && (int)blockIdx.x >= tiles) {
     // s'[r0 .. r0+63] = relu(((s . Wn'^T) + bn') * sn' + tn'): one 64 x 64 x 64 tile on the same LDS tiles and the same
     // MFMA loop (k ascending in pairs) as layer 2 below — bit-identical to k_gemm_nt_node3's tile
     const int r0 = (blockIdx.x - tiles) * 64;
@@ -354,7 +360,8 @@ __global__ void __launch_bounds__(256) k_edge_uv_mlp2_mean(const float* __restri
   // the tile's edge range straight from global (same two addresses in every lane: one broadcast load each), so that
   // the first pass's index loads go out before the barrier below instead of after it, and the f_out rows this thread
   // finishes with at the very end: both shorten the workgroup's chain of dependent global round trips, which is what
-  // a small graph's launch time consists of (715 workgroups, all resident at once, at E = 40 k)
+  // a small graph's launch time consists of (715 node tiles at E = 40 k, 872 / 971 workgroups with the riders: four per CU
+  // by registers and LDS, so one round of an empty GPU's 1024 slots)
   const int e0g = row_ptr[n0], e1g = row_ptr[n0 + nn];
   int di0[4], si0[4];
 #pragma unroll
@@ -384,15 +391,6 @@ __global__ void __launch_bounds__(256) k_edge_uv_mlp2_mean(const float* __restri
     const int i = tid + t * 256;
     float* d = W2s + (i >> 4) * LDH + 4 * (i & 15);
     d[0] = rw2[t][0]; d[1] = rw2[t][1]; d[2] = rw2[t][2]; d[3] = rw2[t][3];
-  }
-  // next layer's node side (NG == 1): the first column tile's B fragments travel with the loads above, the other two
-  // are fetched under the previous tile's MFMAs (see the end of the kernel)
-  float bf0[16];
-  if constexpr (NG == 1) {
-    if (nx.Wp != nullptr) {
-#pragma unroll
-      for (int ks = 0; ks < 16; ++ks) bf0[ks] = nx.Wp[(wave * 16 + ks) * 64 + lane];
-    }
   }
   EDGE_STAMP(1);
   __syncthreads();
@@ -488,43 +486,44 @@ __global__ void __launch_bounds__(256) k_edge_uv_mlp2_mean(const float* __restri
   }
   EDGE_STAMP(9);
   // ---- node side of the NEXT layer for this tile's nodes (EdgeNext, common.hpp): [nn <= 16, 64] x [192, 64]^T
-  if constexpr (NG == 1) {
-    if (nx.Wp != nullptr) {
-      // the loop above ended with a barrier (or never ran): Hs is free; rows >= nn hold the clamped load of row N-1 or
-      // stale sums — finite or not, their products only reach output rows that are never stored
-      float* frow = Hs + rb * LDH + 4 * q;
-      const float4 fz = (rb < nn) ? fo[0] : make_float4(0.f, 0.f, 0.f, 0.f);
-      frow[0] = fz.x; frow[1] = fz.y; frow[2] = fz.z; frow[3] = fz.w;
-      __syncthreads();
-      const int fr = lane & 15, fk = lane >> 4;
-      float bfa[16], bfb[16];
+  if constexpr (NG == 1 && NEXT) {
+    // the first column tile's B fragments are fetched here, after the pass loop, and the other two under the previous
+    // tile's MFMAs: held from before the first barrier they cost 16 registers through the whole edge phase, which put
+    // the kernel over the 128 of four workgroups per CU
+    float bfa[16], bfb[16];
 #pragma unroll
-      for (int ks = 0; ks < 16; ++ks) bfa[ks] = bf0[ks];
+    for (int ks = 0; ks < 16; ++ks) bfa[ks] = nx.Wp[(wave * 16 + ks) * 64 + lane];
+    // the loop above ended with a barrier (or never ran): Hs is free; rows >= nn hold the clamped load of row N-1 or
+    // stale sums — finite or not, their products only reach output rows that are never stored
+    float* frow = Hs + rb * LDH + 4 * q;
+    const float4 fz = (rb < nn) ? fo[0] : make_float4(0.f, 0.f, 0.f, 0.f);
+    frow[0] = fz.x; frow[1] = fz.y; frow[2] = fz.z; frow[3] = fz.w;
+    __syncthreads();
+    const int fr = lane & 15, fk = lane >> 4;
 #pragma unroll
-      for (int t = 0; t < 3; ++t) {
-        const int ct = wave + 4 * t;                   // 12 column tiles of 16: UV' 0..7, root' 8..11
-        if (t < 2) {
+    for (int t = 0; t < 3; ++t) {
+      const int ct = wave + 4 * t;                   // 12 column tiles of 16: UV' 0..7, root' 8..11
+      if (t < 2) {
 #pragma unroll
-          for (int ks = 0; ks < 16; ++ks) bfb[ks] = nx.Wp[((ct + 4) * 16 + ks) * 64 + lane];
-        }
-        const int col = ct * 16 + fr;
-        const float bias = nx.bias[col];
-        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int ks = 0; ks < 16; ++ks)
-          acc = __builtin_amdgcn_mfma_f32_16x16x4f32(Hs[fr * LDH + 4 * ks + fk], bfa[ks], acc, 0, 0, 0);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int row = 4 * fk + r;
-          if (row < nn) {
-            const float v = acc[r] + bias;
-            if (col < 128) nx.UV[(long)(n0 + row) * nx.ld_uv + col] = v;
-            else nx.root[(long)(n0 + row) * nx.ld_root + (col - 128)] = v;
-          }
-        }
-#pragma unroll
-        for (int ks = 0; ks < 16; ++ks) bfa[ks] = bfb[ks];
+        for (int ks = 0; ks < 16; ++ks) bfb[ks] = nx.Wp[((ct + 4) * 16 + ks) * 64 + lane];
       }
+      const int col = ct * 16 + fr;
+      const float bias = nx.bias[col];
+      f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int ks = 0; ks < 16; ++ks)
+        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(Hs[fr * LDH + 4 * ks + fk], bfa[ks], acc, 0, 0, 0);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int row = 4 * fk + r;
+        if (row < nn) {
+          const float v = acc[r] + bias;
+          if (col < 128) nx.UV[(long)(n0 + row) * nx.ld_uv + col] = v;
+          else nx.root[(long)(n0 + row) * nx.ld_root + (col - 128)] = v;
+        }
+      }
+#pragma unroll
+      for (int ks = 0; ks < 16; ++ks) bfa[ks] = bfb[ks];
     }
   }
   EDGE_STAMP(10);
@@ -952,12 +951,16 @@ int yl_edge_uv_mlp2_mean_eval_impl(const float* UV, int64_t ld_uv, const int32_t
     if (did_next) *did_next = 1;
   }
   const unsigned grid = (unsigned)tiles + (unsigned)nx.s_tiles + (unsigned)pr.blocks;
-  if (npt <= 16)
-    hipLaunchKernelGGL(k_edge_uv_mlp2_mean<1>, dim3(grid), dim3(256), 0, (hipStream_t)stream, UV, (long)ld_uv,
+  if (npt <= 16 && nx.Wp != nullptr)
+    hipLaunchKernelGGL((k_edge_uv_mlp2_mean<1, true>), dim3(grid), dim3(256), 0, (hipStream_t)stream, UV, (long)ld_uv,
+                       src_csr, dst_csr, attr_csr, row_ptr, (int)N, (int)npt, Wc4, b1, s1, t1, w2, b2, s2, t2, f_out,
+                       (long)ld_fo, (int)E, tiles, pr, nx);
+  else if (npt <= 16)
+    hipLaunchKernelGGL((k_edge_uv_mlp2_mean<1, false>), dim3(grid), dim3(256), 0, (hipStream_t)stream, UV, (long)ld_uv,
                        src_csr, dst_csr, attr_csr, row_ptr, (int)N, (int)npt, Wc4, b1, s1, t1, w2, b2, s2, t2, f_out,
                        (long)ld_fo, (int)E, tiles, pr, nx);
   else
-    hipLaunchKernelGGL(k_edge_uv_mlp2_mean<4>, dim3(grid), dim3(256), 0, (hipStream_t)stream, UV, (long)ld_uv,
+    hipLaunchKernelGGL((k_edge_uv_mlp2_mean<4, false>), dim3(grid), dim3(256), 0, (hipStream_t)stream, UV, (long)ld_uv,
                        src_csr, dst_csr, attr_csr, row_ptr, (int)N, (int)npt, Wc4, b1, s1, t1, w2, b2, s2, t2, f_out,
                        (long)ld_fo, (int)E, tiles, pr, nx);
   YL_LAUNCH_CHECK();

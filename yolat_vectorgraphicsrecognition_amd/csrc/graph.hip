@@ -590,8 +590,9 @@ __global__ void __launch_bounds__(PS_T) k_prep_small(PrepSmall g, NodeUv a, int 
     else for (long p = prev + 1; p <= cur; ++p) g.seg_ptr[p] = t;
     return;
   }
-  // one pool, two layouts (the whole launch is sized by this role: below 80 KB two workgroups share a CU, so the
-  // segment / node-side workgroups run beside the CSR ones instead of queueing behind them):
+  // one pool, two layouts (the whole launch is sized by this role, and the segment / node-side workgroups inherit it.
+  // By LDS, 78 KB, two workgroups would share a CU; by registers ONE does: 16 waves = 4 per SIMD x 80 allocated = 320 of
+  // a SIMD's 512, a second needs 640 — DESIGN.md 6 "The register file"):
   //   list path     list[PS_CAP] | grp[PS_CAP]            (edge id | local row << 20)
   //   ordered path  msk[PS_NW][PS_RMAX] (64-bit) | cnt[PS_NW][PS_RMAX]
   __shared__ unsigned long long pool[PS_NW * PS_RMAX + PS_NW * PS_RMAX / 2];
