@@ -1157,6 +1157,25 @@ int yolat_fusion_pool_train_bwd_parts_bf16(const float* A, int64_t lda, int64_t 
                                            int64_t ldg, float* dW, float* dbias, float* dgamma, float* dbeta, float* dA,
                                            int64_t ldda, float* work, int parts, yolat_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Training augmentation on a collated device batch (augment.hip): SESYDFloorPlan.random_transfer
+ * (Datasets/graph_dict3.py:283-298 with __transform__, :236-258) and the update_bbox that follows it (:934-959), in
+ * place, ONE launch, no atomics, nothing read back.
+ *   pos [N,2] fp32 contiguous (8-byte aligned);  x [N, >= 2] fp32 with leading dimension ldx: columns col_x / col_y
+ *   receive the new positions (feats = [0,0,0,pos], :966-969: 3 and 4);  seg_ptr [P+1]: the nodes of proposal p are
+ *   [seg_ptr[p], seg_ptr[p+1]) (the prepared graph's, or yolat_segment_ptr of bbox_idx);  prop_ptr [B+1] int64: the
+ *   proposals of graph b are [prop_ptr[b], prop_ptr[b+1]) (slices['labels'] of the collate);  bbox [P,4] fp32
+ *   contiguous (16-byte aligned);  params [B,8] float64, row b = cos(angle), sin(angle), scale, translate x, translate
+ *   y, flip x, flip y (0.0 / 1.0), 0 — the host draws them and computes the trigonometry.
+ * A node moves in float64 in the reference's operation order (every product and sum rounded on its own) and is rounded
+ * once to fp32; bbox row p = (min x, min y, max x, max y) of the rounded positions of its nodes.  A proposal WITHOUT a
+ * node keeps its bbox row (the reference's update_bbox would return one row fewer there); nodes and proposals outside
+ * every range stay as they are.  Entries of seg_ptr / prop_ptr are clamped to [0,N] / [0,P] before use.
+ * N == 0, P == 0 or B == 0: returns 0 without a launch.                                                           */
+int yolat_augment_batch(float* pos, float* x, int64_t ldx, int64_t col_x, int64_t col_y, const int32_t* seg_ptr,
+                        const int64_t* prop_ptr, float* bbox, const double* params, int64_t N, int64_t P, int64_t B,
+                        yolat_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

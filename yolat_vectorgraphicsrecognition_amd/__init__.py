@@ -10,6 +10,7 @@ Layout
     architecture.py  cad_recognition/architecture3cc_rpn_gp_iter2 mirror: SparseCADGCN, ...
     trainer.py       flat-buffer Adam + data-parallel step (RCCL all-reduce of one gradient bucket)
     data.py          Data bag, collate / offset fix-up, synthetic Bezier-graph generators
+    augment.py       training augmentation (graph_dict3.random_transfer + update_bbox) on host items / device batches
     proposals.py     box-proposal generation (graph_dict3._get_proposal) over the native window / edge pick-up op
     dropin/          import shims so the reference's own scripts resolve gcn_lib / torch_scatter / ...
 """
@@ -26,5 +27,7 @@ from .trainer import (FlatParams, FlatAdam, Trainer, shard_graph_ids, allreduce_
                       load_reference_checkpoint)
 
 from .proposals import get_proposal, proposal_windows  # noqa: F401
+from . import augment  # noqa: F401
+from .augment import AugParams, draw_params, augment_item, augment_batch_  # noqa: F401
 
 __version__ = "0.2.0"

@@ -337,6 +337,7 @@ SIGNATURES = {
     "yolat_forward_eval_bf16_loc": (c_int, [ctypes.POINTER(ModelEvalBf16), c_p, c_i64, c_p, c_i64, c_i64, c_p, c_p,
                                             ctypes.POINTER(GraphCsr), c_i64, c_i64, c_i64, c_p, c_i64, c_p, c_sz, c_p,
                                             ctypes.POINTER(Locality), c_int, c_p]),
+    "yolat_augment_batch": (c_int, [c_p, c_p, c_i64, c_i64, c_i64, c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_p]),
 }
 
 

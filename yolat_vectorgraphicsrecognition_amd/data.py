@@ -630,12 +630,25 @@ class DeviceLoader(object):
     further batches have been drawn, and everything that reads them must have been ENQUEUED, on the stream that was current
     when the batch was drawn, by the time the next batch is drawn (the loader then hands the slot back behind an event on
     that stream).  Consecutive batches may be drawn under different streams (``torch.cuda.set_stream`` between draws): their
-    forwards then overlap on the GPU and the hand-over disappears behind them (``slots`` >= streams + 2)."""
+    forwards then overlap on the GPU and the hand-over disappears behind them (``slots`` >= streams + 2).
 
-    def __init__(self, batches, device="cuda", slots=3, csr=True):
+    ``augment``: the reference's training augmentation (``--data_aug true``: random_transfer + update_bbox,
+    Datasets/graph_dict3.py:283-298,934-959) on every batch.  ``True`` draws the parameters with ``augment.draw_params``
+    from the global generators, a callable ``B -> AugParams`` from wherever it likes — when the batch is DRAWN, in batch
+    order, on the consumer's thread — and ``augment.augment_batch_`` is enqueued on the drawing stream before the batch
+    is returned (the draws stay on the batch as ``batch._aug_params``).  ``None``: no augmentation."""
+
+    def __init__(self, batches, device="cuda", slots=3, csr=True, augment=None):
         from ._lib import lib
         if slots < 2:
             raise ValueError("DeviceLoader needs at least two slots")
+        if augment is None or augment is False:
+            self._augment = None
+        else:
+            from . import augment as _aug
+            if augment is not True and not callable(augment):
+                raise TypeError("DeviceLoader: augment must be None, True or a callable B -> AugParams")
+            self._augment = (_aug.draw_params if augment is True else augment, _aug.augment_batch_)
         self._it = iter(batches)
         self._device = torch.device(device)
         self._slots = int(slots)
@@ -747,6 +760,10 @@ class DeviceLoader(object):
         bd["_device_buffer"] = mem[2]
         bd["_yolat_loc"] = loc           # prepared graph / slot addresses: nothing the consumer edits in place
         bd["_loader"] = self             # the slot buffers are the loader's: a batch keeps it (and them) alive
+        if self._augment is not None:
+            draw, apply_ = self._augment
+            params = bd["_aug_params"] = draw(B)
+            apply_(batch, slices, params)
         return batch, slices
 
     def _raw_fast_path(self, bd, first, ship, st, base):

@@ -271,6 +271,44 @@ def build_graph(edge, e_attr, bbox_idx, num_nodes, num_proposals):
     return g
 
 
+def segment_ptr(bbox_idx, num_proposals):
+    """[P + 1] int32 node range pointers of a non-decreasing int64 ``bbox_idx`` [N] (yolat_segment_ptr)."""
+    P, N = int(num_proposals), int(bbox_idx.shape[0])
+    dev = bbox_idx.device
+    # zero-initialised, like build_graph's: with an unsorted bbox_idx the pointers stay inside [0, N]
+    z = torch.zeros(4 + (P + 1 + 3) // 4 * 4 + max(N, 1), dtype=torch.int32, device=dev)
+    seg = z[4:4 + P + 1]
+    check(lib.yolat_segment_ptr(_i(bbox_idx, torch.int64, "bbox_idx"), N, P, seg.data_ptr(),
+                                z[4 + (P + 1 + 3) // 4 * 4:].data_ptr(), z[0:1].data_ptr(), _stream()), "yolat_segment_ptr")
+    return seg
+
+
+def augment_batch(pos, x, seg_ptr, prop_ptr, bbox, params, cols=(3, 4)):
+    """In place: the reference's random_transfer + update_bbox on a collated device batch (yolat_augment_batch).
+    pos [N,2] / bbox [P,4] fp32 contiguous, x [N,C] fp32 (columns `cols` receive the positions), seg_ptr [P+1] int32,
+    prop_ptr [B+1] int64, params [B,8] float64 (augment.AugParams.block()) — all on one device."""
+    pos_ptr = _f(pos, "pos")
+    N, P, B = int(pos.shape[0]), int(bbox.shape[0]), int(params.shape[0])
+    if pos.dim() != 2 or pos.shape[1] != 2 or bbox.dim() != 2 or bbox.shape[1] != 4 or x.dim() != 2 or x.shape[0] != N:
+        raise ValueError("augment_batch: pos must be [N,2], x [N,C], bbox [P,4]")
+    if (N > 0 and not pos.is_contiguous()) or (P > 0 and not bbox.is_contiguous()):
+        raise ValueError("augment_batch: pos and bbox must be contiguous")
+    if not params.is_cuda or params.dtype != torch.float64 or params.dim() != 2 or params.shape[1] != 8 or \
+            not params.is_contiguous():
+        raise TypeError("augment_batch: params must be a contiguous [B,8] float64 CUDA tensor")
+    if seg_ptr.shape[0] != P + 1 or prop_ptr.shape[0] != B + 1:
+        raise ValueError("augment_batch: seg_ptr must be [P+1] and prop_ptr [B+1]")
+    cx, cy = int(cols[0]), int(cols[1])
+    if not (0 <= cx < x.shape[1] and 0 <= cy < x.shape[1]) or cx == cy:
+        raise ValueError("augment_batch: position columns %r outside x [N,%d]" % (cols, x.shape[1]))
+    for t in (x, seg_ptr, prop_ptr, bbox, params):
+        if t.device != pos.device:
+            raise RuntimeError("augment_batch: every operand must live on %s" % pos.device)
+    check(lib.yolat_augment_batch(pos_ptr, _f(x, "x"), _ld(x), cx, cy, _i(seg_ptr, torch.int32, "seg_ptr"),
+                                  _i(prop_ptr, torch.int64, "prop_ptr"), _f(bbox, "bbox"), params.data_ptr(), N, P, B,
+                                  _stream()), "yolat_augment_batch")
+
+
 # ---------------------------------------------------------------------------------------------
 # dense
 # ---------------------------------------------------------------------------------------------
