@@ -659,15 +659,6 @@ extern "C" int yolat_edge_uv_mlp2_mean_eval_bf16(const uint16_t* UV, int64_t ld_
 // host side
 // ------------------------------------------------------------------------------------------------
 namespace {
-struct Carver {
-  char* base; size_t off;
-  template <class T> T* take(size_t n) {
-    off = (off + 255) & ~(size_t)255;
-    T* p = reinterpret_cast<T*>(base + off);
-    off += n * sizeof(T);
-    return p;
-  }
-};
 struct PlanH {
   int* row_ptr; int* perm; int* src; int* dst; float* attr; int* work; int* seg_ptr; int* node_seg;
   u16* UV; float* root; u16* f_tmp[YOLAT_MAX_LAYERS]; u16* s_tmp[YOLAT_MAX_LAYERS];
@@ -676,7 +667,7 @@ struct PlanH {
   size_t bytes;
 };
 PlanH carve_h(const yolat_model_eval* m, long N, long E, long P, void* ws) {
-  Carver c; c.base = reinterpret_cast<char*>(ws); c.off = 0;
+  Carver c{reinterpret_cast<char*>(ws), 0};
   PlanH p;
   const long C = m->C, F = m->F, D = C * m->n_blocks_out, Ee = E > 0 ? E : 1;
   p.row_ptr = c.take<int>(N + 1); p.perm = c.take<int>(Ee); p.src = c.take<int>(Ee); p.dst = c.take<int>(Ee);
@@ -730,11 +721,6 @@ int launch_hgemm(const AL& A, const HOp& B, const Epilogue& ep, long M, long N, 
 }
 }  // namespace
 
-#define YL_TRY(call)            \
-  do {                          \
-    int rc__ = (call);          \
-    if (rc__ != 0) return rc__; \
-  } while (0)
 // one profiled stage: `body` is a statement block that may `return` an error code
 #define YL_HSTAGE(name, flops, bytes, ...)                                    \
   do {                                                                        \
@@ -781,8 +767,7 @@ extern "C" int yolat_forward_eval_bf16_csr(const yolat_model_eval_bf16* mh, cons
                                            const yolat_graph_csr* g, int64_t N, int64_t E, int64_t P, float* logits,
                                            int64_t ld_logits, void* workspace, size_t workspace_bytes,
                                            yolat_stream_t stream) {
-  if (!g || !g->row_ptr || !g->seg_ptr || !g->node_seg || (E > 0 && (!g->src || !g->dst || !g->attr)))
-    return YOLAT_E_INVALID;
+  YL_TRY(yl_adopt_graph<PlanH>(g, E, nullptr));
   int32_t unused_status = 0;
   return forward_eval_bf16_impl(mh, x, ldx, nullptr, 0, 0, nullptr, reinterpret_cast<const int64_t*>(g->node_seg), N, E, P,
                                 logits, ld_logits, workspace, workspace_bytes, &unused_status, stream, g);
@@ -795,7 +780,7 @@ extern "C" int yolat_forward_eval_bf16_loc(const yolat_model_eval_bf16* mh, cons
                                            size_t workspace_bytes, int32_t* status, const yolat_locality* loc, int primed,
                                            yolat_stream_t stream) {
   if (g != nullptr) {
-    if (!g->row_ptr || !g->seg_ptr || !g->node_seg || (E > 0 && (!g->src || !g->dst || !g->attr))) return YOLAT_E_INVALID;
+    YL_TRY(yl_adopt_graph<PlanH>(g, E, nullptr));
     if (!status) return YOLAT_E_INVALID;
     return forward_eval_bf16_impl(mh, x, ldx, nullptr, 0, 0, nullptr, reinterpret_cast<const int64_t*>(g->node_seg), N, E, P,
                                   logits, ld_logits, workspace, workspace_bytes, status, stream, g, false, loc);
@@ -816,11 +801,7 @@ static int forward_eval_bf16_impl(const yolat_model_eval_bf16* mh, const float* 
   const yolat_model_eval* m = mh->base;
   PlanH p = carve_h(m, N, E, P, workspace);
   if (p.bytes > workspace_bytes) return YOLAT_E_INVALID;
-  if (g != nullptr) {                 // prepared graph (collate.hip): the caller's arrays, never written here
-    p.row_ptr = const_cast<int*>(g->row_ptr); p.src = const_cast<int*>(g->src); p.dst = const_cast<int*>(g->dst);
-    p.attr = const_cast<float*>(g->attr); p.seg_ptr = const_cast<int*>(g->seg_ptr);
-    p.node_seg = const_cast<int*>(g->node_seg);
-  }
+  if (g != nullptr) YL_TRY(yl_adopt_graph(g, E, &p));      // prepared graph (collate.hip): the caller's arrays
   hipStream_t st = (hipStream_t)stream;
   const long C = m->C, F = m->F, D = C * m->n_blocks_out, ZW = 2 * (F + D);
   const int lo = m->n_blocks - m->n_blocks_out;

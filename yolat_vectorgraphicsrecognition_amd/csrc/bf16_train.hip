@@ -25,12 +25,6 @@
 //                         i.e. from the same bf16 products.
 #include "segmax.hpp"
 
-#define YL_TRY(call)            \
-  do {                          \
-    int rc__ = (call);          \
-    if (rc__ != 0) return rc__; \
-  } while (0)
-
 typedef unsigned bt_u32x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bt_bf16x8 __attribute__((ext_vector_type(8)));
 

@@ -26,8 +26,39 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
     if (e__ != hipSuccess) return (int)e__;        \
   } while (0)
 
+#define YL_TRY(call)            \
+  do {                          \
+    int rc__ = (call);          \
+    if (rc__ != 0) return rc__; \
+  } while (0)
+
 static inline int yl_cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 static inline bool yl_aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
+
+// Bump allocation of a whole-forward workspace in 256-byte aligned pieces.  base == nullptr: sizing only (off is the size).
+struct Carver {
+  char* base; size_t off;
+  template <class T> T* take(size_t n) {
+    off = (off + 255) & ~(size_t)255;
+    T* p = reinterpret_cast<T*>(base + off);
+    off += n * sizeof(T);
+    return p;
+  }
+};
+
+// A prepared device graph (yolat_graph_csr; collate.hip): YOLAT_E_INVALID unless it holds every array a forward over E edges
+// reads.  With a plan, the plan's graph members are pointed at the caller's arrays (the kernels read them, never write).
+template <class PlanT>
+static inline int yl_adopt_graph(const yolat_graph_csr* g, int64_t E, PlanT* p) {
+  if (!g || !g->row_ptr || !g->seg_ptr || !g->node_seg || (E > 0 && (!g->src || !g->dst || !g->attr)))
+    return YOLAT_E_INVALID;
+  if (p != nullptr) {
+    p->row_ptr = const_cast<int*>(g->row_ptr); p->src = const_cast<int*>(g->src); p->dst = const_cast<int*>(g->dst);
+    p->attr = const_cast<float*>(g->attr); p->seg_ptr = const_cast<int*>(g->seg_ptr);
+    p->node_seg = const_cast<int*>(g->node_seg);
+  }
+  return 0;
+}
 // YOLAT_STRICT_FP32=1: every GEMM of the fp32 mode runs on the fp32-input MFMA kernels (v_mfma_f32_32x32x2_f32) instead
 // of the bf16x6 emulation (x6.hpp) — the one switch for strict-parity runs (IEEE Inf / NaN propagation, fp32 MFMA
 // summation order); the Python side (plan.py, ops.py) reads the same variable.

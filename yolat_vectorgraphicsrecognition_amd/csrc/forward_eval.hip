@@ -5,16 +5,6 @@
 #include "common.hpp"
 
 namespace {
-struct Carver {
-  char* base; size_t off, cap;
-  template <class T> T* take(size_t n) {
-    off = (off + 255) & ~(size_t)255;
-    T* p = reinterpret_cast<T*>(base + off);
-    off += n * sizeof(T);
-    return p;
-  }
-};
-
 struct Plan {
   int* row_ptr; int* perm; int* src; int* dst; float* attr; int* work; int* seg_ptr; int* node_seg;
   float* H1; float* H2; float* UV; float* UV2; float* f_tmp[YOLAT_MAX_LAYERS]; float* s_tmp[YOLAT_MAX_LAYERS];
@@ -25,7 +15,7 @@ struct Plan {
 };
 
 Plan carve(const yolat_model_eval* m, long N, long E, long P, void* ws) {
-  Carver c; c.base = reinterpret_cast<char*>(ws); c.off = 0; c.cap = 0;
+  Carver c{reinterpret_cast<char*>(ws), 0};
   Plan p;
   const long C = m->C, F = m->F, D = C * m->n_blocks_out, Ee = E > 0 ? E : 1;
   p.row_ptr = c.take<int>(N + 1); p.perm = c.take<int>(Ee); p.src = c.take<int>(Ee); p.dst = c.take<int>(Ee);
@@ -63,12 +53,6 @@ static int prep_node_uv(const int64_t* edge, int64_t stride_e, int64_t stride_c,
   return yl_graph_prepare_impl(edge, stride_e, stride_c, e_attr, bbox_idx, E, N, P, p.row_ptr, p.perm, p.src, p.dst,
                                p.attr, p.seg_ptr, p.node_seg, p.work, status, &a, primed, stream);
 }
-
-#define YL_TRY(call)            \
-  do {                          \
-    int rc__ = (call);          \
-    if (rc__ != 0) return rc__; \
-  } while (0)
 
 // ---- stage profiler (hipEvent pairs on the launch stream) ------------------------------------------
 #include <stdlib.h>
@@ -170,8 +154,7 @@ static int forward_eval_impl(const yolat_model_eval* m, const float* x, int64_t 
 extern "C" int yolat_forward_eval_csr(const yolat_model_eval* m, const float* x, int64_t ldx, const yolat_graph_csr* g,
                                       int64_t N, int64_t E, int64_t P, float* logits, int64_t ld_logits, void* workspace,
                                       size_t workspace_bytes, yolat_stream_t stream) {
-  if (!g || !g->row_ptr || !g->seg_ptr || !g->node_seg || (E > 0 && (!g->src || !g->dst || !g->attr)))
-    return YOLAT_E_INVALID;
+  YL_TRY(yl_adopt_graph<Plan>(g, E, nullptr));
   int32_t unused_status = 0;
   return forward_eval_impl(m, x, ldx, nullptr, 0, 0, nullptr, reinterpret_cast<const int64_t*>(g->node_seg), N, E, P, logits,
                            ld_logits, workspace, workspace_bytes, &unused_status, false, stream, g);
@@ -211,11 +194,7 @@ static int forward_eval_impl(const yolat_model_eval* m, const float* x, int64_t 
     return YOLAT_E_INVALID;
   Plan p = carve(m, N, E, P, workspace);
   if (p.bytes > workspace_bytes) return YOLAT_E_INVALID;
-  if (g != nullptr) {                 // prepared graph: the kernels read the caller's arrays (never written here)
-    p.row_ptr = const_cast<int*>(g->row_ptr); p.src = const_cast<int*>(g->src); p.dst = const_cast<int*>(g->dst);
-    p.attr = const_cast<float*>(g->attr); p.seg_ptr = const_cast<int*>(g->seg_ptr);
-    p.node_seg = const_cast<int*>(g->node_seg);
-  }
+  if (g != nullptr) YL_TRY(yl_adopt_graph(g, E, &p));      // prepared graph: the kernels read the caller's arrays
   const long C = m->C, F = m->F, D = C * m->n_blocks_out, ZW = 2 * (F + D);
   const int lo = m->n_blocks - m->n_blocks_out;
 

@@ -25,12 +25,6 @@
 #include "common.hpp"
 #include <stdlib.h>
 
-#define YL_TRY(call)            \
-  do {                          \
-    int rc__ = (call);          \
-    if (rc__ != 0) return rc__; \
-  } while (0)
-
 constexpr int CS_ROWS = 512;    // rows per column-sum workgroup
 constexpr int FB_GRAM_S = 512;  // row slabs (= partial products) of the centered Gram matrix
 constexpr int FB_PROWS = 32;    // proposals per column-partial workgroup (128: one workgroup per CU at P = 8000, 12 KB of loads

@@ -218,20 +218,22 @@ class PackedGraph(Graph):
     node_seg = property(lambda self: self._view("node_seg"))
 
 
+def edge_layout(edge):
+    """(E, stride_e, stride_c) of an edge list given as [E,2] (data.edge) or as [2,E], its transposed view included: the
+    element strides between edges and between the two ends of one.  A [2,2] tensor is [E,2] unless it is a transposed
+    view (stride(0) == 1)."""
+    if edge.dim() == 2:
+        if edge.shape[1] == 2 and not (edge.shape[0] == 2 and edge.stride(0) == 1):
+            return edge.shape[0], edge.stride(0), edge.stride(1)
+        if edge.shape[0] == 2:
+            return edge.shape[1], edge.stride(1), edge.stride(0)
+    raise ValueError("edge must be [E,2] or [2,E]")
+
+
 def build_graph(edge, e_attr, bbox_idx, num_nodes, num_proposals):
     """edge: int64 CUDA tensor, either [E,2] (data.edge) or its [2,E] transposed view;
     e_attr: fp32 [E,4]; bbox_idx: int64 [N] or None."""
-    if edge.dim() != 2:
-        raise ValueError("edge must be 2-D")
-    if edge.shape[0] == 2 and edge.shape[1] != 2:
-        E, se, sc = edge.shape[1], edge.stride(1), edge.stride(0)
-    elif edge.shape[1] == 2:
-        if edge.shape[0] == 2 and edge.stride(0) == 1:      # a [2,2] transposed view
-            E, se, sc = 2, edge.stride(1), edge.stride(0)
-        else:
-            E, se, sc = edge.shape[0], edge.stride(0), edge.stride(1)
-    else:
-        raise ValueError("edge must be [E,2] or [2,E]")
+    E, se, sc = edge_layout(edge)
     dev = edge.device
     N, P = int(num_nodes), int(num_proposals)
     g = Graph()

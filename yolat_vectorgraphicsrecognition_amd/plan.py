@@ -39,10 +39,47 @@ def _x6_on(default=True):
     return bool(default)
 
 
-def _fold(bn, dev):
-    coef = torch.empty(2, bn.num_features, dtype=torch.float32, device=dev)
-    ops.bn_eval_coeffs(bn, coef[0], coef[1])
-    return coef
+def _ptr(t):
+    if t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous():
+        raise ValueError("model tensors must be contiguous fp32 CUDA tensors")
+    return t.data_ptr()
+
+
+# The helpers below append every tensor they create to `keep`: the descriptor holds addresses only.
+
+def _lin_bn(lin, bn, dev, keep):
+    """A Linear and the eval-mode BatchNorm1d behind it: the addresses (W, b, scale, shift) and the fold itself, the
+    BatchNorm as per-channel coefficients [2, C] = (scale, shift)."""
+    W, b = _ptr(lin.weight), _ptr(lin.bias)
+    fold = torch.empty(2, bn.num_features, dtype=torch.float32, device=dev)
+    ops.bn_eval_coeffs(bn, fold[0], fold[1])
+    keep.append(fold)
+    return (W, b, fold[0].data_ptr(), fold[1].data_ptr()), fold
+
+
+def _shift(lin, fold, keep):
+    """Bias of a Linear and the folded BatchNorm behind it as one vector: s * b + t (fold None: b; no bias: b = 0)."""
+    b = lin.bias.detach() if lin.bias is not None else torch.zeros(lin.out_features, device=lin.weight.device)
+    t = (fold[0] * b + fold[1]).contiguous() if fold is not None else b.float().contiguous()
+    keep.append(t)
+    return t
+
+
+def _split3(w, row_scale, packed, keep):
+    """Exact 3-way bfloat16 split of a weight [rows, cols] for a bf16x6-emulated kernel, rows scaled first when row_scale
+    is given (a folded BatchNorm).  Addresses of the three planes, or of the one packed image of the skinny kernel."""
+    rows, cols = w.shape
+    scale = row_scale.data_ptr() if row_scale is not None else None
+    if packed:
+        parts = [torch.empty(lib.yolat_split_bf16x3_packed_elems(rows, cols), dtype=torch.bfloat16, device=w.device)]
+        check(lib.yolat_split_bf16x3_packed(_ptr(w), cols, rows, cols, scale, parts[0].data_ptr(), ops._stream()),
+              "yolat_split_bf16x3_packed")
+    else:
+        parts = [torch.empty(rows * cols, dtype=torch.bfloat16, device=w.device) for _ in range(3)]
+        check(lib.yolat_split_bf16x3(_ptr(w), cols, rows, cols, scale, parts[0].data_ptr(), parts[1].data_ptr(),
+                                     parts[2].data_ptr(), ops._stream()), "yolat_split_bf16x3")
+    keep.extend(parts)
+    return [p.data_ptr() for p in parts]
 
 
 _VERSION_OF = operator.attrgetter("_version")
@@ -65,7 +102,7 @@ class EvalPlan(object):
         self._ws = None
         self._status = None
         self._graphs = {}
-        self._need = {}           # (N, E, P, descriptor build) -> workspace bytes of the prepared-graph forward
+        self._need = {}           # (N, E, P, descriptor build) -> workspace bytes
         self._primed = None        # (workspace, descriptor build, N, E, P, stream) of the last completed direct launch
         self._desc_key = 0
         self._loc = {}             # batch version -> (weakrefs, Locality): the locality property, examined once
@@ -78,211 +115,148 @@ class EvalPlan(object):
         self._desc_key += 1
         self._primed = None
         from .engine import model_convs
-        m = self.model
+        m, net = self.model, self.model.cls_net
         dev = self._tensors[0].device
-        net = m.cls_net
         convs = model_convs(net)
         if len(convs) > YOLAT_MAX_LAYERS:
             raise ValueError("n_blocks > %d is not supported by the eval plan" % YOLAT_MAX_LAYERS)
         d = ModelEval()
         keep = []
-
-        def ptr(t):
-            if t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous():
-                raise ValueError("model tensors must be contiguous fp32 CUDA tensors")
-            return t.data_ptr()
-
-        def folded(bn):
-            c = _fold(bn, dev)
-            keep.append(c)
-            return c[0].data_ptr(), c[1].data_ptr()
-
         d.n_blocks, d.n_blocks_out, d.n_classes = net.n_blocks, net.n_blocks_out, m.n_classes
         d.C = convs[0].nn[0].out_features
         d.F = net.fusion_block[0].out_features
-        wuvs, folds1, folds2 = [], [], []
-        for l, cv in enumerate(convs):
-            c = d.conv[l]
-            c.Cin = cv.in_channels
-            c.W1, c.b1 = ptr(cv.nn[0].weight), ptr(cv.nn[0].bias)
-            c.s1, c.t1 = folded(cv.nn[1])
-            folds1.append((keep[-1][0], keep[-1][1]))
-            c.W2, c.b2 = ptr(cv.nn[3].weight), ptr(cv.nn[3].bias)
-            c.s2, c.t2 = folded(cv.nn[4])
-            fold2 = keep[-1]
-            folds2.append(fold2)
-            c.Wr, c.br = ptr(cv.lin_r.weight), ptr(cv.lin_r.bias)
-            c.Wn, c.bn = ptr(cv.mlp_node[0].weight), ptr(cv.mlp_node[0].bias)
-            c.sn, c.tn = folded(cv.mlp_node[1])
-            keep_sn = keep[-1]
-            C = cv.nn[0].out_features
-            # factorised first edge Linear: per-node weights [W1a - W1b | W1b] and the 4 attr columns
-            wuv = torch.empty(2 * C, cv.in_channels, dtype=torch.float32, device=dev)
-            wc4 = torch.empty(C, 4, dtype=torch.float32, device=dev)
-            check(lib.yolat_conv_split_w1(c.W1, cv.in_channels, C, wuv.data_ptr(), wc4.data_ptr(), ops._stream()),
-                  "yolat_conv_split_w1")
-            keep += [wuv, wc4]
-            wuvs.append(wuv)
-            if True:
-                c.Wuv, c.Wc4 = wuv.data_ptr(), wc4.data_ptr()
-                if self.precision == "fp32":
-                    # folded form of the layer (once per weight version; elementwise on [C]-sized tensors): nn.1's
-                    # folded BatchNorm (s1, t1) and the bias b1 move into the per-node products and the attr weights,
-                    # b2 into the shift of nn.4 — the per-edge arithmetic shrinks to
-                    #   h1 = relu(U'[dst] + V'[src] + Wc4f.attr),  message = relu(s2 * (W2.h1) + t2f)
-                    s1, t1 = folds1[l]
-                    wuvf, uvb, wc4f, t2f = ops.fold_factorised_layer(wuv, wc4, cv.nn[0].bias, s1, t1, cv.nn[3].bias,
-                                                                     fold2[0], fold2[1])
-                    keep += [wuvf, uvb, wc4f, t2f]
-                    c.Wuvf, c.uvb, c.Wc4f, c.t2f = wuvf.data_ptr(), uvb.data_ptr(), wc4f.data_ptr(), t2f.data_ptr()
-                    if (l > 0 and cv.in_channels == 64 and C == 64 and cv.lin_r.bias is not None
-                            and os.environ.get("YOLAT_NODE_CHAIN", "1") != "0"):
-                        # the node side of this layer in the form the PREVIOUS layer's edge kernel consumes (small
-                        # graphs: EdgeNext, csrc/common.hpp): [Wuvf ; Wr] in 16x16x4 MFMA B-fragment order, [uvb ; br]
-                        wst = torch.cat([wuvf, cv.lin_r.weight.detach()], 0)                 # [192, 64]
-                        wnx = wst.view(12, 16, 16, 4).permute(0, 2, 3, 1).contiguous()         # [ct, ks, k & 3, row]
-                        tnx = torch.cat([uvb, cv.lin_r.bias.detach()], 0).contiguous()
-                        keep += [wnx, tnx]
-                        c.Wnx, c.tnx = wnx.data_ptr(), tnx.data_ptr()
-                    if (cv.in_channels == 64 and C == 64 and _x6_on()
-                            and cv.lin_r.bias is not None):
-                        # node side on the bf16x6 rows kernel (yolat_node_uv_eval_x6): [Wuvf ; Wr] stacked and split,
-                        # shifts [uvb ; br]; node branch with its BatchNorm scale folded into the weight rows
-                        def split_rows(w, row_scale):
-                            rows, cols = w.shape
-                            parts = [torch.empty(rows * cols, dtype=torch.bfloat16, device=dev) for _ in range(3)]
-                            check(lib.yolat_split_bf16x3(w.data_ptr(), cols, rows, cols,
-                                                         row_scale.data_ptr() if row_scale is not None else None,
-                                                         parts[0].data_ptr(), parts[1].data_ptr(), parts[2].data_ptr(),
-                                                         ops._stream()), "yolat_split_bf16x3")
-                            return parts
-                        wfr = torch.cat([wuvf, cv.lin_r.weight.detach()], 0).contiguous()
-                        tfr = torch.cat([uvb, cv.lin_r.bias.detach()], 0).contiguous()
-                        sn_t, tn_t = keep_sn[0], keep_sn[1]
-                        bn_b = cv.mlp_node[0].bias
-                        bn_b = bn_b.detach() if bn_b is not None else torch.zeros_like(sn_t)
-                        tnf = (sn_t * bn_b + tn_t).contiguous()
-                        pfr, pn = split_rows(wfr, None), split_rows(cv.mlp_node[0].weight.detach().contiguous(), sn_t)
-                        keep += [wfr, tfr, tnf] + pfr + pn
-                        for i in range(3):
-                            c.Wfr_x6[i], c.Wn_x6[i] = pfr[i].data_ptr(), pn[i].data_ptr()
-                        c.tfr, c.tn_fold = tfr.data_ptr(), tnf.data_ptr()
-        fb, fs = net.fusion_block, net.fusion_block_super
-        d.Wf, d.bf = ptr(fb[0].weight), ptr(fb[0].bias)
-        d.sf, d.tf = folded(fb[1])
-        Dk = fb[0].in_features
-        x6 = (self.precision == "fp32" and _x6_on() and Dk in (64, 128)
-              and d.F % 64 == 0)
-
-        def split3(lin, fold):
-            # Linear (+ BatchNorm) for a bf16x6-emulated kernel: BatchNorm scale folded into the weight rows, exact
-            # 3-way bfloat16 split of the result, shift = s*b + t (no BatchNorm: fold is None, shift = b)
-            rows, cols = lin.out_features, lin.in_features
-            parts = [torch.empty(rows * cols, dtype=torch.bfloat16, device=dev) for _ in range(3)]
-            check(lib.yolat_split_bf16x3(ptr(lin.weight), cols, rows, cols, fold[0].data_ptr() if fold is not None else None,
-                                         parts[0].data_ptr(), parts[1].data_ptr(), parts[2].data_ptr(), ops._stream()),
-                  "yolat_split_bf16x3")
-            bias = lin.bias.detach() if lin.bias is not None else torch.zeros(rows, device=dev)
-            tfold = (fold[0] * bias + fold[1]).contiguous() if fold is not None else bias.float().contiguous()
-            keep.extend(parts + [tfold])
-            return parts[0].data_ptr(), parts[1].data_ptr(), parts[2].data_ptr(), tfold.data_ptr()
-
-        if x6:
-            d.Wf_hi, d.Wf_mid, d.Wf_lo, d.tf_fold = split3(fb[0], keep[-1])
-        d.Wfs, d.bfs = ptr(fs[0].weight), ptr(fs[0].bias)
-        d.sfs, d.tfs = folded(fs[1])
-        if x6:
-            d.Wfs_hi, d.Wfs_mid, d.Wfs_lo, d.tfs_fold = split3(fs[0], keep[-1])
-        m1, m2, m3 = m.prediction_cls[0], m.prediction_cls[1], m.prediction_cls[2]
-        d.H1, d.H2 = m1[0].out_features, m2[0].out_features
-        d.Wc1, d.bc1 = ptr(m1[0].weight), ptr(m1[0].bias)
-        d.sc1, d.tc1 = folded(m1[1])
-        c1fold = keep[-1]
-        d.Wc2, d.bc2 = ptr(m2[0].weight), ptr(m2[0].bias)
-        d.sc2, d.tc2 = folded(m2[1])
-        c2fold = keep[-1]
-        d.Wc3, d.bc3 = ptr(m3[0].weight), ptr(m3[0].bias)
-        # prediction_cls.0 (P x 2304 -> 512) on the LDS-tiled bf16x6 GEMM (yolat_gemm_x6)
-        if (self.precision == "fp32" and _x6_on() and m1[0].in_features % 16 == 0):
-            lin = m1[0]
-            rows, cols = lin.out_features, lin.in_features
-            packed = torch.empty(lib.yolat_gemm_x6_packed_elems(rows, cols), dtype=torch.bfloat16, device=dev)
-            check(lib.yolat_gemm_x6_pack(ptr(lin.weight), cols, rows, cols, c1fold[0].data_ptr(), packed.data_ptr(),
-                                         ops._stream()), "yolat_gemm_x6_pack")
-            bias = lin.bias.detach() if lin.bias is not None else torch.zeros(rows, device=dev)
-            tfold = (c1fold[0] * bias + c1fold[1]).contiguous()
-            keep += [packed, tfold]
-            d.Wc1_gx, d.tc1_gx = packed.data_ptr(), tfold.data_ptr()
-        # classifier layers for the skinny bf16x6 kernel (yolat_linear_x6): all three or none.  Off by default: measured
-        # equal to the fp32 split-K kernel at P = 400 (20.8 vs 21.2 us for cls1; operands streamed from L2 straight
-        # into registers make it L1-bandwidth bound, profiles/r02_linear_x6_skinny.txt) and slower beyond.
-        if (self.precision == "fp32" and _x6_on(False)
-                and all(l[0].in_features % 16 == 0 for l in (m1, m2, m3))):
-            for i, (l, fold) in enumerate(((m1, c1fold), (m2, c2fold), (m3, None))):
-                lin = l[0]
-                rows, cols = lin.out_features, lin.in_features
-                packed = torch.empty(lib.yolat_split_bf16x3_packed_elems(rows, cols), dtype=torch.bfloat16, device=dev)
-                check(lib.yolat_split_bf16x3_packed(ptr(lin.weight), cols, rows, cols,
-                                                    fold[0].data_ptr() if fold is not None else None,
-                                                    packed.data_ptr(), ops._stream()), "yolat_split_bf16x3_packed")
-                bias = lin.bias.detach() if lin.bias is not None else torch.zeros(rows, device=dev)
-                tfold = (fold[0] * bias + fold[1]).contiguous() if fold is not None else bias.float().contiguous()
-                keep += [packed, tfold]
-                d.Wc_x6[i], d.tc_fold[i] = packed.data_ptr(), tfold.data_ptr()
+        layers = [self._build_conv(d.conv[l], l, cv, dev, keep) for l, cv in enumerate(convs)]
+        ff, ffs = self._build_head(d, dev, keep)
         self._desc, self._keep = d, keep
         self._desc_h = None
         if self.precision == "bf16":
-            h = ModelEvalBf16()
-            h.base = ctypes.pointer(d)
-
-            def half(t):
-                o = torch.empty(t.numel(), dtype=torch.bfloat16, device=dev)
-                check(lib.yolat_f32_to_bf16(t.data_ptr(), t.numel(), o.data_ptr(), ops._stream()), "yolat_f32_to_bf16")
-                keep.append(o)
-                return o.data_ptr()
-
-            for l, cv in enumerate(convs):
-                # the edge MLP's second BatchNorm: scale folded into W2's rows before the bf16 rounding, shift + bias
-                # as one vector (enters the accumulators through an MFMA, csrc/edge_chain.hip)
-                s2, t2 = folds2[l]
-                h.W2[l] = half((cv.nn[3].weight.detach() * s2[:, None]).contiguous())
-                b2 = cv.nn[3].bias.detach() if cv.nn[3].bias is not None else torch.zeros_like(t2)
-                t2f = (s2 * b2 + t2).contiguous()
-                keep.append(t2f)
-                h.t2f[l] = t2f.data_ptr()
-                # layer 1's folded BatchNorm moves into the node-side epilogue: U' = s1*U + (s1*b1 + t1), V' = s1*V
-                s1, t1 = folds1[l]
-                uvs = torch.cat([s1, s1]).contiguous()
-                uvt = torch.cat([s1 * cv.nn[0].bias.detach() + t1, torch.zeros_like(t1)]).contiguous()
-                keep += [uvs, uvt]
-                h.uv_scale[l], h.uv_shift[l] = uvs.data_ptr(), uvt.data_ptr()
-                if l > 0:
-                    h.Wuv[l], h.Wr[l], h.Wn[l] = half(wuvs[l]), half(cv.lin_r.weight), half(cv.mlp_node[0].weight)
-            h.Wf, h.Wfs = half(fb[0].weight), half(fs[0].weight)
-            # the two fusion blocks with their BatchNorm folded (scale into the rows before the bf16 rounding, shift +
-            # bias as one vector): the A-in-registers rows kernel, csrc/fusion_h8.hip
-            for lin, bn, wname, tname in ((fb[0], fb[1], "Wf_fold", "tf_fold"), (fs[0], fs[1], "Wfs_fold", "tfs_fold")):
-                sc, sh = _fold(bn, dev)
-                bias = lin.bias.detach() if lin.bias is not None else torch.zeros_like(sh)
-                tfold = (sc * bias + sh).contiguous()
-                keep.append(tfold)
-                setattr(h, wname, half((lin.weight.detach() * sc[:, None]).contiguous()))
-                setattr(h, tname, tfold.data_ptr())
-            h.Wc1, h.Wc2, h.Wc3 = half(m1[0].weight), half(m2[0].weight), half(m3[0].weight)
-            # the conv stack's weights in the fragment order of the one-launch proposal-local kernel (csrc/conv_local.hip);
-            # models outside its shapes (C != 64, in_channels > 8) keep the per-layer launches
-            if CONV_LOCAL:
-                nbytes = int(lib.yolat_conv_local_pack_bytes(d.n_blocks))
-                pack = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-                rc = lib.yolat_conv_local_pack(ctypes.byref(h), pack.data_ptr(), nbytes, ops._stream())
-                if rc == 0:
-                    keep.append(pack)
-                    h.conv_local = pack.data_ptr()
-                elif rc != -2:        # YOLAT_E_UNSUPPORTED: shapes the kernel is not written for
-                    check(rc, "yolat_conv_local_pack")
-            self._desc_h = h
+            self._desc_h = self._build_bf16(d, convs, layers, ff, ffs, dev, keep)
         if self._status is None:
             self._status = torch.zeros(1, dtype=torch.int32, device=dev)
+
+    def _build_conv(self, c, l, cv, dev, keep):
+        """Entry `c` of conv layer l.  Returns (Wuv, fold of nn.1, fold of nn.4): what the bf16 descriptor starts from."""
+        C, cin = cv.nn[0].out_features, cv.in_channels
+        c.Cin = cin
+        (c.W1, c.b1, c.s1, c.t1), f1 = _lin_bn(cv.nn[0], cv.nn[1], dev, keep)
+        (c.W2, c.b2, c.s2, c.t2), f2 = _lin_bn(cv.nn[3], cv.nn[4], dev, keep)
+        c.Wr, c.br = _ptr(cv.lin_r.weight), _ptr(cv.lin_r.bias)
+        (c.Wn, c.bn, c.sn, c.tn), fn = _lin_bn(cv.mlp_node[0], cv.mlp_node[1], dev, keep)
+        # factorised first edge Linear: per-node weights [W1a - W1b | W1b] and the 4 attr columns
+        wuv, wc4 = ops.split_w1(cv.nn[0].weight, cin)
+        keep += [wuv, wc4]
+        c.Wuv, c.Wc4 = wuv.data_ptr(), wc4.data_ptr()
+        if self.precision != "fp32":
+            return wuv, f1, f2
+        # folded form of the layer (once per weight version; elementwise on [C]-sized tensors): nn.1's folded BatchNorm
+        # (s1, t1) and the bias b1 move into the per-node products and the attr weights, b2 into the shift of nn.4 — the
+        # per-edge arithmetic shrinks to
+        #   h1 = relu(U'[dst] + V'[src] + Wc4f.attr),  message = relu(s2 * (W2.h1) + t2f)
+        wuvf, uvb, wc4f, t2f = ops.fold_factorised_layer(wuv, wc4, cv.nn[0].bias, f1[0], f1[1], cv.nn[3].bias, f2[0], f2[1])
+        keep += [wuvf, uvb, wc4f, t2f]
+        c.Wuvf, c.uvb, c.Wc4f, c.t2f = wuvf.data_ptr(), uvb.data_ptr(), wc4f.data_ptr(), t2f.data_ptr()
+        stacked = cin == 64 and C == 64 and cv.lin_r.bias is not None
+        chain = l > 0 and stacked and os.environ.get("YOLAT_NODE_CHAIN", "1") != "0"
+        rows_x6 = stacked and _x6_on()
+        if chain or rows_x6:
+            # the node side as one product: [Wuvf ; Wr] stacked, shifts [uvb ; br]
+            wfr = torch.cat([wuvf, cv.lin_r.weight.detach()], 0)                           # [192, 64]
+            tfr = torch.cat([uvb, cv.lin_r.bias.detach()], 0)
+            keep += [wfr, tfr]
+        if chain:
+            # ... in the form the PREVIOUS layer's edge kernel consumes (small graphs: EdgeNext, csrc/common.hpp):
+            # the weight in 16x16x4 MFMA B-fragment order
+            wnx = wfr.view(12, 16, 16, 4).permute(0, 2, 3, 1).contiguous()                 # [ct, ks, k & 3, row]
+            keep.append(wnx)
+            c.Wnx, c.tnx = wnx.data_ptr(), tfr.data_ptr()
+        if rows_x6:
+            # ... on the bf16x6 rows kernel (yolat_node_uv_eval_x6): the weight split; the node branch with its BatchNorm
+            # scale folded into the weight rows
+            c.Wfr_x6[0], c.Wfr_x6[1], c.Wfr_x6[2] = _split3(wfr, None, False, keep)
+            c.Wn_x6[0], c.Wn_x6[1], c.Wn_x6[2] = _split3(cv.mlp_node[0].weight, fn[0], False, keep)
+            c.tfr, c.tn_fold = tfr.data_ptr(), _shift(cv.mlp_node[0], fn, keep).data_ptr()
+        return wuv, f1, f2
+
+    def _build_head(self, d, dev, keep):
+        """The two fusion blocks and the classifier.  Returns the folds of the two fusion BatchNorms."""
+        m, net = self.model, self.model.cls_net
+        fp32 = self.precision == "fp32"
+        fb, fs = net.fusion_block, net.fusion_block_super
+        (d.Wf, d.bf, d.sf, d.tf), ff = _lin_bn(fb[0], fb[1], dev, keep)
+        (d.Wfs, d.bfs, d.sfs, d.tfs), ffs = _lin_bn(fs[0], fs[1], dev, keep)
+        # Linear + BatchNorm for the bf16x6-emulated fusion kernel: BatchNorm scale folded into the weight rows, exact 3-way
+        # bfloat16 split of the result, shift = s*b + t
+        if fp32 and _x6_on() and fb[0].in_features in (64, 128) and d.F % 64 == 0:
+            d.Wf_hi, d.Wf_mid, d.Wf_lo = _split3(fb[0].weight, ff[0], False, keep)
+            d.tf_fold = _shift(fb[0], ff, keep).data_ptr()
+            d.Wfs_hi, d.Wfs_mid, d.Wfs_lo = _split3(fs[0].weight, ffs[0], False, keep)
+            d.tfs_fold = _shift(fs[0], ffs, keep).data_ptr()
+        m1, m2, m3 = m.prediction_cls[0], m.prediction_cls[1], m.prediction_cls[2]
+        d.H1, d.H2 = m1[0].out_features, m2[0].out_features
+        (d.Wc1, d.bc1, d.sc1, d.tc1), fc1 = _lin_bn(m1[0], m1[1], dev, keep)
+        (d.Wc2, d.bc2, d.sc2, d.tc2), fc2 = _lin_bn(m2[0], m2[1], dev, keep)
+        d.Wc3, d.bc3 = _ptr(m3[0].weight), _ptr(m3[0].bias)
+        # prediction_cls.0 (P x 2304 -> 512) on the LDS-tiled bf16x6 GEMM (yolat_gemm_x6)
+        if fp32 and _x6_on() and m1[0].in_features % 16 == 0:
+            rows, cols = m1[0].out_features, m1[0].in_features
+            packed = torch.empty(lib.yolat_gemm_x6_packed_elems(rows, cols), dtype=torch.bfloat16, device=dev)
+            check(lib.yolat_gemm_x6_pack(_ptr(m1[0].weight), cols, rows, cols, fc1[0].data_ptr(), packed.data_ptr(),
+                                         ops._stream()), "yolat_gemm_x6_pack")
+            keep.append(packed)
+            d.Wc1_gx, d.tc1_gx = packed.data_ptr(), _shift(m1[0], fc1, keep).data_ptr()
+        # classifier layers for the skinny bf16x6 kernel (yolat_linear_x6): all three or none.  Off by default: measured
+        # equal to the fp32 split-K kernel at P = 400 (20.8 vs 21.2 us for cls1; operands streamed from L2 straight
+        # into registers make it L1-bandwidth bound, profiles/r02_linear_x6_skinny.txt) and slower beyond.
+        if fp32 and _x6_on(False) and all(l[0].in_features % 16 == 0 for l in (m1, m2, m3)):
+            for i, (lin, fold) in enumerate(((m1[0], fc1), (m2[0], fc2), (m3[0], None))):
+                d.Wc_x6[i] = _split3(lin.weight, fold[0] if fold is not None else None, True, keep)[0]
+                d.tc_fold[i] = _shift(lin, fold, keep).data_ptr()
+        return ff, ffs
+
+    def _build_bf16(self, d, convs, layers, ff, ffs, dev, keep):
+        """The bf16-storage descriptor on top of `d`, from the folds computed for it (layers: _build_conv's results)."""
+        m, net = self.model, self.model.cls_net
+        h = ModelEvalBf16()
+        h.base = ctypes.pointer(d)
+
+        def half(t):
+            o = torch.empty(t.numel(), dtype=torch.bfloat16, device=dev)
+            check(lib.yolat_f32_to_bf16(t.data_ptr(), t.numel(), o.data_ptr(), ops._stream()), "yolat_f32_to_bf16")
+            keep.append(o)
+            return o.data_ptr()
+
+        def half_folded(lin, fold):
+            # BatchNorm scale folded into the weight rows before the bf16 rounding; its shift + the bias go as one vector
+            return half((lin.weight.detach() * fold[0][:, None]).contiguous()), _shift(lin, fold, keep).data_ptr()
+
+        for l, (cv, (wuv, f1, f2)) in enumerate(zip(convs, layers)):
+            # the edge MLP's second BatchNorm (the vector enters the accumulators through an MFMA, csrc/edge_chain.hip)
+            h.W2[l], h.t2f[l] = half_folded(cv.nn[3], f2)
+            # layer 1's folded BatchNorm moves into the node-side epilogue: U' = s1*U + (s1*b1 + t1), V' = s1*V
+            uvs = torch.cat([f1[0], f1[0]]).contiguous()
+            uvt = torch.cat([_shift(cv.nn[0], f1, keep), torch.zeros_like(f1[1])]).contiguous()
+            keep += [uvs, uvt]
+            h.uv_scale[l], h.uv_shift[l] = uvs.data_ptr(), uvt.data_ptr()
+            if l > 0:
+                h.Wuv[l], h.Wr[l], h.Wn[l] = half(wuv), half(cv.lin_r.weight), half(cv.mlp_node[0].weight)
+        fb, fs = net.fusion_block, net.fusion_block_super
+        h.Wf, h.Wfs = half(fb[0].weight), half(fs[0].weight)
+        # the two fusion blocks with their BatchNorm folded: the A-in-registers rows kernel, csrc/fusion_h8.hip
+        h.Wf_fold, h.tf_fold = half_folded(fb[0], ff)
+        h.Wfs_fold, h.tfs_fold = half_folded(fs[0], ffs)
+        h.Wc1, h.Wc2, h.Wc3 = (half(m.prediction_cls[i][0].weight) for i in range(3))
+        # the conv stack's weights in the fragment order of the one-launch proposal-local kernel (csrc/conv_local.hip);
+        # models outside its shapes (C != 64, in_channels > 8) keep the per-layer launches
+        if CONV_LOCAL:
+            nbytes = int(lib.yolat_conv_local_pack_bytes(d.n_blocks))
+            pack = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            rc = lib.yolat_conv_local_pack(ctypes.byref(h), pack.data_ptr(), nbytes, ops._stream())
+            if rc == 0:
+                keep.append(pack)
+                h.conv_local = pack.data_ptr()
+            elif rc != -2:        # YOLAT_E_UNSUPPORTED: shapes the kernel is not written for
+                check(rc, "yolat_conv_local_pack")
+        return h
 
     def _local_candidate(self, P):
         """would yolat_forward_eval_bf16 consider the one-launch conv stack for a batch of P proposals?  (the model's
@@ -321,45 +295,15 @@ class EvalPlan(object):
         self._loc[key] = (weakref.ref(edge), weakref.ref(bbox_idx), loc)
         return loc
 
-    def run(self, x, edge, e_attr, bbox_idx, num_proposals, loc=None):
-        """loc: the batch's locality record when the caller has it (decided on the host by the collate); None: the plan
-        examines a resident batch itself, once per batch version (`locality`)"""
+    def _prepare(self, N, E, P):
+        """The common opening of every forward: the descriptor of the current weight version and a workspace (grow-only)
+        large enough for the shape.  A rebuild or a new workspace drops the captured graphs."""
         key = self._version_key()
         if key != self._key:
             self._build()
             self._key = key
             self._graphs.clear()
-        N, P = x.shape[0], int(num_proposals)
-        if edge.dim() != 2 or (edge.shape[1] != 2 and edge.shape[0] != 2):
-            raise ValueError("edge must be [E,2] or [2,E]")
-        if edge.shape[1] == 2 and not (edge.shape[0] == 2 and edge.stride(0) == 1):
-            E, se, sc = edge.shape[0], edge.stride(0), edge.stride(1)
-        else:
-            E, se, sc = edge.shape[1], edge.stride(1), edge.stride(0)
-        if self._desc_h is not None:
-            need = int(lib.yolat_forward_eval_bf16_workspace_bytes(ctypes.byref(self._desc_h), N, E, P))
-        else:
-            need = int(lib.yolat_forward_eval_workspace_bytes(ctypes.byref(self._desc), N, E, P))
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = torch.empty(int(need * 1.25) + 4096, dtype=torch.uint8, device=x.device)
-            self._graphs.clear()
-        if self.use_graph:
-            out = self._run_graph(x, edge, e_attr, bbox_idx, N, E, P, se, sc)
-            if out is not None:
-                return out
-        return self._launch(x, edge, e_attr, bbox_idx, N, E, P, se, sc, loc)
-
-    def run_raw(self, raw, loc=None):
-        """The forward on a DeviceLoader batch in COO mode, described by addresses instead of tensor views:
-        raw = (x, ldx, edge, stride_e, stride_c, e_attr, bbox_idx, N, E, P, device) — every tensor view costs this thread
-        what a launch costs, and the hand-over is bound by exactly that (data.DeviceLoader)."""
-        key = self._version_key()
-        if key != self._key:
-            self._build()
-            self._key = key
-            self._graphs.clear()
-        xp, ldx, ep, se, sc, ap, bp, N, E, P, dev = raw
-        nk = ("raw", N, E, P, self._desc_key)
+        nk = (N, E, P, self._desc_key)
         need = self._need.get(nk)
         if need is None:
             if self._desc_h is not None:
@@ -372,61 +316,38 @@ class EvalPlan(object):
         if self._ws is None or self._ws.numel() < need:
             self._ws = torch.empty(int(need * 1.25) + 4096, dtype=torch.uint8, device=self._tensors[0].device)
             self._graphs.clear()
-        logits = torch.empty(P, self._desc.n_classes, dtype=torch.float32, device=dev)
-        stream = ops._stream()
-        bf16 = self._desc_h is not None
-        pk = (self._ws.data_ptr(), self._desc_key, N, E, P, stream, "bf16") if bf16 else (self._ws.data_ptr(), self._desc_key, N, E, P, stream)
-        primed = PRIMED_WS and self._primed == pk
-        self._primed = None
-        if bf16:
-            vouched = self._vouched(loc, P)
-            primed = primed and not vouched
-            rc = lib.yolat_forward_eval_bf16_loc(ctypes.byref(self._desc_h), xp, ldx, ep, se, sc, ap, bp, None, N, E, P,
-                                                 logits.data_ptr(), logits.stride(0), self._ws.data_ptr(), self._ws.numel(),
-                                                 self._status.data_ptr(), ctypes.byref(loc) if loc is not None else None,
-                                                 1 if primed else 0, stream)
-            if vouched:
-                pk = None
-        else:
-            fn = lib.yolat_forward_eval_primed if primed else lib.yolat_forward_eval
-            rc = fn(ctypes.byref(self._desc), xp, ldx, ep, se, sc, ap, bp, N, E, P, logits.data_ptr(), logits.stride(0),
-                    self._ws.data_ptr(), self._ws.numel(), self._status.data_ptr(), stream)
-        if rc != 0:
-            check(rc, "yolat_forward_eval")
-        self._primed = pk
-        return logits
+
+    def run(self, x, edge, e_attr, bbox_idx, num_proposals, loc=None):
+        """loc: the batch's locality record when the caller has it (decided on the host by the collate); None: the plan
+        examines a resident batch itself, once per batch version (`locality`)"""
+        N, P = x.shape[0], int(num_proposals)
+        E, se, sc = ops.edge_layout(edge)
+        self._prepare(N, E, P)
+        if self.use_graph:
+            out = self._run_graph(x, edge, e_attr, bbox_idx, N, E, P, se, sc)
+            if out is not None:
+                return out
+        return self._launch(x, edge, e_attr, bbox_idx, N, E, P, se, sc, loc)
+
+    def run_raw(self, raw, loc=None):
+        """The forward on a DeviceLoader batch in COO mode, described by addresses instead of tensor views:
+        raw = (x, ldx, edge, stride_e, stride_c, e_attr, bbox_idx, N, E, P, device) — every tensor view costs this thread
+        what a launch costs, and the hand-over is bound by exactly that (data.DeviceLoader)."""
+        xp, ldx, ep, se, sc, ap, bp, N, E, P, dev = raw
+        self._prepare(N, E, P)
+        return self._launch_coo(xp, ldx, ep, se, sc, ap, bp, N, E, P, dev, loc, False)
 
     def run_prepared(self, x, g, xref=None, loc=None):
-        """The forward on a prepared device graph (ops.Graph; yolat_forward_eval_csr / _bf16_csr): no COO -> CSR
+        """The forward on a prepared device graph (ops.Graph; yolat_forward_eval_csr / _bf16_loc): no COO -> CSR
         conversion inside the call.  (hipGraph replay of this path was measured and dropped twice: batches arrive in fresh
         allocations, so captured graphs rarely match — 4.3 k vs 6.2 k graphs/s H2D-inclusive at cfg 2, round 3; keyed by the
         fixed slot addresses of a data.DeviceLoader ring they do match, and replay + the copy out of the static output
-        still lose to seven direct launches — 7.3 k vs 7.9 k graphs/s, round 5.)"""
-        key = self._version_key()
-        if key != self._key:
-            self._build()
-            self._key = key
-            self._graphs.clear()
-        N, E, P = g.N, g.E, g.P
-        need = self._need.get((N, E, P, self._desc_key))
-        if need is None:
-            if self._desc_h is not None:
-                need = int(lib.yolat_forward_eval_bf16_workspace_bytes(ctypes.byref(self._desc_h), N, E, P))
-            else:
-                need = int(lib.yolat_forward_eval_workspace_bytes(ctypes.byref(self._desc), N, E, P))
-            if len(self._need) > 64:
-                self._need.clear()
-            self._need[(N, E, P, self._desc_key)] = need
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = torch.empty(int(need * 1.25) + 4096, dtype=torch.uint8, device=self._tensors[0].device)
-            self._graphs.clear()
-        self._primed = None
-        return self._launch_prepared(x, g, xref, loc)
-
-    def _launch_prepared(self, x, g, xref=None, loc=None):
-        """xref = (address, row stride, rows, device) of a dense fp32 x that exists only as a range of a loader slot
+        still lose to seven direct launches — 7.3 k vs 7.9 k graphs/s, round 5.)
+        xref = (address, row stride, rows, device) of a dense fp32 x that exists only as a range of a loader slot
         (data.DeviceLoader): the hand-over is bound by this thread's Python, a tensor view costs what a launch costs"""
         N, E, P = g.N, g.E, g.P
+        self._prepare(N, E, P)
+        self._primed = None
         gc = GraphCsr(*g.device_pointers())
         if xref is not None:
             xp, ldx, rows, dev = xref
@@ -442,7 +363,7 @@ class EvalPlan(object):
                                                  self._status.data_ptr(), ctypes.byref(loc) if loc is not None else None, 0,
                                                  ops._stream())
             if rc != 0:
-                check(rc, "yolat_forward_eval_bf16_csr")
+                check(rc, "yolat_forward_eval_bf16_loc")
         else:
             rc = lib.yolat_forward_eval_csr(ctypes.byref(self._desc), xp, ldx, ctypes.byref(gc), N, E, P,
                                             logits.data_ptr(), logits.stride(0), ws.data_ptr(), ws.numel(), ops._stream())
@@ -451,42 +372,39 @@ class EvalPlan(object):
         return logits
 
     def _launch(self, x, edge, e_attr, bbox_idx, N, E, P, se, sc, loc=None):
-        logits = torch.empty(P, self._desc.n_classes, dtype=torch.float32, device=x.device)
-        if self._desc_h is not None:
-            stream = ops._stream()
-            capturing = torch.cuda.is_current_stream_capturing()
-            key = (self._ws.data_ptr(), self._desc_key, N, E, P, stream, "bf16")
-            if loc is None and not capturing:
-                loc = self.locality(edge, bbox_idx, N, E, P, se, sc)
-            vouched = self._vouched(loc, P)
-            # (a vouched forward does not touch the CSR-build counters: it neither needs nor keeps the `primed` promise)
-            primed = PRIMED_WS and not capturing and not vouched and self._primed == key
-            self._primed = None
-            check(lib.yolat_forward_eval_bf16_loc(ctypes.byref(self._desc_h), ops._f(x, "x"), ops._ld(x),
-                                                  ops._i(edge, torch.int64, "edge"), se, sc, ops._f(e_attr, "e_attr"),
-                                                  ops._i(bbox_idx, torch.int64, "bbox_idx"), None, N, E, P,
-                                                  logits.data_ptr(), logits.stride(0), self._ws.data_ptr(),
-                                                  self._ws.numel(), self._status.data_ptr(),
-                                                  ctypes.byref(loc) if loc is not None else None, 1 if primed else 0,
-                                                  stream), "yolat_forward_eval_bf16")
-            if not capturing and not vouched:
-                self._primed = key
-            return logits
-        # the workspace is this plan's own: when its previous use was a forward of the same shape on the same stream,
-        # the CSR-build counters are already zero (yolat_forward_eval_primed: no memset launch).  A hipGraph capture
-        # always records the self-contained form (a replay may follow a forward of any other shape).
-        stream = ops._stream()
         capturing = torch.cuda.is_current_stream_capturing()
-        key = (self._ws.data_ptr(), self._desc_key, N, E, P, stream)
-        primed = PRIMED_WS and not capturing and self._primed == key
+        if loc is None and not capturing and self._desc_h is not None:
+            loc = self.locality(edge, bbox_idx, N, E, P, se, sc)
+        return self._launch_coo(ops._f(x, "x"), ops._ld(x), ops._i(edge, torch.int64, "edge"), se, sc,
+                                ops._f(e_attr, "e_attr"), ops._i(bbox_idx, torch.int64, "bbox_idx"), N, E, P, x.device, loc,
+                                capturing)
+
+    def _launch_coo(self, xp, ldx, ep, se, sc, ap, bp, N, E, P, dev, loc, capturing):
+        """The forward on a COO batch given by addresses.  The workspace is this plan's own: when its previous use was a
+        forward of the same shape on the same stream, the CSR-build counters are already zero (the `primed` forms: no
+        memset launch).  A hipGraph capture always records the self-contained form (a replay may follow a forward of any
+        other shape), and a vouched bf16 forward does not touch the counters: neither uses nor keeps the promise."""
+        logits = torch.empty(P, self._desc.n_classes, dtype=torch.float32, device=dev)
+        stream = ops._stream()
+        ws, h = self._ws, self._desc_h
+        key = (ws.data_ptr(), self._desc_key, N, E, P, stream)
+        keeps = not capturing and not (h is not None and self._vouched(loc, P))
+        primed = PRIMED_WS and keeps and self._primed == key
         self._primed = None
-        fn = lib.yolat_forward_eval_primed if primed else lib.yolat_forward_eval
-        check(fn(ctypes.byref(self._desc), ops._f(x, "x"), ops._ld(x),
-                 ops._i(edge, torch.int64, "edge"), se, sc, ops._f(e_attr, "e_attr"),
-                 ops._i(bbox_idx, torch.int64, "bbox_idx"), N, E, P, logits.data_ptr(),
-                 logits.stride(0), self._ws.data_ptr(), self._ws.numel(),
-                 self._status.data_ptr(), stream), "yolat_forward_eval")
-        if not capturing:
+        if h is not None:
+            what = "yolat_forward_eval_bf16_loc"
+            rc = lib.yolat_forward_eval_bf16_loc(ctypes.byref(h), xp, ldx, ep, se, sc, ap, bp, None, N, E, P,
+                                                 logits.data_ptr(), logits.stride(0), ws.data_ptr(), ws.numel(),
+                                                 self._status.data_ptr(), ctypes.byref(loc) if loc is not None else None,
+                                                 1 if primed else 0, stream)
+        else:
+            what = "yolat_forward_eval"
+            fn = lib.yolat_forward_eval_primed if primed else lib.yolat_forward_eval
+            rc = fn(ctypes.byref(self._desc), xp, ldx, ep, se, sc, ap, bp, N, E, P, logits.data_ptr(), logits.stride(0),
+                    ws.data_ptr(), ws.numel(), self._status.data_ptr(), stream)
+        if rc != 0:
+            check(rc, what)
+        if keeps:
             self._primed = key
         return logits
 

@@ -394,12 +394,7 @@ class TrainPlan(object):
         else:
             st = model._stage_tensors(data)
             x, edge = st["x"], st["edge"]
-            if edge.dim() != 2 or (edge.shape[1] != 2 and edge.shape[0] != 2):
-                raise ValueError("edge must be [E,2] or [2,E]")
-            if edge.shape[1] == 2 and not (edge.shape[0] == 2 and edge.stride(0) == 1):
-                E, se, sc = edge.shape[0], edge.stride(0), edge.stride(1)
-            else:
-                E, se, sc = edge.shape[1], edge.stride(1), edge.stride(0)
+            E, se, sc = ops.edge_layout(edge)
             e_attr = st["e_attr"] if st["e_attr"].is_contiguous() else st["e_attr"].contiguous()
             ops_in = (x, edge, se, sc, e_attr, st["bbox_idx"], None, x.shape[0], E, st["bbox"].shape[0])
         labels = data.labels
