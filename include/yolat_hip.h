@@ -781,7 +781,12 @@ int yolat_forward_eval_bf16_csr(const yolat_model_eval_bf16* m, const float* x, 
  *     gradient of the parameters BEHIND the conv layers (the "head" bucket of the data-parallel exchange) is final on
  *     `stream`; 2 = backward of the conv layers (all gradients final on `stream`); 4 = Adam (yolat_adam_args).  A caller that
  *     exchanges gradients issues its collectives between the calls; 7 = the whole step.  The workspace
- *     (yolat_train_step_workspace_bytes, 256-byte aligned) carries the step's state between the calls.                  */
+ *     (yolat_train_step_workspace_bytes, 256-byte aligned) carries the step's state between the calls.
+ *   Errors: YOLAT_E_UNSUPPORTED is decided in front of the first launch — nothing was enqueued, the caller may run its own
+ *     schedule on the same state.  Any later failure (YOLAT_E_INVALID, or a hipError_t) leaves part of the step enqueued
+ *     with `side_stream` joined back to `stream`; an entry point that declines its operands in mid-schedule is reported as
+ *     YOLAT_E_INVALID, never as UNSUPPORTED.  The extents are the caller's to guarantee: e_attr [E, 4], x [N, conv[0].Cin],
+ *     bbox_idx [N], labels [P] are read from raw pointers.                                                              */
 typedef struct yolat_train_lin { const float* W; const float* b; } yolat_train_lin;
 typedef struct yolat_train_bn {
   const float* gamma; const float* beta; float* running_mean; float* running_var; int64_t* num_batches_tracked;

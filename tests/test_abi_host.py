@@ -491,3 +491,51 @@ def test_edge_layout():
                 torch.zeros(5, 2, 1, dtype=torch.int64)):
         with pytest.raises(ValueError):
             ops.edge_layout(bad)
+
+
+# ---------------------------------------------------------------------------------------------
+# host checks in front of the training step (trainer.check_batch_shapes, ops.check_status_word)
+# ---------------------------------------------------------------------------------------------
+def _short(t):
+    return t[:-1].clone()
+
+
+@pytest.mark.parametrize("name,edit", [
+    ("^e_attr must", lambda d: setattr(d, "e_attr", d.e_attr[:, :3].contiguous())),                  # [E,3]
+    ("^x must", lambda d: setattr(d, "x", torch.cat([d.x, d.x[:, :1]], 1))),                         # one column too wide
+    ("^bbox_idx must", lambda d: setattr(d, "bbox_idx", _short(d.bbox_idx))),                        # one element short
+    ("^labels must", lambda d: setattr(d, "labels", _short(d.labels))),                              # one element short
+])
+def test_trainer_step_refuses_a_malformed_batch_by_shape(name, edit):
+    """Trainer.step checks the batch's shapes on the host in front of either schedule (the one-call step hands raw pointers
+    to C): ValueError naming the tensor, before anything touches a device — the batch and the model are on the CPU here."""
+    opt = yv.Opt(n_classes=17)
+    tr = yv.Trainer(yv.SparseCADGCN(opt), opt)
+    d, sl = yv.synth_batch(1, 5, num_proposals=12, nodes_lo=4, nodes_hi=9, edges_per_proposal=20)
+    edit(d)
+    with pytest.raises(ValueError, match=name):
+        tr.step(d, sl)
+    assert tr.plan_steps == 0 and tr.optimizer.step_count == 0
+
+
+def test_batch_shape_check_passes_a_well_formed_batch():
+    from yolat_vectorgraphicsrecognition_amd import trainer
+    model = yv.SparseCADGCN(yv.Opt(n_classes=17))
+    d, _ = yv.synth_batch(2, 5, num_proposals=12, nodes_lo=4, nodes_hi=9, edges_per_proposal=20)
+    assert trainer.check_batch_shapes(model, d) is None
+    d.edge = d.edge.t()                                       # the [2,E] view of the same list
+    assert trainer.check_batch_shapes(model, d) is None
+
+
+def test_check_status_word_maps_each_flag_to_its_exception():
+    from yolat_vectorgraphicsrecognition_amd import ops
+    word = lambda v: torch.tensor([v], dtype=torch.int32)
+    assert ops.check_status_word(word(0)) is True
+    for flag, exc, text in ((ops.STATUS_EDGE_RANGE, IndexError, "edge_index"), (ops.STATUS_SEG_UNSORTED, ValueError, "non-decreasing"),
+                            (ops.STATUS_SEG_RANGE, IndexError, "proposal id"), (ops.STATUS_NOT_LOCAL, ValueError, "proposal-local")):
+        with pytest.raises(exc, match=text):
+            ops.check_status_word(word(flag))
+    g = ops.Graph()
+    g.status = word(ops.STATUS_SEG_UNSORTED)
+    with pytest.raises(ValueError, match="non-decreasing"):
+        g.check_status()

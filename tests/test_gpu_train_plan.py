@@ -105,6 +105,35 @@ def test_plan_step_one_stream_and_prepared_graph_batches():
     _run(yv, ta, tb, [yv.collate_to_device(items, csr=True), yv.collate_to_device(items[:2])], steps=3)
 
 
+def test_plan_step_on_ten_streams_walks_the_event_table_past_eight_pairs():
+    """yolat_train_step keeps the fork / join events of every (stream, side stream) pair it has seen in a table that grows:
+    ten distinct current streams, one plan step and one Python-schedule step on each, state bit-identical after every
+    step (the ninth and tenth pair must not take a live pair's events)."""
+    yv = _yv()
+    from yolat_vectorgraphicsrecognition_amd import trainer as T
+    ta, tb = _pair(yv, dict(n_classes=17), 13)
+    streams = [torch.cuda.Stream() for _ in range(10)]
+    assert len({s.cuda_stream for s in streams}) == 10
+    for i, s in enumerate(streams):
+        d, sl = yv.synth_batch(1, 60 + i, num_proposals=40, nodes_lo=5, nodes_hi=12, edges_per_proposal=30)
+        for k in ("x", "edge", "e_attr", "bbox_idx", "bbox", "labels"):
+            d[k] = d[k].cuda()
+        torch.cuda.synchronize()
+        with torch.cuda.stream(s):
+            la = ta.step(d, sl)
+            torch.cuda.synchronize()
+            T.TRAIN_PLAN = False
+            try:
+                lb = tb.step(d, sl)
+            finally:
+                T.TRAIN_PLAN = True
+            torch.cuda.synchronize()
+        assert torch.equal(la, lb), "loss on stream %d" % i
+        _same(_state(ta), _state(tb), "stream %d" % i)
+        torch.cuda.synchronize()
+    assert ta.plan_steps == 10 and tb.plan_steps == 0
+
+
 def test_plan_declines_what_it_does_not_cover_and_the_python_schedule_takes_the_step():
     yv = _yv()
     from yolat_vectorgraphicsrecognition_amd import engine

@@ -105,6 +105,22 @@ def _ld(t):
 _ZERO_STATUS = {}
 
 
+def check_status_word(status):
+    """Synchronising read of an input-validity word (one int32 the pre-processing kernels OR their STATUS_* flags into):
+    raises what the reference raises on such a batch, returns True on zero."""
+    s = int(status.item())
+    if s & STATUS_EDGE_RANGE:
+        raise IndexError("edge_index contains a node id outside [0, N)")
+    if s & STATUS_SEG_UNSORTED:
+        raise ValueError("bbox_idx is not non-decreasing")
+    if s & STATUS_SEG_RANGE:
+        raise IndexError("bbox_idx contains a proposal id outside [0, P)")
+    if s & STATUS_NOT_LOCAL:
+        raise ValueError("a batch handed over as proposal-local (yolat_locality) is not: an edge leaves its proposal, "
+                         "the edge list is not grouped by proposal, or a proposal does not fit a tile")
+    return True
+
+
 class Graph(object):
     """Device-resident integer structure of one batch (CSR by destination, optional CSC by source,
     proposal segments).  Owned by the caller / cached on the batch object."""
@@ -156,17 +172,7 @@ class Graph(object):
 
     def check_status(self):
         """Synchronising validity check of the flags raised by the pre-processing kernels."""
-        s = int(self.status.item())
-        if s & STATUS_EDGE_RANGE:
-            raise IndexError("edge_index contains a node id outside [0, N)")
-        if s & STATUS_SEG_UNSORTED:
-            raise ValueError("bbox_idx is not non-decreasing")
-        if s & STATUS_SEG_RANGE:
-            raise IndexError("bbox_idx contains a proposal id outside [0, P)")
-        if s & STATUS_NOT_LOCAL:
-            raise ValueError("a batch handed over as proposal-local (yolat_locality) is not: an edge leaves its proposal, "
-                             "the edge list is not grouped by proposal, or a proposal does not fit a tile")
-        return True
+        return check_status_word(self.status)
 
 
 class PackedGraph(Graph):

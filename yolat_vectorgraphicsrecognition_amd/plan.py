@@ -442,10 +442,8 @@ class EvalPlan(object):
         """Raises on the input-validity flags of the forwards since the last check.  The word belongs to the plan and the
         kernels only ever OR into it: a raised condition is cleared here, so one malformed batch does not condemn every later
         forward of the model."""
-        g = ops.Graph()
-        g.status = self._status
         try:
-            return ops.Graph.check_status(g)
+            return ops.check_status_word(self._status)
         except (IndexError, ValueError):
             self._status.zero_()
             raise

@@ -13,6 +13,7 @@ Data parallelism shards whole graphs (dataset items) across ranks; there are no 
 (Datasets/graph_dict3.py:594-600), BatchNorm statistics stay per replica (the reference has no
 SyncBN), parameters and optimizer state are replicated.
 """
+import collections
 import os
 
 import torch
@@ -267,6 +268,35 @@ def allreduce_mean_(flat_grad):
 TRAIN_PLAN = True
 
 
+# device operands of one step as TrainPlan.stage hands them to TrainPlan.run: the collated COO arrays (graph None) or a
+# prepared graph (edge / e_attr / bbox_idx None, strides 0)
+Staged = collections.namedtuple("Staged", "x edge stride_e stride_c e_attr bbox_idx graph N E P labels")
+
+
+def check_batch_shapes(model, data):
+    """Host-only check (shapes, no synchronisation) of what either schedule assumes about a training batch: the one-call
+    step hands raw pointers to C, so a malformed batch must stop here.  Raises ValueError naming the tensor."""
+    from . import engine
+    cin = engine.model_convs(model.cls_net)[0].in_channels
+    g = data.__dict__.get("_yolat_graph") if hasattr(data, "__dict__") else None
+    x, labels = data.x, data.labels
+    if x.dim() != 2 or x.shape[1] != cin:
+        raise ValueError("x must be [N, %d] (in_channels of the first conv layer), got %s" % (cin, tuple(x.shape)))
+    if g is not None:
+        N, P = g.N, g.P
+        if x.shape[0] != N:
+            raise ValueError("x has %d rows, the prepared graph %d nodes" % (x.shape[0], N))
+    else:
+        N, P = x.shape[0], data.bbox.shape[0]
+        E = ops.edge_layout(data.edge)[0]
+        if tuple(data.e_attr.shape) != (E, 4):
+            raise ValueError("e_attr must be [E, 4] = [%d, 4], got %s" % (E, tuple(data.e_attr.shape)))
+        if data.bbox_idx.numel() != N:
+            raise ValueError("bbox_idx must hold one proposal id per node (%d), got %d" % (N, data.bbox_idx.numel()))
+    if labels.numel() != P:
+        raise ValueError("labels must hold one class per proposal (%d), got %d" % (P, labels.numel()))
+
+
 class TrainPlan(object):
     """Descriptor (pointers into the flat parameter / gradient buffers + BatchNorm buffers), grow-only workspace and status
     word of yolat_train_step for one Trainer.  `step_phases` enqueues phases of one training step on the current stream
@@ -384,33 +414,33 @@ class TrainPlan(object):
 
     # -- one step -----------------------------------------------------------------------------------------------------
     def stage(self, data):
-        """device operands of the step: (x, edge-or-None, strides, e_attr, bbox_idx, prepared graph-or-None, labels, N, E, P)"""
+        """device operands of the step (a `Staged` record); the batch has passed check_batch_shapes"""
         model = self.model
-        pre = data.__dict__.get("_yolat_graph") if hasattr(data, "__dict__") else None
-        if pre is not None:
-            x = data.x if data.x.dtype == torch.float32 else data.x.float()
-            P = pre.P
-            ops_in = (x, None, 0, 0, None, None, pre, pre.N, pre.E, P)
-        else:
-            st = model._stage_tensors(data)
-            x, edge = st["x"], st["edge"]
-            E, se, sc = ops.edge_layout(edge)
-            e_attr = st["e_attr"] if st["e_attr"].is_contiguous() else st["e_attr"].contiguous()
-            ops_in = (x, edge, se, sc, e_attr, st["bbox_idx"], None, x.shape[0], E, st["bbox"].shape[0])
         labels = data.labels
         if not labels.is_cuda and labels.numel():
             lo, hi = int(labels.min()), int(labels.max())
             if lo < 0 or hi >= model.n_classes:
                 raise IndexError("Target %d is out of bounds." % (lo if lo < 0 else hi))
-        return ops_in + (labels.cuda(non_blocking=True),)
+        labels = labels.cuda(non_blocking=True)
+        pre = data.__dict__.get("_yolat_graph") if hasattr(data, "__dict__") else None
+        if pre is not None:
+            x = data.x if data.x.dtype == torch.float32 else data.x.float()
+            return Staged(x, None, 0, 0, None, None, pre, pre.N, pre.E, pre.P, labels)
+        st = model._stage_tensors(data)
+        x, edge = st["x"], st["edge"]
+        E, se, sc = ops.edge_layout(edge)
+        e_attr = st["e_attr"] if st["e_attr"].is_contiguous() else st["e_attr"].contiguous()
+        return Staged(x, edge, se, sc, e_attr, st["bbox_idx"], None, x.shape[0], E, st["bbox"].shape[0], labels)
 
     def run(self, staged, phases, adam=None):
         """Enqueue `phases` (bit mask, yolat_train_step) of the step on `staged`; returns False when the C side declines the
-        shapes (nothing was enqueued; only possible with phase 1)."""
+        shapes (YOLAT_E_UNSUPPORTED: decided in front of the first launch, nothing was enqueued; only with phase 1)."""
         import ctypes
         from . import engine
         from ._lib import lib, check, GraphCsr, AdamArgs
-        x, edge, se, sc, e_attr, bbox_idx, g, N, E, P, labels = staged
+        x, edge, e_attr, bbox_idx, g, labels = (staged.x, staged.edge, staged.e_attr, staged.bbox_idx, staged.graph,
+                                                 staged.labels)
+        se, sc, N, E, P = staged.stride_e, staged.stride_c, staged.N, staged.E, staged.P
         d = self._desc
         if E < N or E <= 0:
             return False
@@ -456,9 +486,7 @@ class TrainPlan(object):
         return True
 
     def check_status(self):
-        g = ops.Graph()
-        g.status = self._status
-        return ops.Graph.check_status(g)
+        return ops.check_status_word(self._status)
 
 
 class Trainer(object):
@@ -495,61 +523,44 @@ class Trainer(object):
         return (o.exp_avg.data_ptr(), o.exp_avg_sq.data_ptr(), self.flat.numel, o.step_count, float(g["lr"]),
                 float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]), float(scale))
 
-    def _plan_step(self, data):
-        """The step through yolat_train_step; returns the loss tensor, or None when the plan declines (nothing enqueued)."""
+    def _plan_forward(self, data, whole_step):
+        """Phase 1 of the step through yolat_train_step (graph, forward, loss, backward of the head).  Returns (loss,
+        backward) — backward None: `whole_step` was asked for and ONE call ran everything, Adam included — or None when
+        the plan declines (nothing enqueued)."""
         plan = self.plan
         if not (TRAIN_PLAN and TrainPlan.schedule_is_default() and plan.prepare()):
             return None
         staged = plan.stage(data)
-        grouped = dist.is_available() and dist.is_initialized()
-        world = dist.get_world_size() if grouped else 1
-        exchange = self.exchange_gradients and grouped and (world > 1 or self.force_exchange)
-        check = self._steps == 0 or (self.check_inputs_every > 0 and self._steps % self.check_inputs_every == 0)
-        if not self.model.training:          # (nn.Module.train() walks ~100 modules: not once per step)
-            self.model.train()
-        self.optimizer.zero_grad()
-        self.model.__dict__["_yolat_plan"] = plan if staged[6] is None else staged[6]
-        if not exchange and not check:
-            # the whole step in ONE call: graph + forward + loss + backward + Adam
+        self.model.__dict__["_yolat_plan"] = plan if staged.graph is None else staged.graph
+        if whole_step:
             self.optimizer.step_count += 1
             if not plan.run(staged, 7, self._adam_args(1.0)):
                 self.optimizer.step_count -= 1
                 return None
             self.flat.grads_ready = True
-            self._steps += 1
-            self.plan_steps += 1
-            return plan.last[1][0]
+            return plan.last[1][0], None
         if not plan.run(staged, 1):
             return None
-        premul = self.exchange_premul if exchange else None
-        scale = 1.0
 
-        def reduce_(bucket, async_op):
-            if premul is not None:
-                bucket.mul_(premul)
-            return dist.all_reduce(bucket, op=dist.ReduceOp.SUM, async_op=async_op)
+        def backward(on_head_done):
+            if on_head_done is not None:        # the head bucket is final after phase 1
+                on_head_done()
+            plan.run(staged, 2)
+            self.flat.grads_ready = True
+        return plan.last[1][0], backward
 
-        if exchange and self.flat.conv_end > 0 and dp_buckets() == 2:
-            handles = [reduce_(self.flat.grad[self.flat.conv_end:], True)]      # the head bucket, final after phase 1
-            plan.run(staged, 2)
-            handles.append(reduce_(self.flat.grad[:self.flat.conv_end], True))
-            for h in handles:
-                h.wait()
-            scale = 1.0 / world
-        else:
-            plan.run(staged, 2)
-            if exchange:
-                reduce_(self.flat.grad, False)
-                scale = 1.0 / world
-        if premul is not None:
-            scale /= premul
-        self.flat.grads_ready = True
-        if check:
-            self.model.check_last_status()      # raises before the update is applied
-        self._steps += 1
-        self.plan_steps += 1
-        self.optimizer.step(grad_scale=scale)
-        return plan.last[1][0]
+    def _python_forward(self, data, slices):
+        """Forward and loss on the Python schedule (engine.py through autograd); same return as _plan_forward."""
+        out = self.model(data, slices)
+        loss = self.criterion(out, data)["loss"]
+
+        def backward(on_head_done):
+            self.flat.on_head_done = on_head_done
+            try:
+                loss.backward()
+            finally:
+                self.flat.on_head_done = None
+        return loss, backward
 
     def step(self, data, slices=None):
         """One training step on this rank's batch.  Returns the (device) loss tensor."""
@@ -557,18 +568,22 @@ class Trainer(object):
         if engine._FAULT_EARLY_HEAD_EXCHANGE and self.exchange_premul is None:
             raise RuntimeError("engine._FAULT_EARLY_HEAD_EXCHANGE is set outside its test (a leaked fault-injection flag): "
                                "the head bucket would be exchanged before its gradients exist")
-        loss = self._plan_step(data)
-        if loss is not None:
-            return loss.detach()
-        self.model.train()
-        self.optimizer.zero_grad()
-        out = self.model(data, slices)
-        loss = self.criterion(out, data)["loss"]
+        check_batch_shapes(self.model, data)
         grouped = dist.is_available() and dist.is_initialized()
         world = dist.get_world_size() if grouped else 1
         exchange = self.exchange_gradients and grouped and (world > 1 or self.force_exchange)
-        if not exchange:
-            world = 1
+        check = self._steps == 0 or (self.check_inputs_every > 0 and self._steps % self.check_inputs_every == 0)
+        if not self.model.training:          # (nn.Module.train() walks ~100 modules: not once per step)
+            self.model.train()
+        self.optimizer.zero_grad()
+        # the two schedules supply the forward + loss and a backward(on_head_done); the rest of the step is one body
+        fwd = self._plan_forward(data, whole_step=not exchange and not check)
+        planned = fwd is not None
+        loss, backward = fwd if planned else self._python_forward(data, slices)
+        if backward is None:
+            self._steps += 1
+            self.plan_steps += 1
+            return loss.detach()
         premul = self.exchange_premul if exchange else None
 
         def reduce_(bucket, async_op):
@@ -576,30 +591,25 @@ class Trainer(object):
                 bucket.mul_(premul)
             return dist.all_reduce(bucket, op=dist.ReduceOp.SUM, async_op=async_op)
 
+        scale = 1.0 / world if exchange else 1.0
         if exchange and self.flat.conv_end > 0 and dp_buckets() == 2:
             # bucket 1 (fusion blocks + classifier, 93 % of the bytes) is all-reduced while the conv layers'
             # backward still runs; bucket 2 (conv layers) after the backward
             handles = []
             tail = self.flat.grad[self.flat.conv_end:]
-            self.flat.on_head_done = lambda: handles.append(reduce_(tail, True))
-            try:
-                loss.backward()
-            finally:
-                self.flat.on_head_done = None
+            backward(lambda: handles.append(reduce_(tail, True)))
             handles.append(reduce_(self.flat.grad[:self.flat.conv_end], True))
             for h in handles:
                 h.wait()
-            scale = 1.0 / world
         else:
-            loss.backward()
-            scale = 1.0
+            backward(None)
             if exchange:
                 reduce_(self.flat.grad, False)
-                scale = 1.0 / world
         if premul is not None:
             scale /= premul
-        if self._steps == 0 or (self.check_inputs_every > 0 and self._steps % self.check_inputs_every == 0):
+        if check:
             self.model.check_last_status()      # raises before the update is applied
         self._steps += 1
+        self.plan_steps += planned
         self.optimizer.step(grad_scale=scale)
         return loss.detach()
