@@ -448,6 +448,29 @@ size_t yolat_softmax_ce_work_elems(int64_t P);
 int yolat_softmax_ce(const float* logits, int64_t ld, const int64_t* labels, int64_t P, int64_t K,
                      float* loss, float* dlogits, int64_t lddl, float* work, yolat_stream_t stream);
 
+/* classifier != 'softmax' (architecture3cc_rpn_gp_iter2.py:132-133,362-376): torch.sigmoid on the logits and
+ * nn.BCELoss() (mean over all P*K elements) against the one-hot labels.  Every step rounded to fp32 on its own:
+ *   p = 1 / (1 + exp(-z));  loss = (1/n) sum -( t ? max(log p, -100) : max(log(1 - p), -100) ),  n = P K
+ *   q = p (1 - p);  dp = ((p - t) / max(q, 1e-12)) / n;  dz = dp q
+ * — torch's BCELoss backward followed by its sigmoid backward, not the closed form (p - t)/n: where p rounds to exactly
+ * 1.0f / 0.0f the gradient is 0 and a wrong element's loss term is 100, as in the reference.
+ *   yolat_sigmoid:      out [P,K] = p (out may alias z).
+ *   yolat_sigmoid_bwd:  dz [P,K] = dp * (p (1 - p)) (dz may alias dp).
+ *   yolat_bce:          loss[0] and dprob [P,K] (nullable) from probabilities.
+ *   yolat_sigmoid_bce:  the three in one launch from logits: loss[0], dlogits [P,K] (nullable), prob [P,K] (nullable);
+ *                       bit-identical to yolat_sigmoid -> yolat_bce -> yolat_sigmoid_bwd (the same device functions).
+ * work: yolat_bce_work_elems(P) floats (required): per-workgroup partial sums, added in a fixed order -> deterministic.
+ * A label outside [0, K) makes the loss NaN and reads nothing out of bounds; the row's gradient is written (as for an
+ * all-zero target row).                                                                                              */
+int yolat_sigmoid(const float* z, int64_t ldz, int64_t P, int64_t K, float* out, int64_t ldo, yolat_stream_t stream);
+int yolat_sigmoid_bwd(const float* dp, int64_t lddp, const float* p, int64_t ldp, int64_t P, int64_t K, float* dz,
+                      int64_t lddz, yolat_stream_t stream);
+size_t yolat_bce_work_elems(int64_t P);
+int yolat_bce(const float* prob, int64_t ld, const int64_t* labels, int64_t P, int64_t K, float* loss, float* dprob,
+              int64_t lddp, float* work, yolat_stream_t stream);
+int yolat_sigmoid_bce(const float* logits, int64_t ld, const int64_t* labels, int64_t P, int64_t K, float* loss,
+                      float* dlogits, int64_t lddl, float* prob, int64_t ldp, float* work, yolat_stream_t stream);
+
 /* torch.optim.Adam step (train.py:212: lr, weight_decay as L2-in-grad, betas (0.9,0.999),
  * eps 1e-8, no amsgrad) over one flat fp32 buffer of n elements; `step` is the 1-based step.     */
 int yolat_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
@@ -770,11 +793,13 @@ int yolat_forward_eval_bf16_csr(const yolat_model_eval_bf16* m, const float* x, 
  * issues from Python, the same kernels on the same operands in the same order per stream, so the results are bit-identical.
  *   yolat_train_model: pointers into ONE flat parameter buffer (param_base) and its gradient twin (grad_base, same
  *     offsets: trainer.FlatParams); BatchNorm running statistics / counters are updated in place.
- *   Shapes: n_filters C = 64, n_blocks_out = 2, biases and BatchNorm on every layer, no dropout, E >= N; `half` != 0:
- *     bfloat16 storage of the per-edge tensors where E >= 2 N; bit 2 of `half` (half = 3) additionally selects the
- *     "bf16_dense" head (fusion_block, fusion_block_super, prediction_cls.0 / .1 on the yolat_bt_* / _bf16 entry points;
- *     F % 64 == 0, H1 % 32 == 0, H2 % 32 == 0, 16-byte aligned weights of those layers).  Anything else:
- *     YOLAT_E_UNSUPPORTED (the caller keeps its own schedule).
+ *   Shapes: n_filters C = 64, n_blocks_out = 2, biases and BatchNorm on every layer, no dropout, E >= N; `half` is a bit
+ *     set: (half & 3) != 0: bfloat16 storage of the per-edge tensors where E >= 2 N; bit 2 of `half` (half = 3)
+ *     additionally selects the "bf16_dense" head (fusion_block, fusion_block_super, prediction_cls.0 / .1 on the
+ *     yolat_bt_* / _bf16 entry points; F % 64 == 0, H1 % 32 == 0, H2 % 32 == 0, 16-byte aligned weights of those layers);
+ *     bit 4 (half = 4, 5, 7) selects the sigmoid / BCELoss head of classifier != 'softmax' (arch:132-133,362-376):
+ *     the loss and dlogits come from yolat_sigmoid_bce instead of yolat_softmax_ce, `logits` still receives the raw
+ *     logits.  Other bits: YOLAT_E_INVALID.  Anything else: YOLAT_E_UNSUPPORTED (the caller keeps its own schedule).
  *   Batch: the collated COO arrays (edge / e_attr / bbox_idx; the destination-sorted form is built inside the call), or a
  *     prepared graph g.  labels [P] int64.  logits [P, ld_logits] and loss [1] are written; *status as yolat_graph_prepare.
  *   phases (bit mask): 1 = graph + forward + loss + backward of the classifier and the fusion blocks — on return every

@@ -99,6 +99,21 @@ class _ModelFn(torch.autograd.Function):
         return (None, None, None) + tuple(sink.out.get(id(p)) for p in params)
 
 
+class _SigmoidFn(torch.autograd.Function):
+    """torch.sigmoid of arch:132-133 (classifier != 'softmax') on the HIP kernels: ops.sigmoid / ops.sigmoid_bwd."""
+
+    @staticmethod
+    def forward(ctx, z):
+        p = ops.sigmoid(z)
+        ctx.save_for_backward(p)
+        return p
+
+    @staticmethod
+    def backward(ctx, dp):
+        (p,) = ctx.saved_tensors
+        return ops.sigmoid_bwd(dp if dp.stride(-1) == 1 else dp.contiguous(), p)
+
+
 # predict(): one forward over the whole batch + integer selection on the device (csrc/subgraph.hip, yolat_predict_select);
 # False: always the two-pass sub-graph extraction (module flag; the tests run both)
 PREDICT_ONE_SUBMISSION = True
@@ -218,7 +233,7 @@ class SparseCADGCN(nn.Module):
             self._yolat_plan = st["g"]       # ops.Graph carries the status word of the training path
             pred_cls = _ModelFn.apply(self, st["g"], st["x"], *list(self.parameters()))
         if self.classifier != "softmax":
-            pred_cls = torch.sigmoid(pred_cls)
+            pred_cls = _SigmoidFn.apply(pred_cls)
         return pred_cls, st["bbox"]
 
     def check_last_status(self):
@@ -227,11 +242,11 @@ class SparseCADGCN(nn.Module):
         return True if last is None else last.check_status()
 
     def predict(self, data, slices):
-        """arch:139-356.  Eval mode, softmax classifier, a batch with its raw edge list: ONE forward over the whole batch
+        """arch:139-356.  Eval mode, a batch with its raw edge list: ONE forward over the whole batch
         + integer selection on the device (`_predict_one_submission`: no host round trip between the two passes of the
         reference, one read at the end); when the tree of the batch is not made of the ranges of its own proposals — or in
         any other mode — the two-pass extraction (`_predict_two_pass`).  Same 6-tuple either way."""
-        if PREDICT_ONE_SUBMISSION and not self.training and self.classifier == "softmax":
+        if PREDICT_ONE_SUBMISSION and not self.training:
             out = self._predict_one_submission(data, slices)
             if out is not None:
                 return out
@@ -405,7 +420,7 @@ class SparseCADGCN(nn.Module):
         st = self._stage(data)
         pred_cls = _ModelFn.apply(self, st["g"], st["x"], *list(self.parameters()))
         if self.classifier != "softmax":
-            pred_cls = torch.sigmoid(pred_cls)
+            pred_cls = _SigmoidFn.apply(pred_cls)
         return pred_cls, st["bbox"]
 
     def forward_modular(self, data, slices=None):
@@ -416,7 +431,7 @@ class SparseCADGCN(nn.Module):
         out_feat = scatter(out_feat, bbox_idx, dim=0, reduce="max")
         pred_cls = self.prediction_cls(torch.cat([out_feat, out_super], dim=1))
         if self.classifier != "softmax":
-            pred_cls = torch.sigmoid(pred_cls)
+            pred_cls = _SigmoidFn.apply(pred_cls)
         return pred_cls, pred_bbox
 
 
@@ -435,14 +450,32 @@ class _CEFn(torch.autograd.Function):
         return dl * gout, None
 
 
+class _BCEFn(torch.autograd.Function):
+    """nn.BCELoss (mean over all elements) against the one-hot labels, arch:362-376: ops.bce."""
+
+    @staticmethod
+    def forward(ctx, prob, labels):
+        loss = torch.empty(1, dtype=torch.float32, device=prob.device)
+        dp = torch.empty_like(prob) if ctx.needs_input_grad[0] else None      # (no_grad: the loss alone)
+        ops.bce(prob, labels, loss, dp)
+        ctx.save_for_backward(dp)
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, gout):
+        (dp,) = ctx.saved_tensors
+        return dp * gout, None
+
+
 class DetectionLoss(nn.Module):
-    """arch:358-379: CrossEntropyLoss (mean over proposals) for classifier='softmax'."""
+    """arch:358-379: CrossEntropyLoss (mean over proposals) for classifier='softmax', else BCELoss (mean over all
+    elements) of the sigmoid outputs against the one-hot labels."""
 
     def __init__(self, opt):
         super(DetectionLoss, self).__init__()
         self.classifier = opt.classifier
         if opt.classifier != "softmax":
-            self.cls_loss = nn.BCELoss()
+            self.cls_loss = nn.BCELoss()      # the reference's attribute (state / compatibility); the loss is _BCEFn
 
     def forward(self, out, data):
         pred_cls = out[0]
@@ -457,9 +490,7 @@ class DetectionLoss(nn.Module):
         if self.classifier == "softmax":
             l0 = _CEFn.apply(pred_cls.contiguous(), gt_cls)
         else:
-            # non-default branch of the reference (BCE on sigmoid outputs): plain torch ops
-            tgt = torch.zeros(pred_cls.size(), device=pred_cls.device).scatter_(1, gt_cls.unsqueeze(1), 1)
-            l0 = self.cls_loss(pred_cls, tgt)
+            l0 = _BCEFn.apply(pred_cls.contiguous(), gt_cls)
         return {"loss": l0, "loss_cls": l0}
 
 

@@ -1,5 +1,6 @@
-// loss_optim.hip — nn.CrossEntropyLoss of DetectionLoss (architecture3cc_rpn_gp_iter2.py:363,376)
-// and the torch.optim.Adam step of cad_recognition/train.py:212,284 over one flat buffer.
+// loss_optim.hip — nn.CrossEntropyLoss of DetectionLoss (architecture3cc_rpn_gp_iter2.py:363,376), the sigmoid /
+// nn.BCELoss head of classifier != 'softmax' (:132-133,362-376), and the torch.optim.Adam step of
+// cad_recognition/train.py:212,284 over one flat buffer.
 #include "common.hpp"
 
 // One 1024-thread workgroup; thread t owns rows t, t+1024, ...; fixed-order tree reduction.
@@ -122,6 +123,161 @@ extern "C" int yolat_softmax_ce(const float* logits, int64_t ld, const int64_t* 
                      labels, (int)P, (int)K, loss, dlogits, (long)lddl);
   YL_LAUNCH_CHECK();
   return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// classifier != 'softmax' (architecture3cc_rpn_gp_iter2.py:132-133,362-376): torch.sigmoid on the logits, nn.BCELoss
+// (mean over all P*K elements) against the one-hot labels.  Every step is rounded to fp32 on its own, in torch's order:
+//   p = 1 / (1 + exp(-z));  term = -max(log(p), -100) (target 1) or -max(log(1 - p), -100) (target 0)
+//   q = p (1 - p);  dp = ((p - t) / max(q, 1e-12)) / n;  dz = dp q
+// which is BCELoss' backward followed by sigmoid's — NOT the closed form (p - t) / n: where p rounds to exactly 1.0f or
+// 0.0f the reference's gradient is 0 and a wrong element's loss term is 100, and that is kept.
+// The fused entry point and the three separate ones run these same four functions, so they agree bit for bit.
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ float yl_sigmoid(float z) { return 1.f / (1.f + expf(-z)); }
+__device__ __forceinline__ float yl_bce_term(float p, bool t) {
+  return -(t ? fmaxf(logf(p), -100.f) : fmaxf(logf(1.f - p), -100.f));
+}
+__device__ __forceinline__ float yl_bce_dp(float p, bool t, float inv_n) {
+  const float q = p * (1.f - p);
+  return ((p - (t ? 1.f : 0.f)) / fmaxf(q, 1e-12f)) * inv_n;
+}
+__device__ __forceinline__ float yl_sigmoid_dz(float dp, float p) { return dp * (p * (1.f - p)); }
+
+// One element of a row: in = logit (LOGITS) or probability; adds the loss term, writes prob (LOGITS only, nullable)
+// and the gradient w.r.t. `in` (nullable).
+template <bool LOGITS>
+__device__ __forceinline__ float yl_bce_elem(float in, bool t, float inv_n, float* prob, float* dout) {
+  const float p = LOGITS ? yl_sigmoid(in) : in;
+  if (LOGITS && prob != nullptr) *prob = p;
+  if (dout != nullptr) {
+    const float dp = yl_bce_dp(p, t, inv_n);
+    *dout = LOGITS ? yl_sigmoid_dz(dp, p) : dp;
+  }
+  return yl_bce_term(p, t);
+}
+
+// One row per thread, 256 rows per workgroup, like k_softmax_ce_rows.  KMAX > 0: K <= KMAX, the row is loaded into
+// registers first (all loads independent); KMAX == 0: a plain loop over K.  The row's terms are added in ascending
+// column order either way, the workgroup's rows in a fixed-order tree -> work[wg]; k_bce_final adds those in order.
+template <int KMAX, bool LOGITS>
+__global__ void __launch_bounds__(256) k_bce_rows(const float* in, long ld, const int64_t* labels, int P, int K,
+                                                  float inv_n, float* work, float* dout, long ldd, float* prob,
+                                                  long ldp) {
+  __shared__ float red[256];
+  const int tid = threadIdx.x;
+  const int p = blockIdx.x * 256 + tid;
+  float row_loss = 0.f;
+  if (p < P) {
+    const float* z = in + (long)p * ld;
+    // a label outside [0, K) matches no column (nothing is read through it); the loss is poisoned with NaN
+    const int64_t yl = labels[p];
+    const bool bad = yl < 0 || yl >= K;
+    const int y = bad ? -1 : (int)yl;
+    float* d = dout != nullptr ? dout + (long)p * ldd : nullptr;
+    float* pr = (LOGITS && prob != nullptr) ? prob + (long)p * ldp : nullptr;
+    if (KMAX > 0) {
+      float v[KMAX > 0 ? KMAX : 1];
+#pragma unroll
+      for (int k = 0; k < KMAX; ++k) v[k] = z[k < K ? k : K - 1];
+#pragma unroll
+      for (int k = 0; k < KMAX; ++k)
+        if (k < K) row_loss += yl_bce_elem<LOGITS>(v[k], k == y, inv_n, pr ? pr + k : nullptr, d ? d + k : nullptr);
+    } else {
+      for (int k = 0; k < K; ++k)
+        row_loss += yl_bce_elem<LOGITS>(z[k], k == y, inv_n, pr ? pr + k : nullptr, d ? d + k : nullptr);
+    }
+    if (bad) row_loss = __builtin_nanf("");
+  }
+  red[tid] = row_loss;
+  __syncthreads();
+  for (int st = 128; st > 0; st >>= 1) {
+    if (tid < st) red[tid] += red[tid + st];
+    __syncthreads();
+  }
+  if (tid == 0) work[blockIdx.x] = red[0];
+}
+
+__global__ void __launch_bounds__(1024) k_bce_final(const float* work, int n, float inv_n, float* loss) {
+  __shared__ float red[1024];
+  const int tid = threadIdx.x;
+  float a = 0.f;
+  for (int i = tid; i < n; i += 1024) a += work[i];
+  red[tid] = a;
+  __syncthreads();
+  for (int st = 512; st > 0; st >>= 1) {
+    if (tid < st) red[tid] += red[tid + st];
+    __syncthreads();
+  }
+  if (tid == 0) loss[0] = inv_n * red[0];
+}
+
+__global__ void k_sigmoid(const float* z, long ldz, long n, int K, float* out, long ldo) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const long r = i / K;
+  const int c = (int)(i % K);
+  out[r * ldo + c] = yl_sigmoid(z[r * ldz + c]);
+}
+
+__global__ void k_sigmoid_bwd(const float* dp, long lddp, const float* p, long ldp, long n, int K, float* dz, long lddz) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const long r = i / K;
+  const int c = (int)(i % K);
+  dz[r * lddz + c] = yl_sigmoid_dz(dp[r * lddp + c], p[r * ldp + c]);
+}
+
+extern "C" int yolat_sigmoid(const float* z, int64_t ldz, int64_t P, int64_t K, float* out, int64_t ldo,
+                             yolat_stream_t stream) {
+  if (P <= 0 || K <= 0 || !z || !out || ldz < K || ldo < K || P >= (1LL << 31) || K >= (1LL << 31)) return YOLAT_E_INVALID;
+  hipLaunchKernelGGL(k_sigmoid, dim3(yl_cdiv(P * K, 256)), dim3(256), 0, (hipStream_t)stream, z, (long)ldz, (long)(P * K),
+                     (int)K, out, (long)ldo);
+  YL_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int yolat_sigmoid_bwd(const float* dp, int64_t lddp, const float* p, int64_t ldp, int64_t P, int64_t K,
+                                 float* dz, int64_t lddz, yolat_stream_t stream) {
+  if (P <= 0 || K <= 0 || !dp || !p || !dz || lddp < K || ldp < K || lddz < K || P >= (1LL << 31) || K >= (1LL << 31))
+    return YOLAT_E_INVALID;
+  hipLaunchKernelGGL(k_sigmoid_bwd, dim3(yl_cdiv(P * K, 256)), dim3(256), 0, (hipStream_t)stream, dp, (long)lddp, p,
+                     (long)ldp, (long)(P * K), (int)K, dz, (long)lddz);
+  YL_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" size_t yolat_bce_work_elems(int64_t P) { return P > 0 ? (size_t)((P + 255) / 256 + 1) : 1; }
+
+template <bool LOGITS>
+static int bce_launch(const float* in, int64_t ld, const int64_t* labels, int64_t P, int64_t K, float* loss, float* dout,
+                      int64_t ldd, float* prob, int64_t ldp, float* work, yolat_stream_t stream) {
+  if (P <= 0 || K <= 0 || !in || !labels || !loss || !work || ld < K || P >= (1LL << 31) || K >= (1LL << 31))
+    return YOLAT_E_INVALID;
+  if ((dout && ldd < K) || (prob && ldp < K)) return YOLAT_E_INVALID;
+  const int nwg = yl_cdiv(P, 256);
+  const float inv_n = 1.f / (float)(P * K);
+  if (K <= 32)
+    hipLaunchKernelGGL((k_bce_rows<32, LOGITS>), dim3(nwg), dim3(256), 0, (hipStream_t)stream, in, (long)ld, labels, (int)P,
+                       (int)K, inv_n, work, dout, (long)ldd, prob, (long)ldp);
+  else
+    hipLaunchKernelGGL((k_bce_rows<0, LOGITS>), dim3(nwg), dim3(256), 0, (hipStream_t)stream, in, (long)ld, labels, (int)P,
+                       (int)K, inv_n, work, dout, (long)ldd, prob, (long)ldp);
+  YL_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_bce_final, dim3(1), dim3(1024), 0, (hipStream_t)stream, work, nwg, inv_n, loss);
+  YL_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int yolat_bce(const float* prob, int64_t ld, const int64_t* labels, int64_t P, int64_t K, float* loss,
+                         float* dprob, int64_t lddp, float* work, yolat_stream_t stream) {
+  return bce_launch<false>(prob, ld, labels, P, K, loss, dprob, lddp, nullptr, 0, work, stream);
+}
+
+extern "C" int yolat_sigmoid_bce(const float* logits, int64_t ld, const int64_t* labels, int64_t P, int64_t K,
+                                 float* loss, float* dlogits, int64_t lddl, float* prob, int64_t ldp, float* work,
+                                 yolat_stream_t stream) {
+  return bce_launch<true>(logits, ld, labels, P, K, loss, dlogits, lddl, prob, ldp, work, stream);
 }
 
 // torch.optim.Adam (single-tensor formulation): g += wd*p; m.lerp_(g, 1-b1);

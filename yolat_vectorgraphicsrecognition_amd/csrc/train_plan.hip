@@ -1,4 +1,4 @@
-// train_plan.hip — the training step as ONE native call (round 6): graph preparation + forward + CrossEntropy + backward
+// train_plan.hip — the training step as ONE native call (round 6): graph preparation + forward + loss + backward
 // (+ Adam) enqueued from C on two streams, exactly the schedule engine.py issues from Python (same kernels, same operands,
 // same order per stream -> bit-identical losses, gradients and parameters), without ~150-230 ctypes calls, tensor
 // allocations and record_stream marks per step on the host.
@@ -10,8 +10,9 @@
 // the HOST schedule only; the kernels are where they were.
 //
 // Covered: the reference recipe's shapes on the default schedule of engine.py — n_filters 64, n_blocks_out 2 (fusion dims
-// 128: the fused fusion block), Linear biases and BatchNorm everywhere, no dropout, softmax classifier, E >= N (the
-// factorised backward of the first edge Linear) — fp32 and bf16 storage of the per-edge tensors, and the "bf16_dense"
+// 128: the fused fusion block), Linear biases and BatchNorm everywhere, no dropout, E >= N (the factorised backward of the
+// first edge Linear), the softmax / CrossEntropy head or the sigmoid / BCELoss head of classifier != 'softmax' (half bit 4:
+// yolat_sigmoid_bce in place of yolat_softmax_ce, nothing else changes) — fp32 and bf16 storage of the per-edge tensors, and the "bf16_dense"
 // precision (half bit 2: fusion_block, fusion_block_super and prediction_cls.0 / .1 on the bf16-operand kernels of
 // bf16_train.hip and the _bf16 fusion entry points, as engine.py issues them for that mode; needs F % 64 == 0,
 // H1 % 32 == 0, H2 % 32 == 0 and 16-byte aligned weights of those layers).  Anything else returns YOLAT_E_UNSUPPORTED
@@ -35,6 +36,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <algorithm>
 #include <mutex>
 #include <vector>
 
@@ -117,7 +119,7 @@ TrainBuf carve(const yolat_train_model* m, long N, long E, long P, void* ws) {
     ConvBuf& v = b.cv[l];
     const long Cin = m->conv[l].Cin, slot = l - d.lo;
     v.fact_fwd = C == 64 && (double)E >= 2.0 * (double)N;
-    v.half = m->half != 0 && v.fact_fwd;
+    v.half = (m->half & 3) != 0 && v.fact_fwd;
     const size_t es = v.half ? 2 : 4;
     v.f_tmp = slot < 0 ? c.take<float>(N * C) : nullptr;
     v.s_tmp = slot < 0 ? c.take<float>(N * C) : nullptr;
@@ -150,7 +152,7 @@ TrainBuf carve(const yolat_train_model* m, long N, long E, long P, void* ws) {
   b.c1y = c.take<float>(P * d.H1); b.c1st = c.take<float>(nz(yolat_bn_stats_elems(P, d.H1))); b.c1c = c.take<float>(4 * d.H1);
   b.c1pack = c.take<uint16_t>(nz(yolat_gemm_x6_packed_elems(d.H1, ZW)));
   b.c2y = c.take<float>(P * d.H2); b.c2st = c.take<float>(nz(yolat_bn_stats_elems(P, d.H2))); b.c2c = c.take<float>(4 * d.H2);
-  b.dl = c.take<float>(P * K); b.ce_work = c.take<float>(nz(yolat_softmax_ce_work_elems(P)));
+  b.dl = c.take<float>(P * K); b.ce_work = c.take<float>(nz(std::max(yolat_softmax_ce_work_elems(P), yolat_bce_work_elems(P))));
   b.d2 = c.take<float>(P * d.H2); b.d1 = c.take<float>(P * d.H1); b.dZ = c.take<float>(P * ZW);
   b.d_fsup = c.take<float>(N * D); b.d_feats = c.take<float>(N * D);
   b.w3 = c.take<float>(nz(yolat_linear_bwd_w_work_elems(P, K, d.H2)));
@@ -177,7 +179,7 @@ int model_ok(const yolat_train_model* m) {
   if (m->n_blocks < 1 || m->n_blocks > TP_MAXL || m->n_blocks_out < 1 || m->n_blocks_out > m->n_blocks || m->n_classes < 1)
     return YOLAT_E_INVALID;
   if (m->C != 64 || m->n_blocks_out != 2 || m->F <= 0 || m->F % 4 != 0 || m->H1 <= 0 || m->H2 <= 0) return YOLAT_E_UNSUPPORTED;
-  if ((m->half & ~3) != 0) return YOLAT_E_INVALID;
+  if ((m->half & ~7) != 0) return YOLAT_E_INVALID;
   if ((m->half & 2) && (m->F % 64 != 0 || m->H1 % 32 != 0 || m->H2 % 32 != 0)) return YOLAT_E_UNSUPPORTED;
   auto lin_ok = [](const yolat_train_lin& l) { return l.W != nullptr && l.b != nullptr; };
   auto bn_ok = [](const yolat_train_bn& b) { return b.gamma != nullptr && b.beta != nullptr; };
@@ -523,6 +525,8 @@ int Sched::head_fwd() {
       YL_LAUNCH_CHECK();
     }
   }
+  if (m->half & 4)     // classifier != 'softmax': sigmoid + BCELoss (arch:132-133,362-376); logits stay raw, dl = dLoss/dlogits
+    return yolat_sigmoid_bce(a.logits, a.ld_logits, a.labels, P, d.K, a.loss, b.dl, d.K, nullptr, 0, b.ce_work, st);
   return yolat_softmax_ce(a.logits, a.ld_logits, a.labels, P, d.K, a.loss, b.dl, d.K, b.ce_work, st);
 }
 

@@ -992,6 +992,48 @@ def softmax_ce(logits, labels, loss, dlogits=None):
     return loss
 
 
+def sigmoid(z, out=None):
+    """out = 1 / (1 + exp(-z)) (yolat_sigmoid); `out` may be `z` itself."""
+    P, K = z.shape
+    if out is None:
+        out = torch.empty(P, K, dtype=torch.float32, device=z.device)
+    if P > 0:
+        check(lib.yolat_sigmoid(_f(z, "z"), _ld(z), P, K, _f(out, "out"), _ld(out), _stream()), "yolat_sigmoid")
+    return out
+
+
+def sigmoid_bwd(dp, p, dz=None):
+    """dz = dp * (p (1 - p)) (yolat_sigmoid_bwd)."""
+    P, K = p.shape
+    if dz is None:
+        dz = torch.empty(P, K, dtype=torch.float32, device=p.device)
+    if P > 0:
+        check(lib.yolat_sigmoid_bwd(_f(dp, "dp"), _ld(dp), _f(p, "p"), _ld(p), P, K, _f(dz, "dz"), _ld(dz), _stream()),
+              "yolat_sigmoid_bwd")
+    return dz
+
+
+def bce(prob, labels, loss, dprob=None):
+    """nn.BCELoss (mean over all elements) of probabilities against one-hot labels; dprob (optional) = dLoss/dprob."""
+    P, K = prob.shape
+    work = torch.empty(int(lib.yolat_bce_work_elems(P)), dtype=torch.float32, device=prob.device)
+    check(lib.yolat_bce(_f(prob, "prob"), _ld(prob), _i(labels, torch.int64, "labels"), P, K, _f(loss),
+                        _f(dprob, "dprob", True), _ld(dprob) if dprob is not None else K, work.data_ptr(), _stream()),
+          "yolat_bce")
+    return loss
+
+
+def sigmoid_bce(logits, labels, loss, dlogits=None, prob=None):
+    """sigmoid -> bce -> sigmoid_bwd in one launch from the logits (yolat_sigmoid_bce); bit-identical to the three calls."""
+    P, K = logits.shape
+    work = torch.empty(int(lib.yolat_bce_work_elems(P)), dtype=torch.float32, device=logits.device)
+    check(lib.yolat_sigmoid_bce(_f(logits, "logits"), _ld(logits), _i(labels, torch.int64, "labels"), P, K, _f(loss),
+                                _f(dlogits, "dlogits", True), _ld(dlogits) if dlogits is not None else K,
+                                _f(prob, "prob", True), _ld(prob) if prob is not None else K, work.data_ptr(), _stream()),
+          "yolat_sigmoid_bce")
+    return loss
+
+
 def adam_step(param, grad, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, weight_decay, step,
               grad_scale=1.0):
     bump_weight_epoch()

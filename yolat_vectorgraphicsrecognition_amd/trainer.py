@@ -327,7 +327,7 @@ class TrainPlan(object):
         from . import engine
         m = self.model
         net = getattr(m, "cls_net", None)
-        if net is None or m.classifier != "softmax":
+        if net is None:
             return False
         try:
             convs = engine.model_convs(net)
@@ -359,7 +359,10 @@ class TrainPlan(object):
         d = TrainModel()
         d.n_blocks, d.n_blocks_out, d.n_classes = net.n_blocks, net.n_blocks_out, m.n_classes
         # value 1: bf16 storage of the per-edge tensors; bit 2 on top (3): the bf16_dense head (csrc/train_plan.hip)
+        # bit 4: the sigmoid / BCELoss head of classifier != "softmax" (yolat_sigmoid_bce in place of yolat_softmax_ce)
         d.half = {"bf16": 1, "bf16_dense": 3}.get(m.__dict__.get("_yolat_train_precision", "fp32"), 0)
+        if m.classifier != "softmax":
+            d.half |= 4
         d.C = convs[0].nn[0].out_features
         d.F = net.fusion_block[0].out_features
         d.H1, d.H2 = m.prediction_cls[0][0].out_features, m.prediction_cls[1][0].out_features
@@ -400,7 +403,8 @@ class TrainPlan(object):
 
     def prepare(self):
         """(Re)builds the descriptor when a tensor it points at has moved; returns False when the model is outside the plan."""
-        key = tuple(t.data_ptr() for t in self._tensors()) + (self.model.__dict__.get("_yolat_train_precision", "fp32"),)
+        key = tuple(t.data_ptr() for t in self._tensors()) + (self.model.__dict__.get("_yolat_train_precision", "fp32"),
+                                                                     self.model.classifier)
         if key != self._key:
             if not self.model_fits():
                 self._desc = None
