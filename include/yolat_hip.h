@@ -157,6 +157,16 @@ int yolat_linear_fwd(const float* A, int64_t lda, int64_t M, int64_t K,
                      const float* o_scale, const float* o_shift, int o_relu,
                      float* Y, int64_t ldy, int accumulate, float* stats, yolat_stream_t stream);
 
+/* yolat_linear_fwd for few rows x long K (the per-proposal classifier: P x 2304 -> 512) without A prologue, statistics or
+ * accumulation: fp32 operands as they are (nothing is prepared per weight), 128-deep tiles brought into LDS by DMA, the
+ * products on the bf16 matrix cores as a bf16x6-emulated fp32 GEMM (six of the nine products of the exact 3-way bfloat16
+ * splits, fp32 accumulation; csrc/linear_sk_x6.hip).  Same precision class as the fp32 MFMA kernels, another summation
+ * grouping; deterministic.  K % 128 == 0, lda % 4 == 0, ldw % 4 == 0, A and W 16-byte aligned, M and Nout <= 65536: else
+ * YOLAT_E_UNSUPPORTED.  Non-finite inputs: an Inf operand gives NaN (Inf - Inf inside the split).                    */
+int yolat_linear_sk_x6(const float* A, int64_t lda, int64_t M, int64_t K, const float* W, int64_t ldw, const float* bias,
+                       int64_t Nout, const float* o_scale, const float* o_shift, int o_relu, float* Y, int64_t ldy,
+                       yolat_stream_t stream);
+
 /* Eval-mode fusion_block + per-proposal max pooling fused (arch:61-63 + arch:122):
  *   pool[p, 0:Nout] = max_{rows r of proposal p} relu((A[r].W^T + bias)*o_scale + o_shift)
  * node_seg[M] = proposal id of each row (non-decreasing).  `pool` MUST be zero-filled first

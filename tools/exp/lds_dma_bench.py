@@ -1,7 +1,8 @@
 """LDS-DMA experiment: the cfg-2 classifier-1 GEMM (P = 400 rows, 2304 -> 512; k_gemm_nt_sk, 122 MB of
 operand tiles through L2 -> CU) with its tiles brought in by global_load_lds_dwordx4 (k_gemm_nt_sk_dma) instead of
 global -> VGPR -> ds_write.  Bit-identity check, HIP-event timing of both, in-kernel s_memtime split of the DMA variant
-(cycles waiting for the tile / computing), and the cfg-2 forward with either kernel.
+(cycles waiting for the tile / computing), and the cfg-2 forward with either kernel.  Also the bf16x6 variant of the 8-wave
+kernel (yolat_linear_sk_x6, csrc/linear_sk_x6.hip): timing, error against fp64 and the same in-kernel split.
 usage: python tools/exp/lds_dma_bench.py [reps=200]"""
 import ctypes, os, sys, time
 import numpy as np
@@ -51,6 +52,27 @@ for (M, K, N) in ((400, 2304, 512), (400, 512, 256), (2000, 2304, 512)):
     hook(0, None)
     st = stamps.cpu().numpy()[:3 * grid].reshape(grid, 3)
     st = st[st[:, 2] > 0]
+    # the bf16x6 variant of the 8-wave kernel (csrc/linear_sk_x6.hip, yolat_linear_sk_x6): same tiles, products on the bf16 MFMA
+    Y6 = torch.empty(M, N, device="cuda")
+    run8, run = run, lambda Y: ops.linear_sk_x6(A, lin.weight.detach(), lin.bias.detach(), Y)
+    hook(0, None)
+    t6 = timed(Y6)
+    stamps6 = torch.zeros(3 * grid + 8, dtype=torch.int64, device="cuda")
+    hook(0, stamps6.data_ptr())
+    run(Y6)
+    torch.cuda.synchronize()
+    hook(0, None)
+    run = run8
+    s6 = stamps6.cpu().numpy()[:3 * grid].reshape(grid, 3)
+    s6 = s6[s6[:, 2] > 0]
+    ref = (A.double() @ lin.weight.detach().double().t() + lin.bias.detach().double())
+    nch = K // 128
+    print("   8-wave LDS-DMA bf16x6 variant: %.2f us (fp32 8-wave %.2f us) | max |err| vs fp64: x6 %.3e, fp32 MFMA %.3e of scale %.3e | "
+          "per workgroup: waiting for tiles %.0f cycles, reads + split + MFMA %.0f, whole K loop %.0f = %.0f per chunk (fp32 8-wave: "
+          "%.0f / %.0f / %.0f = %.0f per chunk)"
+          % (t6, t8, float((Y6.double() - ref).abs().max()), float((Y8.double() - ref).abs().max()), float(ref.abs().max()),
+             s6[:, 0].mean(), s6[:, 1].mean(), s6[:, 2].mean(), s6[:, 2].mean() / nch,
+             st[:, 0].mean(), st[:, 1].mean(), st[:, 2].mean(), st[:, 2].mean() / nch))
     print("M=%d K=%d N=%d (%d workgroups): VGPR-staged %.2f us | LDS-DMA %.2f us | bit-identical %s | 8-wave DMA variant per workgroup: "
           "waiting for tiles %.0f cycles, MFMA + reads %.0f, whole K loop %.0f (%d chunks)"
           % (M, K, N, grid, t0, t1, bool(torch.equal(Y0, Y1)), st[:, 0].mean() if len(st) else -1, st[:, 1].mean() if len(st) else -1,

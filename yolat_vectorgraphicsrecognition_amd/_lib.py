@@ -191,6 +191,7 @@ SIGNATURES = {
     "yolat_linear_fwd": (c_int, [c_p, c_i64, c_i64, c_i64, c_p, c_p, c_int,
                                  c_p, c_i64, c_p, c_i64, c_p, c_p, c_int,
                                  c_p, c_i64, c_int, c_p, c_p]),
+    "yolat_linear_sk_x6": (c_int, [c_p, c_i64, c_i64, c_i64, c_p, c_i64, c_p, c_i64, c_p, c_p, c_int, c_p, c_i64, c_p]),
     "yolat_linear_segmax_fwd": (c_int, [c_p, c_i64, c_i64, c_i64, c_p, c_i64, c_p, c_i64, c_p, c_p, c_p, c_p, c_i64,
                                         c_p]),
     "yolat_linear_fwd_wt": (c_int, [c_p, c_i64, c_i64, c_i64, c_p, c_i64, c_i64, c_p, c_i64, c_int, c_p]),

@@ -400,10 +400,17 @@ static int forward_eval_impl(const yolat_model_eval* m, const float* x, int64_t 
   // the bf16x6 GEMM wins once there are enough 128-row tiles to run without a deep K split (measured: P = 2000
   // 41 vs 58 us, P = 8000 129 vs 187 us; P = 400: 21 us either way — profiles/r02_gemm_x6_cls1.txt)
   const bool cls1_gx = m->Wc1_gx && m->tc1_gx && ZW % 16 == 0 && P >= YOLAT_CLS1_X6_MIN_ROWS;
+  // few proposals, nothing pre-split: the shape yolat_linear_fwd sends to the LDS-DMA split-K kernel (dense.hip
+  // launch_gemm_nt) runs the same tiles with the products on the bf16 matrix cores (linear_sk_x6.hip).
+  // YOLAT_CLS1_SK_X6=0: the fp32-input MFMA kernel, as YOLAT_STRICT_FP32=1 selects it.
+  static const bool sk_x6_on = []() { const char* v = getenv("YOLAT_CLS1_SK_X6"); return !(v && v[0] == '0'); }();
+  const bool cls1_sk = sk_x6_on && !cls1_gx && !cls_x6 && !yl_strict_fp32() && ZW >= 1024 && ZW % 128 == 0 &&
+                       (long)yl_cdiv(P, 64) * yl_cdiv(m->H1, 64) < 160 && yl_aligned16(p.Z) && yl_aligned16(m->Wc1);
   snprintf(nm, sizeof nm, "cls1[P x %ld -> %ld]", ZW, (long)m->H1);
   YL_STAGE(nm, 2.0 * P * ZW * m->H1, 4.0 * (P * ZW + ZW * m->H1 + P * m->H1),
            cls1_gx ? yolat_gemm_x6(p.Z, ZW, P, ZW, m->Wc1_gx, m->tc1_gx, 1, m->H1, p.c1, m->H1, p.gx_work, stream)
            : cls_x6 ? cls1_x6(p.Z, ZW, P, p.Zs, m->Wc_x6[0], m->tc_fold[0], m->H1, p.c1, stream)
+           : cls1_sk ? yolat_linear_sk_x6(p.Z, ZW, P, ZW, m->Wc1, ZW, m->bc1, m->H1, m->sc1, m->tc1, 1, p.c1, m->H1, stream)
                   : yolat_linear_fwd(p.Z, ZW, P, ZW, nullptr, nullptr, 0, m->Wc1, ZW, m->bc1, m->H1, m->sc1, m->tc1, 1,
                                      p.c1, m->H1, 0, nullptr, stream));
   snprintf(nm, sizeof nm, "cls2[P x %ld -> %ld]", (long)m->H1, (long)m->H2);

@@ -377,6 +377,18 @@ def linear_fwd(A, W, bias, Y, a_pro=None, a_relu=False, o_pro=None, o_relu=False
     return Y
 
 
+def linear_sk_x6(A, W, bias, Y, o_pro=None, o_relu=False):
+    """Y = epi(A @ W.T + bias) on the LDS-DMA split-K kernel with bf16x6-emulated products (csrc/linear_sk_x6.hip): few
+    rows x long K, K % 128 == 0, 16-byte aligned rows.  Outside its shapes the library's error is raised."""
+    M, K = A.shape
+    Nout = W.shape[0]
+    osc, osh = (o_pro if o_pro is not None else (None, None))
+    check(lib.yolat_linear_sk_x6(_f(A, "A"), _ld(A), M, K, _f(W, "W"), _ld(W), _f(bias, "bias", True), Nout,
+                                 _f(osc, "o_scale", True), _f(osh, "o_shift", True), int(o_relu), _f(Y, "Y"), _ld(Y),
+                                 _stream()), "yolat_linear_sk_x6")
+    return Y
+
+
 def linear_fwd_wt(A, Wt, Y, accumulate=False):
     """Y = A @ Wt   (Wt: [K, Nout] row-major, e.g. dX = dY @ W)."""
     M, K = A.shape
