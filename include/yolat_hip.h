@@ -131,6 +131,12 @@ int yolat_graph_prepare(const int64_t* edge, int64_t stride_e, int64_t stride_c,
  * floor) and csr_wgs + other_wgs <= 250; within that, rows = 100 where the grid allows it, else the fewest rows that fit.
  * YOLAT_PREP_R / YOLAT_PREP_SMALL are honoured as in the launch itself. */
 int yolat_graph_prepare_plan(int64_t N, int64_t E, int64_t other_wgs, int32_t* rows, int32_t* csr_wgs);
+/* The same plan per launch regime of the eval forward (yolat_eval_regime_observe): regime 0 (latency, one forward at a
+ * time) is yolat_graph_prepare_plan; regime 1 (throughput, several forwards in flight) aims at rows = 250 under the same
+ * limits (40 CSR workgroups at N = 10 000 / E = 40 000), which holds fewer CUs per forward.  The arrays built are the same
+ * at every `rows`.  Any other regime: returns 0. */
+int yolat_graph_prepare_plan_regime(int64_t N, int64_t E, int64_t other_wgs, int regime, int32_t* rows,
+                                    int32_t* csr_wgs);
 
 /* dst[r, 0:width] = src[idx[r], 0:width]  (e_attr -> CSR order; fp32)                           */
 int yolat_gather_rows(const float* src, int64_t ld_src, const int32_t* idx, int64_t rows,
@@ -345,6 +351,17 @@ int yolat_edge_uv_mlp2_mean_eval_variant(const float* UV, int64_t ld_uv, const i
                                          const float* t1, const float* W2, const float* b2, const float* s2,
                                          const float* t2, int64_t C, float* f_out, int64_t ld_fo, int variant,
                                          yolat_stream_t stream);
+/* YOLAT_EDGE_TILES with `tiles_per_wg` consecutive node tiles per workgroup (1 .. YOLAT_EDGE_MT_MAX).  1 launches the
+ * one-tile kernel.  More: where the tiles hold <= 16 nodes, a workgroup stages W2 and the per-column constants once and
+ * has the next tile's row_ptr range and first edge ids on their way while the current tile computes; every tile's
+ * arithmetic is the one-tile kernel's in its order, so f_out is bit-identical.  With tiles of more than 16 nodes the
+ * argument has no effect.  (The eval forward uses it when several forwards are in flight: yolat_eval_regime_*.)      */
+#define YOLAT_EDGE_MT_MAX 16
+int yolat_edge_uv_mlp2_mean_eval_mt(const float* UV, int64_t ld_uv, const int32_t* src_csr, const int32_t* dst_csr,
+                                    const float* attr_csr, const int32_t* row_ptr, int64_t N, int64_t E,
+                                    const float* Wc4, const float* b1, const float* s1, const float* t1,
+                                    const float* W2, const float* b2, const float* s2, const float* t2, int64_t C,
+                                    float* f_out, int64_t ld_fo, int tiles_per_wg, yolat_stream_t stream);
 int yolat_edge_uv_mlp2_eval(const float* UV, int64_t ld_uv, const int32_t* src_csr, const int32_t* dst_csr,
                             const float* attr_csr, int64_t E, const float* Wc4, const float* b1, const float* s1,
                             const float* t1, const float* W2, const float* b2, const float* s2, const float* t2,
@@ -575,6 +592,27 @@ int yolat_forward_eval_primed(const yolat_model_eval* m, const float* x, int64_t
                               const int64_t* bbox_idx, int64_t N, int64_t E, int64_t P, float* logits,
                               int64_t ld_logits, void* workspace, size_t workspace_bytes, int32_t* status,
                               yolat_stream_t stream);
+
+/* The launch regime of yolat_forward_eval / _primed / _csr.  The forward's launch shapes were chosen one forward at a time;
+ * with several forwards in flight on several streams other shapes of the same kernels hold fewer CUs for less time (fewer,
+ * fatter CSR workgroups: yolat_graph_prepare_plan_regime; several node tiles per workgroup in the small-graph edge launches:
+ * yolat_edge_uv_mlp2_mean_eval_mt).  Every shape computes bit-identical results: the regime never changes an output.
+ * A process-global, thread-safe gauge records which stream each forward was enqueued on and when (host steady clock; no
+ * HIP call, so it is legal during stream capture).  A forward takes the THROUGHPUT regime (1) when at least 3 distinct
+ * streams, its own included, enqueued a forward within the last 1 ms, else the LATENCY regime (0): exactly the launches of
+ * a single forward.  A hipGraph capture records whichever regime the gauge returned at capture time; every replay runs it.
+ *   yolat_eval_regime_observe  records (stream_key, now_ns) and returns the regime; the forward calls it with its stream
+ *                              handle and clock, tests with synthetic ones.  The table holds 64 streams; a full table
+ *                              forgets the one seen longest ago.
+ *   yolat_eval_regime_set/get  mode 0 auto (default), 1 latency, 2 throughput.  YOLAT_EVAL_REGIME=auto|latency|throughput
+ *                              (read once per process) sets the initial mode; yolat_eval_regime_set wins over it.
+ *   yolat_eval_regime_counts   out[0] / out[1]: forwards enqueued in the latency / throughput regime since load.
+ * YOLAT_EVAL_REGIME_STREAMS / YOLAT_EVAL_REGIME_WINDOW_US (read once) replace the 3 streams / 1000 us, and YOLAT_EDGE_MT=<T>
+ * the tiles per workgroup of the throughput regime's edge launches (1: the one-tile kernel): measurements only. */
+int yolat_eval_regime_observe(uint64_t stream_key, uint64_t now_ns);
+int yolat_eval_regime_set(int mode);
+int yolat_eval_regime_get(void);
+int yolat_eval_regime_counts(int64_t out[2]);
 
 /* ------------------------------------------------------------------------------------------
  * Batch hand-over as native host code (collate.hip).  Reference: collate (cad_recognition/train.py:

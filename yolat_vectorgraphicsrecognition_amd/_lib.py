@@ -173,6 +173,8 @@ SIGNATURES = {
                                               c_p, c_p, c_i64, c_p, c_i64, c_p]),
     "yolat_edge_uv_mlp2_mean_eval_variant": (c_int, [c_p, c_i64, c_p, c_p, c_p, c_p, c_i64, c_i64, c_p, c_p, c_p, c_p,
                                                       c_p, c_p, c_p, c_p, c_i64, c_p, c_i64, c_int, c_p]),
+    "yolat_edge_uv_mlp2_mean_eval_mt": (c_int, [c_p, c_i64, c_p, c_p, c_p, c_p, c_i64, c_i64, c_p, c_p, c_p, c_p,
+                                                 c_p, c_p, c_p, c_p, c_i64, c_p, c_i64, c_int, c_p]),
     "yolat_edge_uv_sums": (c_int, [c_p, c_i64, c_p, c_p, c_p, c_i64, c_i64, c_p, c_i64, c_p]),
     "yolat_conv_merge_dw1": (c_int, [c_p, c_p, c_i64, c_i64, c_p, c_i64, c_int, c_p]),
     "yolat_fusion_pair_eval": (c_int, [c_p, c_i64, c_i64, c_i64, c_p, c_p, c_p, c_p, c_i64, c_p, c_p, c_i64, c_p, c_i64,
@@ -186,6 +188,11 @@ SIGNATURES = {
     "yolat_graph_prepare": (c_int, [c_p, c_i64, c_i64, c_p, c_p, c_i64, c_i64, c_i64, c_p, c_p, c_p, c_p, c_p,
                                     c_p, c_p, c_p, c_p, c_p]),
     "yolat_graph_prepare_plan": (c_int, [c_i64, c_i64, c_i64, c_p, c_p]),
+    "yolat_graph_prepare_plan_regime": (c_int, [c_i64, c_i64, c_i64, c_int, c_p, c_p]),
+    "yolat_eval_regime_observe": (c_int, [ctypes.c_uint64, ctypes.c_uint64]),
+    "yolat_eval_regime_set": (c_int, [c_int]),
+    "yolat_eval_regime_get": (c_int, []),
+    "yolat_eval_regime_counts": (c_int, [c_p]),
     "yolat_gather_rows": (c_int, [c_p, c_i64, c_p, c_i64, c_i64, c_p, c_i64, c_p]),
     "yolat_bn_stats_elems": (c_sz, [c_i64, c_i64]),
     "yolat_linear_fwd": (c_int, [c_p, c_i64, c_i64, c_i64, c_p, c_p, c_int,

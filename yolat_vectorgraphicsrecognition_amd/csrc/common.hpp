@@ -950,13 +950,14 @@ struct EdgeNext {
 // 0: the automatic choice is not the node-tile kernel; 1 / 4: node tiles with <= 16 / <= 64 nodes (edge.hip)
 int yl_edge_tile_groups(int64_t N, int64_t E);
 // yolat_edge_uv_mlp2_mean_eval_variant with an optional rider / next-layer node side (edge.hip): *rode = 1 when the
-// launched kernel carried the rider, *did_next = 1 when it computed `next`
+// launched kernel carried the rider, *did_next = 1 when it computed `next`; tiles_per_wg > 1: the several-tiles-per-workgroup
+// kernel where the tiles hold <= 16 nodes (the throughput regime's shape, same results)
 int yl_edge_uv_mlp2_mean_eval_impl(const float* UV, int64_t ld_uv, const int32_t* src_csr, const int32_t* dst_csr,
                                    const float* attr_csr, const int32_t* row_ptr, int64_t N, int64_t E, const float* Wc4,
                                    const float* b1, const float* s1, const float* t1, const float* W2, const float* b2,
                                    const float* s2, const float* t2, int64_t C, float* f_out, int64_t ld_fo, int variant,
                                    const PoolRider* rider, int* rode, const EdgeNext* next, int* did_next,
-                                   yolat_stream_t stream);
+                                   yolat_stream_t stream, int tiles_per_wg = 1);
 // yolat_fusion_pair_eval_x6 with an optional rider (fusion_x6.hip)
 int yl_fusion_pair_eval_x6_impl(const float* A, int64_t lda, int64_t N, int64_t D, const uint16_t* Wh, const uint16_t* Wm,
                                 const uint16_t* Wl, const float* tfold, int64_t F, const int32_t* node_seg, float* pool,
@@ -983,11 +984,16 @@ int yl_local_prep(const int64_t* edge, int64_t se, int64_t sc, const int64_t* bb
                   int32_t* seg_ptr, int32_t* node_seg, int32_t* eptr, int32_t* status, int32_t* info, bool vouched,
                   hipStream_t st);
 
-// yolat_graph_prepare with an optional co-scheduled node-side GEMM set (graph.hip)
+// The launch regime of the fp32 eval forward (forward_eval.hip, yolat_eval_regime_observe): one forward at a time, or
+// several in flight on several streams.  Every shape a regime selects computes bit-identical results.
+#define YL_REGIME_LATENCY 0
+#define YL_REGIME_THROUGHPUT 1
+// yolat_graph_prepare with an optional co-scheduled node-side GEMM set (graph.hip); `regime` plans k_prep_small
 int yl_graph_prepare_impl(const int64_t* edge, int64_t stride_e, int64_t stride_c, const float* e_attr,
                           const int64_t* bbox_idx, int64_t E, int64_t N, int64_t P, int32_t* row_ptr, int32_t* perm,
                           int32_t* src_csr, int32_t* dst_csr, float* attr_csr, int32_t* seg_ptr, int32_t* node_seg,
-                          int32_t* work, int32_t* status, const NodeUv* extra, bool primed, yolat_stream_t stream);
+                          int32_t* work, int32_t* status, const NodeUv* extra, bool primed, yolat_stream_t stream,
+                          int regime = YL_REGIME_LATENCY);
 // tile y of row tile x: y = 0,1 -> UV halves, 2 -> root Linear, 3 -> node-branch Linear
 template <int BK>
 __device__ __forceinline__ void node_uv_tile(const NodeUv& a, int x, int y) {

@@ -532,6 +532,311 @@ __global__ void __launch_bounds__(256, NG == 1 ? 4 : 1) k_edge_uv_mlp2_mean(cons
 #endif
 }
 
+// ---- the phases of a node tile of k_edge_uv_mlp2_mean<1, *> above as inlined functions, for k_edge_mt_uv_mlp2_mean below:
+// statement for statement that kernel's loads, products, sums and roundings, in its order.  (The one-tile kernel keeps its
+// own body: routed through these functions it computes the same values but is scheduled differently — other registers,
+// other instruction order — and measured 0.2-0.3 % slower one forward at a time, outside the spread of the unchanged code;
+// the latency regime has to stay exactly what it was.  tests/test_gpu_eval_regime.py holds the two bit-equal.)
+constexpr int EDGE_LDH = 65;
+// per-thread constants of layer 1 (gather role: columns 4q..4q+3)
+struct EdgeL1 { float4 wc[4]; float4 bb, sc, sh; };
+__device__ __forceinline__ void edge_l1_consts(EdgeL1& k, const float* __restrict__ Wc4, const float* __restrict__ b1,
+                                               const float* __restrict__ s1, const float* __restrict__ t1, int q) {
+#pragma unroll
+  for (int j = 0; j < 4; ++j) k.wc[j] = *reinterpret_cast<const float4*>(Wc4 + (4 * q + j) * 4);
+  k.bb = b1 ? *reinterpret_cast<const float4*>(b1 + 4 * q) : make_float4(0.f, 0.f, 0.f, 0.f);
+  k.sc = make_float4(1.f, 1.f, 1.f, 1.f); k.sh = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (s1) { k.sc = *reinterpret_cast<const float4*>(s1 + 4 * q); k.sh = *reinterpret_cast<const float4*>(t1 + 4 * q); }
+}
+// W2 -> registers (issued early) -> LDS
+__device__ __forceinline__ void edge_w2_load(const DenseOp& W2, int tid, float (&rw2)[4][4]) {
+#pragma unroll
+  for (int t = 0; t < 4; ++t) {
+    const int i = tid + t * 256;
+    W2.template load4<false>(i >> 4, 4 * (i & 15), rw2[t]);
+  }
+}
+__device__ __forceinline__ void edge_w2_store(float* W2s, int tid, const float (&rw2)[4][4]) {
+#pragma unroll
+  for (int t = 0; t < 4; ++t) {
+    const int i = tid + t * 256;
+    float* d = W2s + (i >> 4) * EDGE_LDH + 4 * (i & 15);
+    d[0] = rw2[t][0]; d[1] = rw2[t][1]; d[2] = rw2[t][2]; d[3] = rw2[t][3];
+  }
+}
+// one 64-edge pass, gather role: rows rb + 16 t of the pass that starts at edge c0 -> layer-1 activations in Hs
+__device__ __forceinline__ void edge_gather_layer1(const float* __restrict__ UV, long ld_uv, const float* __restrict__ attr,
+                                                   int c0, int E, int rb, int q, const int (&di)[4], const int (&si)[4],
+                                                   const EdgeL1& k, float* Hs) {
+  float4 u[4], v[4], a[4];
+#pragma unroll
+  for (int t = 0; t < 4; ++t) {
+    const int e = yl_min(c0 + rb + 16 * t, E - 1);
+    u[t] = *reinterpret_cast<const float4*>(UV + (long)di[t] * ld_uv + 4 * q);
+    v[t] = *reinterpret_cast<const float4*>(UV + (long)si[t] * ld_uv + 64 + 4 * q);
+    a[t] = *reinterpret_cast<const float4*>(attr + (long)e * 4);
+  }
+#pragma unroll
+  for (int t = 0; t < 4; ++t) {
+    auto one = [&](float uu, float vv, const float4& w, float b, float s, float h) {
+      float z = uu + vv;
+      z = fmaf(a[t].x, w.x, z); z = fmaf(a[t].y, w.y, z); z = fmaf(a[t].z, w.z, z); z = fmaf(a[t].w, w.w, z);
+      return fmaxf(fmaf(z + b, s, h), 0.f);
+    };
+    float* hrow = Hs + (rb + 16 * t) * EDGE_LDH + 4 * q;
+    hrow[0] = one(u[t].x, v[t].x, k.wc[0], k.bb.x, k.sc.x, k.sh.x);
+    hrow[1] = one(u[t].y, v[t].y, k.wc[1], k.bb.y, k.sc.y, k.sh.y);
+    hrow[2] = one(u[t].z, v[t].z, k.wc[2], k.bb.z, k.sc.z, k.sh.z);
+    hrow[3] = one(u[t].w, v[t].w, k.wc[3], k.bb.w, k.sc.w, k.sh.w);
+  }
+}
+// the 64 x 64 x 64 product of the two LDS tiles, k ascending in pairs: this wave's 32 x 32 quarter
+__device__ __forceinline__ f32x16 edge_mfma_tile(const float* Hs, const float* W2s, int wm, int wn, int l31, int lhi) {
+  f32x16 acc;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+#pragma unroll 8
+  for (int kk = 0; kk < 64; kk += 2) {
+    const float av = Hs[(wm * 32 + l31) * EDGE_LDH + kk + lhi];
+    const float bv = W2s[(wn * 32 + l31) * EDGE_LDH + kk + lhi];
+    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, acc, 0, 0, 0);
+  }
+  return acc;
+}
+// layer 2's bias / BatchNorm / ReLU -> the pass's messages in Hs
+__device__ __forceinline__ void edge_store_messages(const f32x16& acc2, float* Hs, int wm, int lhi, int col, float bias2,
+                                                    float sc2, float sh2) {
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const int row = wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * lhi;
+    Hs[row * EDGE_LDH + col] = fmaxf(fmaf(acc2[r] + bias2, sc2, sh2), 0.f);
+  }
+}
+// aggregation role: rows of node rb + 16 j inside the pass [c0, c0 + 64), ascending edge order
+template <int NG>
+__device__ __forceinline__ void edge_aggregate(const float* Hs, int c0, int rb, int q, int nn, const int (&my_b)[NG],
+                                               const int (&my_e)[NG], float4 (&sum)[NG]) {
+#pragma unroll
+  for (int j = 0; j < NG; ++j) {
+    if (rb + 16 * j < nn) {
+      const int lo = my_b[j] > c0 ? my_b[j] : c0;
+      const int hi = my_e[j] < c0 + 64 ? my_e[j] : c0 + 64;
+      for (int e = lo; e < hi; ++e) {
+        const float* m = Hs + (e - c0) * EDGE_LDH + 4 * q;
+        sum[j].x += m[0]; sum[j].y += m[1]; sum[j].z += m[2]; sum[j].w += m[3];
+      }
+    }
+  }
+}
+// f_out[n] = sum / deg + root term (fo: the rows loaded earlier; holds the final rows afterwards)
+template <int NG>
+__device__ __forceinline__ void edge_mean_out(float* f_out, long ld_fo, int n0, int rb, int q, int nn, const int (&my_b)[NG],
+                                              const int (&my_e)[NG], const float4 (&sum)[NG], float4 (&fo)[NG]) {
+#pragma unroll
+  for (int j = 0; j < NG; ++j) {
+    const int deg = my_e[j] - my_b[j];
+    if (rb + 16 * j < nn && deg > 0) {
+      const float inv = 1.f / (float)deg;
+      float4* o = reinterpret_cast<float4*>(f_out + (long)(n0 + rb + 16 * j) * ld_fo + 4 * q);
+      float4 d = fo[j];                                // this workgroup is the only writer of its nodes' rows
+      // explicit mul then add (no fma contraction): the same two roundings as k_csr_mean_fwd*
+      d.x = yl_mul_rn(sum[j].x, inv) + d.x; d.y = yl_mul_rn(sum[j].y, inv) + d.y;
+      d.z = yl_mul_rn(sum[j].z, inv) + d.z; d.w = yl_mul_rn(sum[j].w, inv) + d.w;
+      *o = d;
+      fo[j] = d;
+    }
+  }
+}
+// s'[r0 .. r0+63] = relu(((s . Wn'^T) + bn') * sn' + tn'): one 64 x 64 x 64 tile on the same LDS tiles and the same
+// MFMA loop (k ascending in pairs) as layer 2 — bit-identical to k_gemm_nt_node3's tile
+__device__ __forceinline__ void edge_s_tile(const EdgeNext& nx, int N, int r0, float* Hs, float* W2s, int tid, int wm, int wn,
+                                            int l31, int lhi) {
+#pragma unroll
+  for (int t = 0; t < 4; ++t) {
+    const int i = tid + t * 256, row = i >> 4, c4 = 4 * (i & 15);
+    const float4 av = *reinterpret_cast<const float4*>(nx.s_in + (long)yl_min(r0 + row, N - 1) * nx.ld_si + c4);
+    const float4 wv = *reinterpret_cast<const float4*>(nx.Wn + row * 64 + c4);
+    float* da = Hs + row * EDGE_LDH + c4;
+    float* dw = W2s + row * EDGE_LDH + c4;
+    da[0] = av.x; da[1] = av.y; da[2] = av.z; da[3] = av.w;
+    dw[0] = wv.x; dw[1] = wv.y; dw[2] = wv.z; dw[3] = wv.w;
+  }
+  const int colS = wn * 32 + l31;
+  const float bS = nx.bn ? nx.bn[colS] : 0.f, scS = nx.sn[colS], shS = nx.tn[colS];
+  __syncthreads();
+  const f32x16 accS = edge_mfma_tile(Hs, W2s, wm, wn, l31, lhi);
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const int row = r0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * lhi;
+    if (row < N) nx.s_out[(long)row * nx.ld_so + colS] = fmaxf(fmaf(accS[r] + bS, scS, shS), 0.f);
+  }
+}
+// node side of the NEXT layer for one tile's nodes (EdgeNext, common.hpp): [nn <= 16, 64] x [192, 64]^T.  Hs must be free
+// (the pass loop ended with a barrier, or never ran); fz = the thread's final f_out columns of node rb.
+__device__ __forceinline__ void edge_next_node_side(const EdgeNext& nx, int n0, int nn, int rb, int q, int wave, int lane,
+                                                    const float4& fo0, float* Hs) {
+  // the first column tile's B fragments are fetched here, after the pass loop, and the other two under the previous
+  // tile's MFMAs: held from before the first barrier they cost 16 registers through the whole edge phase, which put
+  // the kernel over the 128 of four workgroups per CU
+  float bfa[16], bfb[16];
+#pragma unroll
+  for (int ks = 0; ks < 16; ++ks) bfa[ks] = nx.Wp[(wave * 16 + ks) * 64 + lane];
+  // rows >= nn hold the clamped load of row N-1 or stale sums — finite or not, their products only reach output rows
+  // that are never stored
+  float* frow = Hs + rb * EDGE_LDH + 4 * q;
+  const float4 fz = (rb < nn) ? fo0 : make_float4(0.f, 0.f, 0.f, 0.f);
+  frow[0] = fz.x; frow[1] = fz.y; frow[2] = fz.z; frow[3] = fz.w;
+  __syncthreads();
+  const int fr = lane & 15, fk = lane >> 4;
+#pragma unroll
+  for (int t = 0; t < 3; ++t) {
+    const int ct = wave + 4 * t;                   // 12 column tiles of 16: UV' 0..7, root' 8..11
+    if (t < 2) {
+#pragma unroll
+      for (int ks = 0; ks < 16; ++ks) bfb[ks] = nx.Wp[((ct + 4) * 16 + ks) * 64 + lane];
+    }
+    const int col = ct * 16 + fr;
+    const float bias = nx.bias[col];
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int ks = 0; ks < 16; ++ks)
+      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(Hs[fr * EDGE_LDH + 4 * ks + fk], bfa[ks], acc, 0, 0, 0);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int row = 4 * fk + r;
+      if (row < nn) {
+        const float v = acc[r] + bias;
+        if (col < 128) nx.UV[(long)(n0 + row) * nx.ld_uv + col] = v;
+        else nx.root[(long)(n0 + row) * nx.ld_root + (col - 128)] = v;
+      }
+    }
+#pragma unroll
+    for (int ks = 0; ks < 16; ++ks) bfa[ks] = bfb[ks];
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
+// Several node tiles per workgroup (the THROUGHPUT regime of the eval forward, forward_eval.hip; NG == 1 shapes only).
+// Under load a tile workgroup holds a quarter of a CU for as long as it lives, and 3.0-3.7 us of the 13.8 / 9.5 us of a
+// k_edge_uv_mlp2_mean<1, *> workgroup are its start: the row_ptr -> edge-id round trips and staging the same 16 KB W2
+// into LDS, once per ~14 nodes (profiles/r06_edge_stamps.txt).  Here a workgroup owns T consecutive tiles: W2, Wc4, the
+// folded vectors and layer 2's constants are loaded once, and while tile t runs, the row_ptr range and the first pass's
+// src / dst ids of tile t + 1 are on their way (consecutive tiles own consecutive CSR ranges, so tile t + 1 starts at tile
+// t's end: its 64 dst ids, 64 src ids and 17 row_ptr entries are ONE load per thread, issued at the top of tile t next to
+// that tile's f_out rows, landed with tile t's gathers and parked in the other half of a 2 x 145-int LDS array).  Tiles
+// after the first start at the UV gather.  Per tile every product, sum and rounding is k_edge_uv_mlp2_mean<1, *>'s, in
+// its order (the bodies above): bit-identical results (tests/test_gpu_eval_regime.py).
+// Grid: wgs = ceil(tiles / T) tile workgroups, then the node-branch tiles and the pooling rider as in the one-tile kernel.
+// Bound like it: 256 threads, <= 128 VGPRs, no scratch, 4 x LDS <= 160 KB (tests/test_edge_mt_resources_host.py).
+// ------------------------------------------------------------------------------------------------
+template <bool NEXT>
+__global__ void __launch_bounds__(256, 4) k_edge_mt_uv_mlp2_mean(const float* __restrict__ UV, long ld_uv,
+                                                                 const int* __restrict__ src, const int* __restrict__ dst,
+                                                                 const float* __restrict__ attr,
+                                                                 const int* __restrict__ row_ptr, int N, int npt,
+                                                                 const float* __restrict__ Wc4, const float* __restrict__ b1,
+                                                                 const float* __restrict__ s1, const float* __restrict__ t1,
+                                                                 DenseOp W2, const float* __restrict__ b2,
+                                                                 const float* __restrict__ s2, const float* __restrict__ t2,
+                                                                 float* f_out, long ld_fo, int E, int tiles, int T, int wgs,
+                                                                 PoolRider rider, EdgeNext nx) {
+  if ((int)blockIdx.x >= wgs + nx.s_tiles) {
+    yl_pool_rider(rider, blockIdx.x - wgs - nx.s_tiles, rider.blocks, threadIdx.x, 256);
+    return;
+  }
+  constexpr int LDH = EDGE_LDH;
+  __shared__ float Hs[64 * LDH];
+  __shared__ float W2s[64 * LDH];
+  // a tile's start, written one tile ahead: [0, 64) dst ids and [64, 128) src ids of its first pass, [128, 145) its rp
+  __shared__ int ahead[2][64 + 64 + 17];
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int wm = wave >> 1, wn = wave & 1, l31 = lane & 31, lhi = lane >> 5;
+  if (NEXT && (int)blockIdx.x >= wgs) {
+    edge_s_tile(nx, N, (blockIdx.x - wgs) * 64, Hs, W2s, tid, wm, wn, l31, lhi);
+    return;
+  }
+  const int q = tid & 15, rb = tid >> 4;
+  const int col = wn * 32 + l31;
+  const int tA = blockIdx.x * T, tB = yl_min(tA + T, tiles);   // this workgroup's tiles
+  // this thread's share of the start of the tile at node nA whose edges begin at eA (tid >= 145: nothing)
+  auto start_load = [&](int nA, int eA) -> int {
+    if (tid < 64) return dst[yl_min(eA + tid, E - 1)];
+    if (tid < 128) return src[yl_min(eA + tid - 64, E - 1)];
+    if (tid < 145) return row_ptr[yl_min(nA + tid - 128, nA + yl_min(npt, N - nA))];
+    return 0;
+  };
+  {
+    const int n0 = tA * npt;
+    const int e0g = row_ptr[n0];                      // broadcast load; the ids go out before the barrier below
+    const int st = start_load(n0, e0g);
+    float rw2[4][4];
+    edge_w2_load(W2, tid, rw2);
+    if (tid < 145) ahead[0][tid] = st;
+    edge_w2_store(W2s, tid, rw2);
+  }
+  // the per-column constants of the two layers: loaded from global once.  Without the next layer's node side they stay in
+  // registers through all tiles; with it (32 B-fragment registers per tile) they would not fit the 128 of four workgroups
+  // per CU, so that instance parks them in LDS (2.5 KB) and re-reads them at the top of every tile
+  __shared__ EdgeL1 k1s[NEXT ? 16 : 1];
+  __shared__ float c2s[NEXT ? 3 * 64 : 1];
+  EdgeL1 k1;
+  float bias2, sc2, sh2;
+  if constexpr (NEXT) {
+    if (rb == 0) edge_l1_consts(k1s[q], Wc4, b1, s1, t1, q);
+    if (tid < 64) { c2s[tid] = b2 ? b2[tid] : 0.f; c2s[64 + tid] = s2 ? s2[tid] : 1.f; c2s[128 + tid] = s2 ? t2[tid] : 0.f; }
+  } else {
+    edge_l1_consts(k1, Wc4, b1, s1, t1, q);
+    bias2 = b2 ? b2[col] : 0.f; sc2 = s2 ? s2[col] : 1.f; sh2 = s2 ? t2[col] : 0.f;
+  }
+  for (int t = tA; t < tB; ++t) {
+    // the barrier that publishes ahead[cur] (and W2s for the first tile) and ends the previous tile's use of Hs
+    __syncthreads();
+    if constexpr (NEXT) { k1 = k1s[q]; bias2 = c2s[col]; sc2 = c2s[64 + col]; sh2 = c2s[128 + col]; }
+    const int* cur = ahead[(t - tA) & 1];
+    int* nxt = ahead[(t - tA + 1) & 1];
+    const int n0 = t * npt;
+    const int nn = yl_min(npt, N - n0);
+    const int e0 = cur[128], e1 = cur[128 + nn];
+    int my_b[1], my_e[1];
+    float4 sum[1], fo[1];
+    my_b[0] = cur[128 + yl_min(rb, nn)]; my_e[0] = cur[128 + yl_min(rb + 1, nn)];
+    sum[0] = make_float4(0.f, 0.f, 0.f, 0.f);
+    fo[0] = *reinterpret_cast<const float4*>(f_out + (long)yl_min(n0 + rb, N - 1) * ld_fo + 4 * q);
+    const bool more = t + 1 < tB;
+    int st = 0;
+    if (more) st = start_load(n0 + npt, e1);          // tile t + 1 begins where this one ends
+    if (e0 >= e1 && more && tid < 145) nxt[tid] = st;  // no pass below: park it now (the next top barrier publishes it)
+    for (int c0 = e0; c0 < e1; c0 += 64) {
+      int di[4], si[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        if (c0 == e0) { di[u] = cur[rb + 16 * u]; si[u] = cur[64 + rb + 16 * u]; }
+        else {
+          const int e = yl_min(c0 + rb + 16 * u, E - 1);
+          di[u] = dst[e]; si[u] = src[e];
+        }
+      }
+      edge_gather_layer1(UV, ld_uv, attr, c0, E, rb, q, di, si, k1, Hs);
+      if (c0 == e0 && more && tid < 145) nxt[tid] = st;           // landed with (before) the gathers
+      __syncthreads();
+      const f32x16 acc2 = edge_mfma_tile(Hs, W2s, wm, wn, l31, lhi);
+      __syncthreads();
+      edge_store_messages(acc2, Hs, wm, lhi, col, bias2, sc2, sh2);
+      __syncthreads();
+      edge_aggregate<1>(Hs, c0, rb, q, nn, my_b, my_e, sum);
+      __syncthreads();
+    }
+    edge_mean_out<1>(f_out, ld_fo, n0, rb, q, nn, my_b, my_e, sum, fo);
+    if constexpr (NEXT) {
+      // the B-fragment addresses do not depend on the tile: hoisted out of the tile loop they are 96 registers held through
+      // every edge phase (spills at 128), so they are derived per tile from a lane id the compiler cannot see through
+      int lane_t = lane;
+      asm volatile("" : "+v"(lane_t));
+      edge_next_node_side(nx, n0, nn, rb, q, wave, lane_t, fo[0], Hs);
+    }
+  }
+}
+
 // ------------------------------------------------------------------------------------------------
 // Wave-specialised factorised edge MLP + mean aggregation (round 2) — the large-graph path.
 // Why (profiles/r02_base_fwd_cfg5_pmc_sq_*.txt and the phase ablation in profiles/r02_edge_ablation.txt, cfg 5): the
@@ -898,11 +1203,12 @@ int yl_edge_uv_mlp2_mean_eval_impl(const float* UV, int64_t ld_uv, const int32_t
                                    const float* b1, const float* s1, const float* t1, const float* W2, const float* b2,
                                    const float* s2, const float* t2, int64_t C, float* f_out, int64_t ld_fo, int variant,
                                    const PoolRider* rider, int* rode, const EdgeNext* next, int* did_next,
-                                   yolat_stream_t stream) {
+                                   yolat_stream_t stream, int tiles_per_wg) {
   if (rode) *rode = 0;
   if (did_next) *did_next = 0;
   if (E < 0 || N <= 0 || !UV || !Wc4 || !W2 || !row_ptr || !f_out) return YOLAT_E_INVALID;
   if (variant < YOLAT_EDGE_AUTO || variant > YOLAT_EDGE_WS_X6) return YOLAT_E_INVALID;
+  if (tiles_per_wg < 1 || tiles_per_wg > YOLAT_EDGE_MT_MAX) return YOLAT_E_INVALID;
   if (C != 64) return YOLAT_E_UNSUPPORTED;
   if (E == 0) return 0;
   if (!src_csr || !dst_csr || !attr_csr || E >= (1LL << 31) || ld_fo < C || ld_uv < 2 * C) return YOLAT_E_INVALID;
@@ -950,6 +1256,21 @@ int yl_edge_uv_mlp2_mean_eval_impl(const float* UV, int64_t ld_uv, const int32_t
     nx = *next;
     if (did_next) *did_next = 1;
   }
+  // several tiles per workgroup: only where the one-tile kernel would be an NG == 1 instance; otherwise it is that kernel
+  if (tiles_per_wg > 1 && npt <= 16) {
+    const int wgs = yl_cdiv(tiles, tiles_per_wg);
+    const unsigned mt_grid = (unsigned)wgs + (unsigned)nx.s_tiles + (unsigned)pr.blocks;
+    if (nx.Wp != nullptr)
+      hipLaunchKernelGGL((k_edge_mt_uv_mlp2_mean<true>), dim3(mt_grid), dim3(256), 0, (hipStream_t)stream, UV, (long)ld_uv,
+                         src_csr, dst_csr, attr_csr, row_ptr, (int)N, (int)npt, Wc4, b1, s1, t1, w2, b2, s2, t2, f_out,
+                         (long)ld_fo, (int)E, tiles, tiles_per_wg, wgs, pr, nx);
+    else
+      hipLaunchKernelGGL((k_edge_mt_uv_mlp2_mean<false>), dim3(mt_grid), dim3(256), 0, (hipStream_t)stream, UV, (long)ld_uv,
+                         src_csr, dst_csr, attr_csr, row_ptr, (int)N, (int)npt, Wc4, b1, s1, t1, w2, b2, s2, t2, f_out,
+                         (long)ld_fo, (int)E, tiles, tiles_per_wg, wgs, pr, nx);
+    YL_LAUNCH_CHECK();
+    return 0;
+  }
   const unsigned grid = (unsigned)tiles + (unsigned)nx.s_tiles + (unsigned)pr.blocks;
   if (npt <= 16 && nx.Wp != nullptr)
     hipLaunchKernelGGL((k_edge_uv_mlp2_mean<1, true>), dim3(grid), dim3(256), 0, (hipStream_t)stream, UV, (long)ld_uv,
@@ -975,6 +1296,19 @@ extern "C" int yolat_edge_uv_mlp2_mean_eval_variant(const float* UV, int64_t ld_
                                                     float* f_out, int64_t ld_fo, int variant, yolat_stream_t stream) {
   return yl_edge_uv_mlp2_mean_eval_impl(UV, ld_uv, src_csr, dst_csr, attr_csr, row_ptr, N, E, Wc4, b1, s1, t1, W2, b2, s2,
                                         t2, C, f_out, ld_fo, variant, nullptr, nullptr, nullptr, nullptr, stream);
+}
+
+// The node-tile kernel (YOLAT_EDGE_TILES) with `tiles_per_wg` consecutive tiles per workgroup: 1 is the one-tile kernel,
+// 2 .. YOLAT_EDGE_MT_MAX select k_edge_mt_uv_mlp2_mean where the tiles hold <= 16 nodes (elsewhere the argument has no effect).
+extern "C" int yolat_edge_uv_mlp2_mean_eval_mt(const float* UV, int64_t ld_uv, const int32_t* src_csr,
+                                               const int32_t* dst_csr, const float* attr_csr, const int32_t* row_ptr,
+                                               int64_t N, int64_t E, const float* Wc4, const float* b1, const float* s1,
+                                               const float* t1, const float* W2, const float* b2, const float* s2,
+                                               const float* t2, int64_t C, float* f_out, int64_t ld_fo, int tiles_per_wg,
+                                               yolat_stream_t stream) {
+  return yl_edge_uv_mlp2_mean_eval_impl(UV, ld_uv, src_csr, dst_csr, attr_csr, row_ptr, N, E, Wc4, b1, s1, t1, W2, b2, s2,
+                                        t2, C, f_out, ld_fo, YOLAT_EDGE_TILES, nullptr, nullptr, nullptr, nullptr, stream,
+                                        tiles_per_wg);
 }
 
 extern "C" int yolat_edge_uv_mlp2_mean_eval(const float* UV, int64_t ld_uv, const int32_t* src_csr,

@@ -45,13 +45,14 @@ static int prep_node_uv(const int64_t* edge, int64_t stride_e, int64_t stride_c,
                         const int64_t* bbox_idx, int64_t E, int64_t N, int64_t P, const Plan& p, int32_t* status,
                         const float* x, int64_t ldx, int64_t Cin, const float* Wuv, const float* uv_bias, const float* Wr,
                         const float* br, const float* Wn, const float* bn, const float* sn, const float* tn, int64_t C,
-                        float* f_out, int64_t ld_fo, float* s_out, int64_t ld_so, bool primed, yolat_stream_t stream) {
+                        float* f_out, int64_t ld_fo, float* s_out, int64_t ld_so, bool primed, yolat_stream_t stream,
+                        int regime) {
   NodeUv a;
   const int rc = yl_build_node_uv(&a, x, ldx, x, ldx, N, Cin, Wuv, uv_bias, Wr, br, Wn, bn, sn, tn, C, p.UV, 2 * C, f_out,
                                   ld_fo, s_out, ld_so);
   if (rc != 0) return rc;
   return yl_graph_prepare_impl(edge, stride_e, stride_c, e_attr, bbox_idx, E, N, P, p.row_ptr, p.perm, p.src, p.dst,
-                               p.attr, p.seg_ptr, p.node_seg, p.work, status, &a, primed, stream);
+                               p.attr, p.seg_ptr, p.node_seg, p.work, status, &a, primed, stream, regime);
 }
 
 // ---- stage profiler (hipEvent pairs on the launch stream) ------------------------------------------
@@ -129,6 +130,104 @@ extern "C" int yolat_profile_get(int index, char* name, int cap, float* total_ms
   return 0;
 }
 
+// ---- the regime gauge --------------------------------------------------------------------------------
+// Every launch shape of the forward was chosen one forward at a time, where a launch costs its latency.  With several
+// forwards in flight on several streams the GPU is bound by what the launches RESERVE (workgroups x share of a CU x
+// resident time, DESIGN.md 6 "The loaded regime"), and other shapes win: fewer, fatter CSR workgroups in k_prep_small
+// (graph.hip prep_small_rows) and several node tiles per workgroup in the edge launches (edge.hip
+// k_edge_mt_uv_mlp2_mean).  Every shape gives bit-identical results, so the choice never changes an output.
+// The gauge is a process-global table of (stream, host steady-clock time of its last forward): a forward takes the
+// THROUGHPUT regime when at least K distinct streams enqueued a forward within the last W, itself included, else the
+// LATENCY regime (today's launches, exactly).  No HIP call is made: legal during stream capture — a captured hipGraph
+// replays whichever regime the gauge returned at capture time.
+// K = 3 streams, W = 1 ms (DESIGN.md 6 "The regime gauge": the stream-count sweep behind K; W is ~10 forward durations
+// and > 10x the host's enqueue time of one forward).  YOLAT_EVAL_REGIME_STREAMS / YOLAT_EVAL_REGIME_WINDOW_US (read once)
+// exist for that measurement only.
+#include <atomic>
+#include <chrono>
+#include <mutex>
+#include <string.h>
+namespace {
+constexpr int RG_SLOTS = 64;
+constexpr int RG_STREAMS = 3;
+constexpr uint64_t RG_WINDOW_NS = 1000000ull;
+struct RegimeGauge {
+  std::mutex mu;
+  uint64_t key[RG_SLOTS], seen[RG_SLOTS];
+  bool used[RG_SLOTS];
+};
+RegimeGauge g_gauge{};
+std::atomic<int> g_regime_mode{-1};                    // -1: not set at run time (the environment decides)
+std::atomic<long long> g_regime_counts[2];
+int regime_env_mode() {
+  static const int m = []() {
+    const char* e = getenv("YOLAT_EVAL_REGIME");
+    if (e && !strcmp(e, "latency")) return 1;
+    if (e && !strcmp(e, "throughput")) return 2;
+    return 0;
+  }();
+  return m;
+}
+int regime_streams() {
+  static const int k = []() { const char* e = getenv("YOLAT_EVAL_REGIME_STREAMS"); const int v = e ? atoi(e) : 0;
+                              return v >= 1 ? v : RG_STREAMS; }();
+  return k;
+}
+uint64_t regime_window_ns() {
+  static const uint64_t w = []() { const char* e = getenv("YOLAT_EVAL_REGIME_WINDOW_US"); const long long v = e ? atoll(e) : 0;
+                                   return v >= 1 ? (uint64_t)v * 1000ull : RG_WINDOW_NS; }();
+  return w;
+}
+// node tiles per workgroup in the throughput regime's edge launches: 2 by A/B (3 loses what 2 gains, 4 and more lose to the
+// one-tile kernel: a workgroup's tiles run in sequence and the launch gets longer; profiles/eval_regime_sweep.json).
+// YOLAT_EDGE_MT=<T> forces T (1: the one-tile kernel) for measurement
+constexpr int RG_EDGE_MT = 2;
+int regime_edge_mt() {
+  static const int t = []() { const char* e = getenv("YOLAT_EDGE_MT"); const int v = e ? atoi(e) : 0;
+                              return (v >= 1 && v <= YOLAT_EDGE_MT_MAX) ? v : RG_EDGE_MT; }();
+  return t;
+}
+}  // namespace
+
+extern "C" int yolat_eval_regime_get(void) {
+  const int m = g_regime_mode.load(std::memory_order_relaxed);
+  return m >= 0 ? m : regime_env_mode();
+}
+extern "C" int yolat_eval_regime_set(int mode) {
+  if (mode < 0 || mode > 2) return YOLAT_E_INVALID;
+  g_regime_mode.store(mode, std::memory_order_relaxed);
+  return 0;
+}
+extern "C" int yolat_eval_regime_observe(uint64_t stream_key, uint64_t now_ns) {
+  const uint64_t win = regime_window_ns();
+  int recent = 0;
+  {
+    std::lock_guard<std::mutex> lock(g_gauge.mu);
+    RegimeGauge& t = g_gauge;
+    int slot = -1, spare = -1, oldest = 0;
+    for (int i = 0; i < RG_SLOTS; ++i) {
+      if (t.used[i] && t.key[i] == stream_key) { slot = i; break; }
+      if (!t.used[i]) { if (spare < 0) spare = i; }
+      else if (!t.used[oldest] || t.seen[i] < t.seen[oldest]) oldest = i;
+    }
+    if (slot < 0) slot = spare >= 0 ? spare : oldest;          // a full table forgets the stream seen longest ago
+    t.used[slot] = true; t.key[slot] = stream_key; t.seen[slot] = now_ns;
+    for (int i = 0; i < RG_SLOTS; ++i)
+      // (|now - seen|: two threads may record in the other order than they read the clock)
+      if (t.used[i] && (t.seen[i] >= now_ns ? t.seen[i] - now_ns : now_ns - t.seen[i]) <= win) ++recent;
+  }
+  const int mode = yolat_eval_regime_get();
+  if (mode == 1) return YL_REGIME_LATENCY;
+  if (mode == 2) return YL_REGIME_THROUGHPUT;
+  return recent >= regime_streams() ? YL_REGIME_THROUGHPUT : YL_REGIME_LATENCY;
+}
+extern "C" int yolat_eval_regime_counts(int64_t out[2]) {
+  if (!out) return YOLAT_E_INVALID;
+  out[0] = g_regime_counts[0].load(std::memory_order_relaxed);
+  out[1] = g_regime_counts[1].load(std::memory_order_relaxed);
+  return 0;
+}
+
 // cls1 on the skinny bf16x6 kernel: K = 2304 is long enough that splitting Z once (a small launch) beats splitting it
 // on the fly in each of the H1/32 column tiles
 static int cls1_x6(const float* Z, long ZW, long P, uint16_t* Zs, const uint16_t* Wp, const float* shift, long H1,
@@ -195,6 +294,12 @@ static int forward_eval_impl(const yolat_model_eval* m, const float* x, int64_t 
   Plan p = carve(m, N, E, P, workspace);
   if (p.bytes > workspace_bytes) return YOLAT_E_INVALID;
   if (g != nullptr) YL_TRY(yl_adopt_graph(g, E, &p));      // prepared graph: the kernels read the caller's arrays
+  // which regime this forward is enqueued in (the gauge above): it selects launch shapes, never values
+  const int regime = yolat_eval_regime_observe(
+      (uint64_t)(uintptr_t)stream,
+      (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now().time_since_epoch()).count());
+  g_regime_counts[regime].fetch_add(1, std::memory_order_relaxed);
+  const int edge_mt = regime == YL_REGIME_THROUGHPUT ? regime_edge_mt() : 1;
   const long C = m->C, F = m->F, D = C * m->n_blocks_out, ZW = 2 * (F + D);
   const int lo = m->n_blocks - m->n_blocks_out;
 
@@ -229,11 +334,11 @@ static int forward_eval_impl(const yolat_model_eval* m, const float* x, int64_t 
              16.0 * E + 12.0 * E + 32.0 * E + 12.0 * N + 4.0 * (2.0 * N * cv0.Cin + 4.0 * N * C),
              prep_node_uv(edge, stride_e, stride_c, e_attr, bbox_idx, E, N, P, p, status, x, ldx, cv0.Cin,
                           fold0 ? cv0.Wuvf : cv0.Wuv, fold0 ? cv0.uvb : nullptr, cv0.Wr, cv0.br, cv0.Wn, cv0.bn, cv0.sn,
-                          cv0.tn, C, f0, ld0, s0, ld0, primed, stream));
+                          cv0.tn, C, f0, ld0, s0, ld0, primed, stream, regime));
   } else if (g == nullptr) {
   YL_STAGE("graph_prep[csr+attr+segments]", 0, 16.0 * E + 12.0 * E + 32.0 * E + 12.0 * N,
            yl_graph_prepare_impl(edge, stride_e, stride_c, e_attr, bbox_idx, E, N, P, p.row_ptr, p.perm, p.src,
-                                 p.dst, p.attr, p.seg_ptr, p.node_seg, p.work, status, nullptr, primed, stream));
+                                 p.dst, p.attr, p.seg_ptr, p.node_seg, p.work, status, nullptr, primed, stream, regime));
   }
 
   // ---- pooling prologue (segment.hip k_pool_prepare): a launch of its own for large graphs; for small ones
@@ -321,10 +426,11 @@ static int forward_eval_impl(const yolat_model_eval* m, const float* x, int64_t 
                    fold ? yl_edge_uv_mlp2_mean_eval_impl(uv_l, 2 * C, p.src, p.dst, p.attr, p.row_ptr, N, E, cv.Wc4f,
                                                          nullptr, nullptr, nullptr, cv.W2, nullptr, cv.s2, cv.t2f, C,
                                                          f_out, ld_out, YOLAT_EDGE_AUTO, rd, &rode,
-                                                         nx.Wp ? &nx : nullptr, &did_next, stream)
+                                                         nx.Wp ? &nx : nullptr, &did_next, stream, edge_mt)
                         : yl_edge_uv_mlp2_mean_eval_impl(uv_l, 2 * C, p.src, p.dst, p.attr, p.row_ptr, N, E, cv.Wc4,
                                                          cv.b1, cv.s1, cv.t1, cv.W2, cv.b2, cv.s2, cv.t2, C, f_out,
-                                                         ld_out, YOLAT_EDGE_AUTO, rd, &rode, nullptr, nullptr, stream));
+                                                         ld_out, YOLAT_EDGE_AUTO, rd, &rode, nullptr, nullptr, stream,
+                                                         edge_mt));
           if (rode) pool_done |= ride_a.parts;
           // (had the launch not taken `next`, the following layer's node side runs as its own launch into p.UV,
           // recomputing the node branch the chain already wrote — same values)

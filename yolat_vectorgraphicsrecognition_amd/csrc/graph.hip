@@ -699,12 +699,17 @@ __global__ void __launch_bounds__(PS_T) k_prep_small(PrepSmall g, NodeUv a, int 
 // one at a time, 200 is what "fill 250 CUs" gave until then), and when that grid with the segment / node-side
 // workgroups is more than one round of PS_PLAN_GRID CUs, fewer and fatter workgroups in what is left of the round, as
 // long as they keep R <= PS_RMAX and the edge headroom.
+// That rule is the LATENCY regime's (one forward at a time).  In the THROUGHPUT regime (several forwards in flight, the
+// eval forward's gauge: forward_eval.hip) the row target is PS_PLAN_ROWS_TP = 250 under the same caps: 40 CSR workgroups at
+// cfg 2, the measured +4.4 % under load of profiles/prep_plan_ab.json, whose 1.5 us one at a time no longer matter there.
+// k_prep_small computes the same arrays at every R (tests/test_gpu_prep_plan.py), so the regime never changes a result.
 // YOLAT_PREP_R=<1..PS_RMAX> (read once per process; tests and measurements) forces the rows per workgroup of every graph
-// within the E limit, whatever the grid then is.
+// within the E limit, whatever the grid then is, in both regimes.
 #define PS_PLAN_ROWS 100
+#define PS_PLAN_ROWS_TP 250
 #define PS_PLAN_EDGES (PS_CAP / 2)
 #define PS_PLAN_GRID 250
-static int prep_small_rows(int64_t N, int64_t E, int64_t other_blocks) {
+static int prep_small_rows(int64_t N, int64_t E, int64_t other_blocks, int regime) {
   static const bool on = []() { const char* e = getenv("YOLAT_PREP_SMALL"); return !(e && e[0] == '0'); }();
   static const int forced = []() { const char* e = getenv("YOLAT_PREP_R"); const int r = e ? atoi(e) : 0;
                                    return (r >= 1 && r <= PS_RMAX) ? r : 0; }();
@@ -712,7 +717,8 @@ static int prep_small_rows(int64_t N, int64_t E, int64_t other_blocks) {
   if (forced) return forced;
   int64_t r_edges = E > 0 ? (int64_t)PS_PLAN_EDGES * N / E : PS_RMAX;      // R E / N <= PS_PLAN_EDGES
   if (r_edges < 1) r_edges = 1;                                            // degree > PS_PLAN_EDGES: one row is the floor
-  int64_t R = PS_PLAN_ROWS;
+  int64_t R = regime == YL_REGIME_THROUGHPUT ? PS_PLAN_ROWS_TP : PS_PLAN_ROWS;
+  if (R > PS_RMAX) R = PS_RMAX;
   if (R > r_edges) R = r_edges;
   if (R > N) R = N;
   if ((N + R - 1) / R + other_blocks > PS_PLAN_GRID) {
@@ -724,11 +730,17 @@ static int prep_small_rows(int64_t N, int64_t E, int64_t other_blocks) {
   return (int)R;
 }
 
-extern "C" int yolat_graph_prepare_plan(int64_t N, int64_t E, int64_t other_wgs, int32_t* rows, int32_t* csr_wgs) {
-  const int R = (other_wgs < 0) ? 0 : prep_small_rows(N, E, other_wgs);
+extern "C" int yolat_graph_prepare_plan_regime(int64_t N, int64_t E, int64_t other_wgs, int regime, int32_t* rows,
+                                               int32_t* csr_wgs) {
+  const bool ok = other_wgs >= 0 && (regime == YL_REGIME_LATENCY || regime == YL_REGIME_THROUGHPUT);
+  const int R = ok ? prep_small_rows(N, E, other_wgs, regime) : 0;
   if (rows) *rows = R;
   if (csr_wgs) *csr_wgs = R > 0 ? (int32_t)((N + R - 1) / R) : 0;
   return R > 0 ? 1 : 0;
+}
+
+extern "C" int yolat_graph_prepare_plan(int64_t N, int64_t E, int64_t other_wgs, int32_t* rows, int32_t* csr_wgs) {
+  return yolat_graph_prepare_plan_regime(N, E, other_wgs, YL_REGIME_LATENCY, rows, csr_wgs);
 }
 
 extern "C" size_t yolat_graph_work_elems(int64_t N, int64_t E) {
@@ -739,7 +751,7 @@ int yl_graph_prepare_impl(const int64_t* edge, int64_t stride_e, int64_t stride_
                               const int64_t* bbox_idx, int64_t E, int64_t N, int64_t P, int32_t* row_ptr,
                               int32_t* perm, int32_t* src_csr, int32_t* dst_csr, float* attr_csr, int32_t* seg_ptr,
                               int32_t* node_seg, int32_t* work, int32_t* status, const NodeUv* extra, bool primed,
-                              yolat_stream_t stream) {
+                              yolat_stream_t stream, int regime) {
   if (N <= 0 || E < 0 || N >= (1LL << 31) - 8192 || E >= (1LL << 31) - 256) return YOLAT_E_INVALID;
   if (!row_ptr || !work || !status) return YOLAT_E_INVALID;
   if (E > 0 && (!edge || !e_attr || !perm || !src_csr || !dst_csr || !attr_csr)) return YOLAT_E_INVALID;
@@ -759,7 +771,7 @@ int yl_graph_prepare_impl(const int64_t* edge, int64_t stride_e, int64_t stride_
   // small graphs: everything in ONE launch (k_prep_small), no counters to zero
   const int node_blocks = extra ? yl_cdiv(extra->N, 8 * PS_NW * PS_NODE_ITERS) : 0;
   const int seg_blocks = bbox_idx ? yl_cdiv(N + 1, PS_T) : 0;
-  const int Rs = (extra == nullptr || yl_node3_smallk_shape_ok(*extra)) ? prep_small_rows(N, E, node_blocks + seg_blocks) : 0;
+  const int Rs = (extra == nullptr || yl_node3_smallk_shape_ok(*extra)) ? prep_small_rows(N, E, node_blocks + seg_blocks, regime) : 0;
   if (Rs > 0) {
     PrepSmall g;
     g.edge = edge; g.se = (long)stride_e; g.sc = (long)stride_c; g.attr = reinterpret_cast<const float4*>(e_attr);

@@ -759,6 +759,20 @@ def edge_uv_mlp2_mean_eval(UV, g, wc4, b1, pro1, W2, b2, pro2, f_out, variant=ED
     return f_out
 
 
+def edge_uv_mlp2_mean_eval_mt(UV, g, wc4, b1, pro1, W2, b2, pro2, f_out, tiles_per_wg=1):
+    """edge_uv_mlp2_mean_eval on the node-tile kernel with `tiles_per_wg` consecutive tiles per workgroup
+    (yolat_edge_uv_mlp2_mean_eval_mt; 1 = the one-tile kernel; bit-identical f_out at every value)."""
+    s1, t1 = pro1 if pro1 is not None else (None, None)
+    s2, t2 = pro2 if pro2 is not None else (None, None)
+    check(lib.yolat_edge_uv_mlp2_mean_eval_mt(_f(UV, "UV"), _ld(UV), g.src.data_ptr(), g.dst.data_ptr(),
+                                              g.attr.data_ptr(), g.row_ptr.data_ptr(), g.N, g.E, _f(wc4),
+                                              _f(b1, "b1", True), _f(s1, "s1", True), _f(t1, "t1", True), _f(W2),
+                                              _f(b2, "b2", True), _f(s2, "s2", True), _f(t2, "t2", True),
+                                              W2.shape[0], _f(f_out), _ld(f_out), int(tiles_per_wg), _stream()),
+          "yolat_edge_uv_mlp2_mean_eval_mt")
+    return f_out
+
+
 def edge_mlp2_eval(x, g, W1, b1, pro1, W2, b2, pro2, H2):
     """Eval-mode two-layer edge MLP in one kernel (BN folded into pro1/pro2 = (scale, shift))."""
     N, Cin = x.shape
