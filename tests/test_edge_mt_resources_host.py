@@ -6,51 +6,17 @@ VGPR, no scratch, and four workgroups' LDS inside the CU's 160 KB — for the in
 side and the one that does not.  Compiled and read the way tests/test_kernel_resources_host.py does (hipcc
 --offload-arch=gfx950 -O3 --save-temps, the code object metadata in the device assembly)."""
 import os
-import re
-import shutil
-import subprocess
 
 import pytest
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(REPO, "yolat_vectorgraphicsrecognition_amd", "csrc")
-KEYS = (".vgpr_count", ".vgpr_spill_count", ".private_segment_fixed_size", ".group_segment_fixed_size",
-        ".max_flat_workgroup_size")
-
-
-def find_hipcc():
-    for cand in (os.environ.get("HIPCC"), shutil.which("hipcc"), "/opt/rocm/bin/hipcc"):
-        if cand and os.path.isfile(cand) and os.access(cand, os.X_OK):
-            return cand
-    return None
+from kernel_meta import CSRC, find_hipcc, kernel_resources, one
 
 
 @pytest.fixture(scope="module")
-def resources(tmp_path_factory):
-    hipcc = find_hipcc()
-    if hipcc is None:
+def resources():
+    if find_hipcc() is None:
         pytest.skip("hipcc is not on this machine")
-    work = str(tmp_path_factory.mktemp("kres_mt"))
-    r = subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-c", "--save-temps", "-o",
-                        os.path.join(work, "edge.o"), os.path.join(CSRC, "edge.hip")], cwd=work, capture_output=True,
-                       text=True, timeout=900)
-    assert r.returncode == 0, r.stderr[-4000:]
-    with open(os.path.join(work, "edge-hip-amdgcn-amd-amdhsa-gfx950.s")) as f:
-        text = f.read()
-    out = {}
-    for rec in text[text.index("amdhsa.kernels:"):].split("\n  - ")[1:]:
-        name = re.search(r"^    \.name:\s+(\S+)", rec, re.M)
-        if not name:
-            continue
-        out[name.group(1)] = {k: int(re.search(r"^    %s:\s+(\d+)" % re.escape(k), rec, re.M).group(1)) for k in KEYS}
-    return out
-
-
-def one(resources, prefix):
-    hits = [k for k in resources if k.startswith(prefix)]
-    assert len(hits) == 1, (prefix, hits)
-    print(hits[0][:60], resources[hits[0]])
-    return resources[hits[0]]
+    return kernel_resources(os.path.join(CSRC, "edge.hip"))
 
 
 @pytest.mark.parametrize("inst", ["ILb1EE", "ILb0EE"])

@@ -1078,7 +1078,7 @@ def test_factorised_training_edge_lin1_matches_gathered_gemm(N, E):
 
 @pytest.mark.parametrize("N,E,Cin", [(300, 1000, 64), (50, 31, 64), (2000, 9001, 64), (700, 5000, 5), (4000, 30000, 64)])
 def test_factorised_edge_lin1_backward_matches_gathered_gemms(N, E, Cin):
-    """ops.edge_lin1_bwd_factorised (per-node sums of dH1 + N-row dense algebra, csrc/edge.hip yolat_edge_uv_sums)
+    """ops.edge_lin1_bwd_factorised (per-node sums of dH1 + N-row dense algebra, csrc/edge_ops.hip yolat_edge_uv_sums)
     against the gathered path yolat_edge_lin1_bwd_w / _bwd_x / yolat_edge_scatter_bwd and against float64 autograd of
     the reference formulation cat[x_i, x_j - x_i, attr] @ W1^T (torch_vertex.py:331,335)."""
     yv = _yv()
@@ -1503,7 +1503,7 @@ def test_linear_fwd_gemm_x6_stats_path_matches_fp32_kernel(M, K, N):
 
 @pytest.mark.parametrize("E,half", [(1, False), (63, False), (1000, True), (300001, False), (300001, True)])
 def test_edge_attr_dw_streaming_reduction_matches_fp64(E, half):
-    """yolat_edge_attr_dw (edge.hip k_attr_dw): dWc4 = dH1^T . attr and db1 = column sums of dH1 — the part of the first edge
+    """yolat_edge_attr_dw (edge_ops.hip k_attr_dw): dWc4 = dH1^T . attr and db1 = column sums of dH1 — the part of the first edge
     Linear's weight gradient that reads the edge attributes (torch_vertex.py:331) — against fp64, for fp32 and
     bfloat16-stored gradients, ragged sizes, with and without the bias gradient; run-to-run bit identity."""
     from yolat_vectorgraphicsrecognition_amd._lib import lib, check
@@ -1534,7 +1534,7 @@ def test_edge_attr_dw_streaming_reduction_matches_fp64(E, half):
 @pytest.mark.parametrize("N,E,half", [(1, 1, False), (40, 300, False), (5000, 42001, True), (50000, 300001, False),
                                       (50000, 300001, True), (3000, 2500, False)])
 def test_bn_apply_edge_sums_equals_apply_then_sums(N, E, half):
-    """yolat_bn_apply_edge_sums + yolat_edge_uv_sums_v (edge.hip, round 4) against the three launches they replace —
+    """yolat_bn_apply_edge_sums + yolat_edge_uv_sums_v (edge_ops.hip, round 4) against the three launches they replace —
     yolat_bn_relu_bwd_apply, yolat_edge_uv_sums, yolat_edge_attr_dw (torch_vertex.py:331-332 backward): dH1 and dUV
     BIT-identical (same arithmetic, same ascending row order per node; bf16 storage: sums of the stored values), dWc4 /
     db1 against fp64 of the stored dH1 (their summation order differs from k_attr_dw's).  Skewed in-degrees incl. empty

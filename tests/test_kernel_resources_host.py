@@ -16,67 +16,20 @@ claim needs, not what the compiler happens to give:
 The two translation units are compiled the way tools/kernel_resources.sh does (hipcc --offload-arch=gfx950 -O3
 --save-temps) and the numbers are read from the code objects' metadata in the device assembly."""
 import os
-import re
-import shutil
-import subprocess
 
 import pytest
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(REPO, "yolat_vectorgraphicsrecognition_amd", "csrc")
-KEYS = (".vgpr_count", ".vgpr_spill_count", ".private_segment_fixed_size", ".group_segment_fixed_size",
-        ".max_flat_workgroup_size")
-
-
-def find_hipcc():
-    for cand in (os.environ.get("HIPCC"), shutil.which("hipcc"), "/opt/rocm/bin/hipcc"):
-        if cand and os.path.isfile(cand) and os.access(cand, os.X_OK):
-            return cand
-    return None
-
-
-def kernel_resources(hipcc, src, workdir):
-    """{mangled kernel name: {metadata key: int}} of every kernel of one translation unit"""
-    base = os.path.splitext(os.path.basename(src))[0]
-    r = subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-c", "--save-temps", "-o",
-                        os.path.join(workdir, base + ".o"), src], cwd=workdir, capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stderr[-4000:]
-    asm = os.path.join(workdir, base + "-hip-amdgcn-amd-amdhsa-gfx950.s")
-    assert os.path.isfile(asm), os.listdir(workdir)
-    out = {}
-    with open(asm) as f:
-        text = f.read()
-    # the amdhsa.kernels metadata: one "- .agpr_count: ..." record per kernel, keys in alphabetical order
-    for rec in text[text.index("amdhsa.kernels:"):].split("\n  - ")[1:]:
-        name = re.search(r"^    \.name:\s+(\S+)", rec, re.M)       # (4 spaces: the kernel's, not an argument's)
-        if not name:
-            continue
-        cur = {}
-        for k in KEYS:
-            m = re.search(r"^    %s:\s+(\d+)" % re.escape(k), rec, re.M)
-            assert m, (name.group(1), k)
-            cur[k] = int(m.group(1))
-        out[name.group(1)] = cur
-    return out
+from kernel_meta import CSRC, find_hipcc, kernel_resources, one
 
 
 @pytest.fixture(scope="module")
-def resources(tmp_path_factory):
-    hipcc = find_hipcc()
-    if hipcc is None:
+def resources():
+    if find_hipcc() is None:
         pytest.skip("hipcc is not on this machine")
-    work = str(tmp_path_factory.mktemp("kres"))
     res = {}
     for name in ("edge.hip", "graph.hip"):
-        res.update(kernel_resources(hipcc, os.path.join(CSRC, name), work))
+        res.update(kernel_resources(os.path.join(CSRC, name)))
     return res
-
-
-def one(resources, prefix):
-    hits = [k for k in resources if k.startswith(prefix)]
-    assert len(hits) == 1, (prefix, hits)
-    print(hits[0][:60], resources[hits[0]])
-    return resources[hits[0]]
 
 
 def alloc(vgprs):

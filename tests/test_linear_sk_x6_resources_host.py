@@ -9,15 +9,14 @@ import os
 
 import pytest
 
-from test_kernel_resources_host import CSRC, find_hipcc, kernel_resources, one
+from kernel_meta import CSRC, find_hipcc, kernel_resources, one
 
 
 @pytest.fixture(scope="module")
-def resources(tmp_path_factory):
-    hipcc = find_hipcc()
-    if hipcc is None:
+def resources():
+    if find_hipcc() is None:
         pytest.skip("hipcc is not on this machine")
-    return kernel_resources(hipcc, os.path.join(CSRC, "linear_sk_x6.hip"), str(tmp_path_factory.mktemp("kres_sk_x6")))
+    return kernel_resources(os.path.join(CSRC, "linear_sk_x6.hip"))
 
 
 def test_sk_x6dma_fits_two_workgroups_per_cu(resources):

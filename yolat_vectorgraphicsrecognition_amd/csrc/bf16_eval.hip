@@ -624,13 +624,7 @@ static int yl_edge_uv_mlp2_mean_bf16_impl(const u16* UV, long ld_uv, const int* 
     if (E < 16) return YOLAT_E_UNSUPPORTED;
     return yl_edge_chain_bf16(UV, ld_uv, src, dst, attr, row_ptr, N, E, Wc4, s1, W2f, t2f, root, ld_r, f_out, ld_fo, st, gate);
   }
-  long npt = E > 0 ? (56 * N) / E : 64;
-  {
-    const long npt2 = E > 0 ? ((112 * N) / E < 16 ? (112 * N) / E : 16) : 16;
-    if (npt2 >= 2 * npt - 2 && N / (npt2 > 0 ? npt2 : 1) >= 8192) npt = npt2;
-    if (npt < 1) npt = 1;
-    if (npt > 64) npt = 64;
-  }
+  const long npt = yl_edge_tile_npt(N, E);
   hipLaunchKernelGGL((npt <= 16 ? k_edge_uv_mlp2_mean_h<1> : k_edge_uv_mlp2_mean_h<4>), dim3(yl_cdiv(N, npt)), dim3(256), 0,
                      st, UV, (unsigned)ld_uv, src, dst, attr, row_ptr, (int)N, (int)npt, Wc4, s1, W2f, (const float*)nullptr,
                      (const float*)nullptr, t2f, root, (unsigned)ld_r, f_out, (unsigned)ld_fo, (int)(E > 0 ? E : 1), gate);

@@ -949,6 +949,8 @@ struct EdgeNext {
 };
 // 0: the automatic choice is not the node-tile kernel; 1 / 4: node tiles with <= 16 / <= 64 nodes (edge.hip)
 int yl_edge_tile_groups(int64_t N, int64_t E);
+// nodes per workgroup of the node-tile edge kernels, fp32 and bf16 (edge.hip); 64 for a graph without edges
+long yl_edge_tile_npt(long N, long E);
 // yolat_edge_uv_mlp2_mean_eval_variant with an optional rider / next-layer node side (edge.hip): *rode = 1 when the
 // launched kernel carried the rider, *did_next = 1 when it computed `next`; tiles_per_wg > 1: the several-tiles-per-workgroup
 // kernel where the tiles hold <= 16 nodes (the throughput regime's shape, same results)

@@ -82,6 +82,11 @@ def _is_h(t):
     return t is not None and t.dtype == torch.bfloat16
 
 
+def _fh(t, name="tensor", half=None):
+    """data_ptr of a tensor stored as bfloat16 or fp32: by its own dtype, or checked against the storage `half` names."""
+    return _h(t, name) if (_is_h(t) if half is None else half) else _f(t, name)
+
+
 def _i(t, dtype, name="index"):
     if t is None:
         return None
@@ -475,7 +480,7 @@ def linear_bwd_w(dY, A, dW, db=None, a_pro=None, a_relu=False, accumulate=False)
     work = torch.empty(int(lib.yolat_linear_bwd_w_work_elems(M, Nout, K)), dtype=torch.float32,
                        device=dY.device)
     if _is_h(dY):
-        check(lib.yolat_linear_bwd_w_h(_h(dY, "dY"), _ld(dY), M, Nout, _h(A, "A") if _is_h(A) else _f(A, "A"),
+        check(lib.yolat_linear_bwd_w_h(_h(dY, "dY"), _ld(dY), M, Nout, _fh(A, "A"),
                                        int(_is_h(A)), _ld(A), K, _f(asc, "a_scale", True), _f(ash, "a_shift", True),
                                        int(a_relu), _f(dW, "dW"), _ld(dW), _f(db, "db", True), int(accumulate),
                                        work.data_ptr(), _stream()), "yolat_linear_bwd_w_h")
@@ -502,7 +507,7 @@ class BnCsrGrad(object):
         d.d_out, d.ld_out = _f(d_out, "d_out"), _ld(d_out)
         d.dst, d.inv_deg = g.dst.data_ptr(), g.inv_deg().data_ptr()
         d.half = int(_is_h(Y))
-        d.Y, d.ldy = (_h(Y, "Y") if d.half else _f(Y, "Y")), _ld(Y)
+        d.Y, d.ldy = _fh(Y, "Y"), _ld(Y)
         d.mean, d.invstd, d.scale, d.shift = _f(save_mean), _f(save_invstd), _f(scale), _f(shift)
         d.coef, d.relu = self.coef.data_ptr(), int(relu)
         self._d = d
@@ -537,10 +542,10 @@ class BnCsrGrad(object):
         if next_bn is not None:
             coef1 = torch.empty(2 * self.C, dtype=torch.float32, device=self.dev)
             nm, ni, ng, nb, nc = _f(next_bn[0]), _f(next_bn[1]), _f(next_bn[2]), _f(next_bn[3]), coef1.data_ptr()
-        check(lib.yolat_bn_csr_l2_bwd(ctypes.byref(self._d), self.E, _h(A, "A") if hp else _f(A, "A"), _ld(A),
+        check(lib.yolat_bn_csr_l2_bwd(ctypes.byref(self._d), self.E, _fh(A, "A", hp), _ld(A),
                                       _f(asc, "a_scale", True), _f(ash, "a_shift", True), int(a_relu), _f(W, "W"), _ld(W),
                                       _f(dW, "dW"), _ld(dW), _f(db, "db", True), int(accumulate),
-                                      _h(dA, "dA") if hp else _f(dA, "dA"), _ld(dA), work.data_ptr(), nm, ni, ng, nb, nc,
+                                      _fh(dA, "dA", hp), _ld(dA), work.data_ptr(), nm, ni, ng, nb, nc,
                                       _stream()), "yolat_bn_csr_l2_bwd")
         return coef1
 
@@ -554,9 +559,9 @@ def bn_relu_bwd_apply(dZ, Y, save_mean, save_invstd, scale, shift, relu, coef, d
     """The apply pass of bn_relu_bwd alone, with the coefficient vector [2C] = (c1 | c2) given."""
     M, C = Y.shape
     hp = _is_h(Y)
-    check(lib.yolat_bn_relu_bwd_apply(_h(dZ, "dZ") if hp else _f(dZ, "dZ"), _ld(dZ), _h(Y, "Y") if hp else _f(Y, "Y"), _ld(Y),
+    check(lib.yolat_bn_relu_bwd_apply(_fh(dZ, "dZ", hp), _ld(dZ), _fh(Y, "Y"), _ld(Y),
                                       M, C, _f(save_mean), _f(save_invstd), _f(scale), _f(shift), int(relu), _f(coef),
-                                      _h(dY, "dY") if hp else _f(dY, "dY"), _ld(dY), int(hp), _stream()),
+                                      _fh(dY, "dY", hp), _ld(dY), int(hp), _stream()),
           "yolat_bn_relu_bwd_apply")
     return dY
 
@@ -652,8 +657,8 @@ def bn_apply_edge_sums(dA1, H1, save_mean, save_invstd, scale, shift, relu, coef
     dUV = torch.empty(N, 2 * C, dtype=torch.float32, device=H1.device)
     dwc4 = torch.empty(C, 4, dtype=torch.float32, device=H1.device)
     work = torch.empty(int(lib.yolat_bn_apply_edge_sums_work_elems(N)), dtype=torch.float32, device=H1.device)
-    check(lib.yolat_bn_apply_edge_sums(_h(dA1, "dA1") if hp else _f(dA1, "dA1"), _ld(dA1), _h(H1, "H1") if hp else _f(H1, "H1"),
-                                       _ld(H1), dA1.data_ptr(), _ld(dA1), int(hp), E, _f(save_mean), _f(save_invstd),
+    check(lib.yolat_bn_apply_edge_sums(_fh(dA1, "dA1", hp), _ld(dA1), _fh(H1, "H1"), _ld(H1), dA1.data_ptr(), _ld(dA1),
+                                       int(hp), E, _f(save_mean), _f(save_invstd),
                                        _f(scale), _f(shift), int(relu), _f(coef), g.row_ptr.data_ptr(), g.attr.data_ptr(), N,
                                        dUV.data_ptr(), 2 * C, dwc4.data_ptr(), _f(db1, "db1", True), work.data_ptr(),
                                        _stream()), "yolat_bn_apply_edge_sums")
@@ -677,13 +682,9 @@ def edge_lin1_bwd_factorised(dH1, x, g, W1, dW1, db1, dx=None, dx_accumulate=Fal
                                        N, C, dUV.data_ptr(), 2 * C, _stream()), "yolat_edge_uv_sums_v")
     else:
         dUV = torch.empty(N, 2 * C, dtype=torch.float32, device=x.device)
-        if _is_h(dH1):
-            check(lib.yolat_edge_uv_sums_h(_h(dH1), _ld(dH1), g.row_ptr.data_ptr(), g.col_ptr.data_ptr(),
-                                           g.slots.data_ptr(), N, C, dUV.data_ptr(), 2 * C, _stream()),
-                  "yolat_edge_uv_sums_h")
-        else:
-            check(lib.yolat_edge_uv_sums(_f(dH1), _ld(dH1), g.row_ptr.data_ptr(), g.col_ptr.data_ptr(),
-                                         g.slots.data_ptr(), N, C, dUV.data_ptr(), 2 * C, _stream()), "yolat_edge_uv_sums")
+        fn = lib.yolat_edge_uv_sums_h if _is_h(dH1) else lib.yolat_edge_uv_sums
+        check(fn(_fh(dH1), _ld(dH1), g.row_ptr.data_ptr(), g.col_ptr.data_ptr(), g.slots.data_ptr(), N, C,
+                 dUV.data_ptr(), 2 * C, _stream()), fn.__name__)
     def weight_grads():
         dwuv = torch.empty(2 * C, Cin, dtype=torch.float32, device=x.device)
         linear_bwd_w(dUV, x, dwuv)
@@ -707,7 +708,7 @@ def edge_lin1_bwd_factorised(dH1, x, g, W1, dW1, db1, dx=None, dx_accumulate=Fal
 
 def edge_lin1_fwd_factorised(x, g, W1, b1, H1, stats=None, keep=None):
     """Same result as edge_lin1_fwd (to fp32 rounding) through the per-node products: UV = x.[W1a-W1b | W1b]^T by a
-    dense GEMM over the N nodes, then a gather-add over the E edges (csrc/edge.hip, yolat_edge_uv_lin1_fwd).  Pays
+    dense GEMM over the N nodes, then a gather-add over the E edges (csrc/edge_ops.hip, yolat_edge_uv_lin1_fwd).  Pays
     when E >> N; Cin == C == 64 only."""
     N, Cin = x.shape
     C = W1.shape[0]
@@ -716,14 +717,9 @@ def edge_lin1_fwd_factorised(x, g, W1, b1, H1, stats=None, keep=None):
         keep["wuv"] = wuv               # the backward of the same step needs the same split (edge_lin1_bwd_factorised)
     uv = torch.empty(N, 2 * C, dtype=torch.float32, device=x.device)
     linear_fwd(x, wuv, None, uv)
-    if _is_h(H1):
-        check(lib.yolat_edge_uv_lin1_fwd_h(uv.data_ptr(), 2 * C, g.src.data_ptr(), g.dst.data_ptr(), g.attr.data_ptr(),
-                                           g.E, wc4.data_ptr(), _f(b1, "b1", True), C, _h(H1, "H1"), _ld(H1),
-                                           _f(stats, "stats", True), _stream()), "yolat_edge_uv_lin1_fwd_h")
-        return H1
-    check(lib.yolat_edge_uv_lin1_fwd(uv.data_ptr(), 2 * C, g.src.data_ptr(), g.dst.data_ptr(), g.attr.data_ptr(), g.E,
-                                     wc4.data_ptr(), _f(b1, "b1", True), C, _f(H1), _ld(H1),
-                                     _f(stats, "stats", True), _stream()), "yolat_edge_uv_lin1_fwd")
+    fn = lib.yolat_edge_uv_lin1_fwd_h if _is_h(H1) else lib.yolat_edge_uv_lin1_fwd
+    check(fn(uv.data_ptr(), 2 * C, g.src.data_ptr(), g.dst.data_ptr(), g.attr.data_ptr(), g.E, wc4.data_ptr(),
+             _f(b1, "b1", True), C, _fh(H1, "H1"), _ld(H1), _f(stats, "stats", True), _stream()), fn.__name__)
     return H1
 
 
@@ -829,12 +825,9 @@ def csr_mean_fwd(H, g, out, h_pro=None, h_relu=False, accumulate=False):
 
 def csr_mean_bwd(dOut, g, dM):
     C = dOut.shape[1]
-    if _is_h(dM):
-        check(lib.yolat_csr_mean_bwd_h(_f(dOut), _ld(dOut), C, g.row_ptr.data_ptr(), g.dst.data_ptr(), g.E, _h(dM, "dM"),
-                                       _ld(dM), _stream()), "yolat_csr_mean_bwd_h")
-        return dM
-    check(lib.yolat_csr_mean_bwd(_f(dOut), _ld(dOut), C, g.row_ptr.data_ptr(), g.dst.data_ptr(), g.E,
-                                 _f(dM), _ld(dM), _stream()), "yolat_csr_mean_bwd")
+    fn = lib.yolat_csr_mean_bwd_h if _is_h(dM) else lib.yolat_csr_mean_bwd
+    check(fn(_f(dOut), _ld(dOut), C, g.row_ptr.data_ptr(), g.dst.data_ptr(), g.E, _fh(dM, "dM"), _ld(dM), _stream()),
+          fn.__name__)
     return dM
 
 
