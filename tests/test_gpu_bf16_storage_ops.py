@@ -518,8 +518,10 @@ def test_edge_uv_lin1_fwd_bf16_storage_matches_fp64(E, kind, with_b1, with_stats
 # ---------------------------------------------------------------------------------------------
 # 8  BatchNorm + ReLU + mean aggregation backward, never materialised
 # ---------------------------------------------------------------------------------------------
+# the last two: 513 and 1025 tiles, i.e. two and three per workgroup of the one-kernel backward (512 workgroups at most), the
+# last workgroup one and two — the smallest E at which its two-tiles-in-flight pipeline and cross-tile accumulators run
 BN_CSR_CASES = [(50, 31, "uniform"), (64, 64, "uniform"), (64, 65, "uniform"), (64, 129, "uniform"), (300, 1000, "uniform"),
-                (300, 1000, "hub150")]
+                (300, 1000, "hub150"), (4000, 32769, "uniform"), (4000, 65537, "hub1000")]
 
 
 def _bn_csr_case(N, E, kind):
@@ -547,7 +549,9 @@ def test_bn_csr_grad_bf16_storage_matches_fp64(N, E, kind, with_next):
     """ops.BnCsrGrad with bfloat16 Y (bn_csr.hip): stats(), then bwd_w_and_x() on bfloat16 A / dA (k_bn_csr_l2_bwd_h),
     with and without the statistics of the next BatchNorm's backward.  31 and 64 edges are one 64-row tile, 129 three
     (an odd count for the kernel that keeps two tiles in flight); hub150 puts a 150-edge segment over three tiles and
-    130 nodes without in-edge behind it (a hub needs E >= 2 deg: only (300, 1000) can hold one).
+    130 nodes without in-edge behind it (a hub needs E >= 2 deg: of the small cases only (300, 1000) can hold one).
+    32769 and 65537 edges are 513 and 1025 tiles: two and three per workgroup, the last workgroup one and two, so the
+    two-tiles-in-flight pipeline, the prefetch two tiles ahead and the accumulators carried from tile to tile all run.
 
     Reference: the float64 backward of mean-aggregate(relu(batchnorm(Y))) on the bfloat16 values of Y, restated as
     dY = scale (g - c1 - xhat c2) with g = [z > 0] d_out[dst] / deg (bf16_ref.bn_relu_bwd_ref is checked against autograd

@@ -7,6 +7,7 @@ import pytest
 import torch
 
 import golden_util as gu
+import graph_ref as gr
 from oracle import oracle_np as onp
 from oracle import oracle_torch as orc
 
@@ -1531,19 +1532,29 @@ def test_edge_attr_dw_streaming_reduction_matches_fp64(E, half):
     assert torch.equal(outs[0][0], outs[2][0]) and torch.equal(outs[0][1], outs[2][1])
 
 
-@pytest.mark.parametrize("N,E,half", [(1, 1, False), (40, 300, False), (5000, 42001, True), (50000, 300001, False),
-                                      (50000, 300001, True), (3000, 2500, False)])
-def test_bn_apply_edge_sums_equals_apply_then_sums(N, E, half):
+@pytest.mark.parametrize("N,E,half,graph", [
+    pytest.param(1, 1, False, None, id="1-1-False"), pytest.param(40, 300, False, None, id="40-300-False"),
+    pytest.param(5000, 42001, True, None, id="5000-42001-True"), pytest.param(50000, 300001, False, None, id="50000-300001-False"),
+    pytest.param(50000, 300001, True, None, id="50000-300001-True"), pytest.param(3000, 2500, False, None, id="3000-2500-False"),
+    pytest.param(45, 820, False, "ladder", id="ladder"), pytest.param(300, 2000, False, "hub1000", id="hub1000")])
+def test_bn_apply_edge_sums_equals_apply_then_sums(N, E, half, graph):
     """yolat_bn_apply_edge_sums + yolat_edge_uv_sums_v (edge_ops.hip, round 4) against the three launches they replace —
     yolat_bn_relu_bwd_apply, yolat_edge_uv_sums, yolat_edge_attr_dw (torch_vertex.py:331-332 backward): dH1 and dUV
     BIT-identical (same arithmetic, same ascending row order per node; bf16 storage: sums of the stored values), dWc4 /
     db1 against fp64 of the stored dH1 (their summation order differs from k_attr_dw's).  Skewed in-degrees incl. empty
-    rows ((3000, 2500): most nodes have no edge); run-to-run bit identity."""
+    rows ((3000, 2500): most nodes have no edge); run-to-run bit identity.  `graph` names a graph of graph_ref.GRAPHS in
+    place of the squared-uniform draw: the ladder (in-degree n at node n = 0..40: a wave's eight-row trips end inside a
+    node at every offset) and hub1000 (a workgroup owns 16 nodes, one of them with 1000 of its ~1090 rows: all four
+    quarter boundaries of the workgroup's row range fall inside that node, so two of its waves own no node)."""
     yv = _yv()
     ops = yv.ops
-    rng = np.random.default_rng(N + E)
-    src = rng.integers(0, N, size=E).astype(np.int64)
-    dst = (rng.integers(0, N, size=E) ** 2 // max(N, 1)).astype(np.int64)
+    if graph is None:
+        rng = np.random.default_rng(N + E)
+        src = rng.integers(0, N, size=E).astype(np.int64)
+        dst = (rng.integers(0, N, size=E) ** 2 // max(N, 1)).astype(np.int64)
+    else:
+        n, src, dst = gr.GRAPHS[graph]()
+        assert (n, len(src)) == (N, E)
     gen = torch.Generator().manual_seed(E)
     attr = (torch.randn(E, 4, generator=gen) * (torch.rand(E, 1, generator=gen) > 0.85)).contiguous().cuda()
     g = ops.build_graph(dev(np.stack([src, dst], 1)), attr, None, N, 1)
