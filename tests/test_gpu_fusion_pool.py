@@ -3,7 +3,7 @@ tests/segmax_layouts.py, on every path the drivers select.
 
 Training (ops.fusion_pool_train_fwd / _bwd, csrc/fusion_train.hip), one parametrised case per mode x layout:
   fp32       F = 1024: x6 rows kernel with the key64 epilogue (fusion_x6.hip), k_gram128, two-term k_fus_da_mfma<32>
-  fp32_f160  F = 160 (F % 64 == 32): generic k_gemm_nt with the key64 epilogue (common.hpp; a half-masked column tile)
+  fp32_f160  F = 160 (F % 64 == 32): generic k_gemm_nt with the key64 epilogue (gemm_nt.hpp; a half-masked column tile)
              and the fp32 dA scatter k_fus_da_sparse<8, 256>
   strict     F = 1024 under YOLAT_STRICT_FP32=1, read once per process: ONE child process runs every layout (k_gemm_nt
              key64 epilogue, k_fus_da_sparse) and each case reads its layout's result

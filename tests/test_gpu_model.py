@@ -518,7 +518,7 @@ def test_other_model_shapes_match_oracle(cin, blocks, blocks_out, classes):
 def test_launch_merging_of_the_small_graph_forward(tmp_path):
     """Small graphs run fewer launches than the op list has stages (forward_eval.hip): the pooling prologue (zero / max of
     feats / mean of the node branch) rides as extra workgroups in the last edge launch and the fusion launch
-    (common.hpp PoolRider), and layer l's edge launch computes layer l + 1's node side (EdgeNext: UV / root rows in the
+    (internal.hpp PoolRider), and layer l's edge launch computes layer l + 1's node side (EdgeNext: UV / root rows in the
     tile epilogue on 16x16x4 MFMAs, the node branch in extra workgroups).  The switches are read once per process,
     hence child processes:
       YOLAT_POOL_RIDERS=0   same arithmetic in the same order -> logits bit-identical to the default;
@@ -562,7 +562,7 @@ def test_launch_merging_of_the_small_graph_forward(tmp_path):
 
 
 def test_strict_fp32_switch_runs_the_fp32_mfma_kernels_and_agrees(tmp_path):
-    """YOLAT_STRICT_FP32=1 (csrc/x6.hpp, common.hpp yl_strict_fp32, plan._x6_on): one switch that takes every GEMM of the fp32
+    """YOLAT_STRICT_FP32=1 (csrc/x6.hpp, base.hpp yl_strict_fp32, plan._x6_on): one switch that takes every GEMM of the fp32
     mode off the bf16x6 emulation — eval forward at a size where the emulated kernels are the default for the edge stage
     (E >= 131072), the node side (N >= 65536), the fusion block and the classifier (P >= 1024), and one train step.  The
     two modes differ by summation order only; an Inf in the input propagates IEEE-style (no finite logits for that graph's

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Kernel-by-kernel comparison of the gfx950 device assembly of two csrc trees.
 
-    python tools/kernel_isa_diff.py <csrc_a> <csrc_b>
+    python tools/kernel_isa_diff.py [--per-file] <csrc_a> <csrc_b>
 
 Every .hip of both trees is compiled the way tools/kernel_resources.sh does (hipcc --offload-arch=gfx950 -O3 -std=c++17
 --save-temps, at most 16 at a time).  The device assembly is cut into one text per function symbol — the body from its
@@ -9,11 +9,17 @@ label to its end label, and for a kernel its .amdhsa_kernel descriptor — with 
 index of the block labels (.LBB<n>_) normalised, since that index only counts the functions in front of it in the file.
 One line per symbol: SAME, DIFF, ONLY-A or ONLY-B; the SAME kernels of a library namespace (rocprim's sort kernels,
 several hundred long names) are compared like the rest and counted on one line.  A symbol that several translation
-units emit (the static kernels of common.hpp, template instances of a shared header) is SAME only when the two trees
+units emit (the static kernels of gemm_tn.hpp, template instances of a shared header) is SAME only when the two trees
 give it the same SET of texts: the compiler does not always give one source the same instructions in every translation
-unit (k_gemm_nt_two of common.hpp has two forms within one tree), so a kernel that moves into a new file can come out
+unit (k_gemm_nt_two had two forms within one tree while every file included it), so a kernel that moves into a new file can come out
 changed, and that is a DIFF.  The exit status is 0 only when every line is SAME: a change that only moves kernels
-between files passes, anything that changes what a kernel executes or the resources it declares does not."""
+between files passes, anything that changes what a kernel executes or the resources it declares does not.
+
+--per-file compares the .hip files of the two trees by name instead, symbol by symbol: SAME or DIFF where both files emit
+the symbol, GONE for a symbol that only the old file emits, NEW for one that only the new file emits (a file that exists
+in one tree only counts as empty in the other).  The exit status is 0 when there is no DIFF and no NEW.  This is the
+mode for a change that takes dead copies of a kernel out of translation units that never launch it: in the whole-tree
+mode the symbol's set of texts shrinks, which is a DIFF there."""
 import concurrent.futures
 import glob
 import os
@@ -69,25 +75,66 @@ def functions(asm):
 
 
 def tree(hipcc, csrc, workdir, pool):
-    """{symbol: set of the texts the tree's translation units give it}"""
+    """{file name: {symbol: text}} of the tree's translation units"""
     srcs = sorted(glob.glob(os.path.join(csrc, "*.hip")))
     if not srcs:
         sys.exit("kernel_isa_diff: no .hip under %s" % csrc)
-    out = {}
     jobs = [pool.submit(device_asm, hipcc, os.path.abspath(s), os.path.join(workdir, os.path.basename(s))) for s in srcs]
-    for j in jobs:
-        for sym, text in functions(j.result()).items():
+    return {os.path.basename(s): functions(j.result()) for s, j in zip(srcs, jobs)}
+
+
+def texts(files):
+    """{symbol: set of the texts the tree's translation units give it}"""
+    out = {}
+    for syms in files.values():
+        for sym, text in syms.items():
             out.setdefault(sym, set()).add(text)
     return out
 
 
+def library_name(sym):
+    """the named namespace of a symbol that is not the anonymous one (library code: rocprim), else None"""
+    ns = re.match(r"_ZN(\d+)", sym)
+    if ns and not sym.startswith("_ZN12_GLOBAL__N_1"):
+        return sym[3 + len(ns.group(1)):][:int(ns.group(1))]
+    return None
+
+
+def per_file(a, b):
+    bad, total, lib_same = 0, 0, {}
+    for name in sorted(set(a) | set(b)):
+        fa, fb = a.get(name, {}), b.get(name, {})
+        for sym in sorted(set(fa) | set(fb)):
+            if sym not in fb:
+                verdict = "GONE"
+            elif sym not in fa:
+                verdict = "NEW"
+            else:
+                verdict = "SAME" if fa[sym] == fb[sym] else "DIFF"
+            total += 1
+            bad += verdict in ("DIFF", "NEW")
+            lib = library_name(sym)
+            if verdict == "SAME" and lib:
+                lib_same[lib] = lib_same.get(lib, 0) + 1
+            else:
+                print("%-4s %-16s %s" % (verdict, name, sym))
+    for lib, n in sorted(lib_same.items()):
+        print("SAME %s:: %d kernels" % (lib, n))
+    print("%d symbols in %d files, %d DIFF or NEW" % (total, len(set(a) | set(b)), bad))
+    return 1 if bad else 0
+
+
 def main():
-    if len(sys.argv) != 3:
+    args = [x for x in sys.argv[1:] if x != "--per-file"]
+    if len(args) != 2:
         sys.exit(__doc__)
     hipcc = find_hipcc()
     with tempfile.TemporaryDirectory(prefix="isa_diff_") as work, concurrent.futures.ThreadPoolExecutor(16) as pool:
-        a = tree(hipcc, sys.argv[1], os.path.join(work, "a"), pool)
-        b = tree(hipcc, sys.argv[2], os.path.join(work, "b"), pool)
+        a = tree(hipcc, args[0], os.path.join(work, "a"), pool)
+        b = tree(hipcc, args[1], os.path.join(work, "b"), pool)
+    if len(args) < len(sys.argv) - 1:
+        return per_file(a, b)
+    a, b = texts(a), texts(b)
     bad, lib_same = 0, {}
     for sym in sorted(set(a) | set(b)):
         if sym not in b:
@@ -97,9 +144,8 @@ def main():
         else:
             verdict = "SAME" if a[sym] == b[sym] else "DIFF"
         bad += verdict != "SAME"
-        ns = re.match(r"_ZN(\d+)", sym)        # a named namespace that is not the anonymous one: library code
-        if verdict == "SAME" and ns and not sym.startswith("_ZN12_GLOBAL__N_1"):
-            name = sym[3 + len(ns.group(1)):][:int(ns.group(1))]
+        name = library_name(sym)
+        if verdict == "SAME" and name:
             lib_same[name] = lib_same.get(name, 0) + 1
         else:
             print("%-6s %s" % (verdict, sym))

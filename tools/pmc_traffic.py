@@ -11,18 +11,26 @@ import sys
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CS = "yolat_vectorgraphicsrecognition_amd/csrc/"
+
+
+def srcs(hip, *headers):
+    """the kernel's .hip and the headers that file includes, directly or through another header"""
+    return [CS + h + ".hpp" for h in headers] + [CS + hip]
+
+
+GEMM_NT = ("base", "operands", "epilogue", "gemm_nt")
 # eval-plan stage (forward_eval.hip YL_STAGE names) -> (kernel name prefix, source files)
 # pick: which launch grid of the kernel belongs to the stage when one forward launches the kernel with several grids
 #   "all"  average over every grid;  "last_layer" / "with_next": the node-tile edge kernel of a small graph is launched once
 #   per conv layer — the last layer's launch carries the pooling rider (the largest grid), the others the next layer's node
 #   side (EdgeNext: smaller grids)
 STAGES = {
-    "fusion_gemm+segmax[N x 128 -> 1024 -> P] | super[P x 128 -> 1024]": ("k_fusion_rows_x6<128", [CS + "common.hpp", CS + "x6.hpp", CS + "fusion_x6.hip"], "all"),
-    "edge_uv_mlp2_mean[E x (U+V+attr) -> 64 -> 64 -> mean]": ("k_edge_uv_mlp2_mean", [CS + "common.hpp", CS + "edge.hip"], "last_layer"),
-    "edge_uv_mlp2_mean+node_uv_next[E x (U+V+attr) -> 64 -> 64 -> mean; N x 64 -> 128+64+64]": ("k_edge_uv_mlp2_mean", [CS + "common.hpp", CS + "edge.hip"], "with_next"),
-    "node_uv[UV | lin_r | mlp_node, N x 64 -> 128+64+64]": ("k_gemm_nt_node3", [CS + "common.hpp", CS + "dense.hip"], "all"),
+    "fusion_gemm+segmax[N x 128 -> 1024 -> P] | super[P x 128 -> 1024]": ("k_fusion_rows_x6<128", srcs("fusion_x6.hip", "base", "x6", "segmax", "operands", "internal"), "all"),
+    "edge_uv_mlp2_mean[E x (U+V+attr) -> 64 -> 64 -> mean]": ("k_edge_uv_mlp2_mean", srcs("edge.hip", *GEMM_NT, "gemm_nt_two", "internal"), "last_layer"),
+    "edge_uv_mlp2_mean+node_uv_next[E x (U+V+attr) -> 64 -> 64 -> mean; N x 64 -> 128+64+64]": ("k_edge_uv_mlp2_mean", srcs("edge.hip", *GEMM_NT, "gemm_nt_two", "internal"), "with_next"),
+    "node_uv[UV | lin_r | mlp_node, N x 64 -> 128+64+64]": ("k_gemm_nt_node3", srcs("dense.hip", *GEMM_NT, "gemm_nt_two", "gemm_sk", "gemm_tn", "internal"), "all"),
     # small graphs: the one-launch form (k_prep_small); larger ones: the last of the four launches
-    "graph_prep[csr+attr+segments] + node_uv[layer 0]": (("k_prep_small", "k_prep_rows_node3"), [CS + "common.hpp", CS + "graph.hip"], "all"),
+    "graph_prep[csr+attr+segments] + node_uv[layer 0]": (("k_prep_small", "k_prep_rows_node3"), srcs("graph.hip", *GEMM_NT, "internal"), "all"),
 }
 
 
@@ -30,11 +38,11 @@ STAGES = {
 STAGES_BF16 = {
     # round 5: the one-launch proposal-local conv stack (the per-layer edge / node launches behind it are dead, gated launches
     # on such a batch: their rows in the PMC files are not the stages' traffic and are dropped below)
-    "conv_local_bf16[all conv layers + pooling prologue, one launch]": ("k_conv_local_h", [CS + "common.hpp", CS + "conv_local.hip"], "all"),
-    "edge_uv_mlp2_mean_bf16[E x (U+V+attr) -> 64 -> 64 -> mean]": ("k_edge_chain_h", [CS + "common.hpp", CS + "edge_chain.hip"], "all"),
-    "fusion_gemm_bf16+segmax[N x 128 -> 1024 -> P] | super[P x 128 -> 1024]": ("k_hfusion_rows8<128", [CS + "common.hpp", CS + "segmax.hpp", CS + "fusion_h8.hip"], "all"),
-    "node_uv_bf16[UV | lin_r | mlp_node, N x 64 -> 128+64+64]": ("k_hgemm_node3", [CS + "common.hpp", CS + "bf16_eval.hip"], "all"),
-    "graph_prep[csr+attr+segments] + node_uv[layer 0, bf16 out]": ("k_prep_rows_node3", [CS + "common.hpp", CS + "graph.hip"], "all"),
+    "conv_local_bf16[all conv layers + pooling prologue, one launch]": ("k_conv_local_h", srcs("conv_local.hip", "base", "internal"), "all"),
+    "edge_uv_mlp2_mean_bf16[E x (U+V+attr) -> 64 -> 64 -> mean]": ("k_edge_chain_h", srcs("edge_chain.hip", "base", "internal"), "all"),
+    "fusion_gemm_bf16+segmax[N x 128 -> 1024 -> P] | super[P x 128 -> 1024]": ("k_hfusion_rows8<128", srcs("fusion_h8.hip", "base", "segmax", "internal"), "all"),
+    "node_uv_bf16[UV | lin_r | mlp_node, N x 64 -> 128+64+64]": ("k_hgemm_node3", srcs("bf16_eval.hip", *GEMM_NT, "internal"), "all"),
+    "graph_prep[csr+attr+segments] + node_uv[layer 0, bf16 out]": ("k_prep_rows_node3", srcs("graph.hip", *GEMM_NT, "internal"), "all"),
 }
 
 

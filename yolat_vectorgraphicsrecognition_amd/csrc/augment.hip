@@ -18,7 +18,7 @@
 // and stores cover one contiguous stretch of pos.  A proposal of 1 node reduces over 15 neutral lanes; a proposal of
 // more than 1024 nodes is just a longer walk.  No atomics.  Traffic per batch: 8 N + 4 P bytes read (pos, the
 // segment pointers), 16 N + 16 P written (pos, the two columns of x, bbox).
-#include "common.hpp"
+#include "base.hpp"
 
 constexpr int AUG_G = 16;                    // lanes per proposal
 constexpr int AUG_THREADS = 256;

@@ -11,7 +11,10 @@
 //     and the classifier activations stay fp32 (small or precision-critical).
 // Rounding to bf16 is round-to-nearest-even (v_cvt_pk_bf16_f32).  Parity target: <= 1e-2 of the logits'
 // scale against the fp32 oracle (SURVEY.md §8c "bf16 variant"); the fp32 path keeps the 1e-4 bar.
-#include "common.hpp"
+#include "operands.hpp"
+#include "epilogue.hpp"
+#include "gemm_nt.hpp"
+#include "internal.hpp"
 #include <stdlib.h>
 #include <atomic>
 
@@ -44,7 +47,7 @@ extern "C" int yolat_f32_to_bf16(const float* src, int64_t n, uint16_t* dst, yol
 // to 144 B so that both the 16-byte staging writes (8 lanes = one row) and the 16-byte fragment reads
 // (8 consecutive rows at one k offset) hit 8 distinct 16-byte bank groups.
 //   MFMA operand layout: A/B lane l holds the 8 consecutive k = 16 ks + 8 (l>>5) .. +7 of row / column l&31;
-//   C/D layout as for the fp32 MFMA, so wave_epilogue (common.hpp) is shared with the fp32 kernels.
+//   C/D layout as for the fp32 MFMA, so wave_epilogue (epilogue.hpp) is shared with the fp32 kernels.
 // A operand: bf16 rows (HOp) or fp32 rows converted while staging (FOp); B operand: bf16 weight rows.
 // Rows beyond M / N are clamped (their outputs are masked by the epilogue).
 // ------------------------------------------------------------------------------------------------
@@ -593,15 +596,6 @@ static __global__ void __launch_bounds__(256) k_pool_prepare_h(const u16* feats,
 // edge stage dispatch: register-chained MFMA waves (edge_chain.hip) for large, dense-enough graphs, node tiles
 // otherwise.  Both take the folded second Linear (W2f = bf16(diag(s2) W2), t2f = s2 b2 + t2).
 // ------------------------------------------------------------------------------------------------
-int yl_edge_chain_bf16(const uint16_t* UV, int64_t ld_uv, const int32_t* src_csr, const int32_t* dst_csr,
-                       const float* attr_csr, const int32_t* row_ptr, int64_t N, int64_t E, const float* Wc4,
-                       const float* s1, const uint16_t* W2f, const float* t2f, const float* root, int64_t ld_r,
-                       uint16_t* f_out, int64_t ld_fo, hipStream_t st, YlGate gate);
-
-bool yl_conv_local_model_ok(const yolat_model_eval_bf16* mh);
-int yl_conv_local_bf16(const yolat_model_eval_bf16* mh, const void* pack, const float* x, int64_t ldx, const YlLocalIn& in,
-                       int64_t N, int64_t E, int64_t P, uint16_t* feats, int64_t ld_feats, float* Z, int64_t ldz, int32_t* flag,
-                       int32_t flag_val, hipStream_t st);
 // YOLAT_CONV_LOCAL: 0 = never, 1 = batches with >= 1024 proposals (default), 2 = every batch
 // (read per call: tests flip it in-process)
 static __global__ void k_zero_word(int* p) { if (threadIdx.x == 0) *p = 0; }
@@ -609,10 +603,6 @@ static int yl_conv_local_mode() {
   const char* e = getenv("YOLAT_CONV_LOCAL");
   return (e && e[0] >= '0' && e[0] <= '3') ? e[0] - '0' : 1;      // (3: measurement only — forced, WITHOUT the gated fall-back)
 }
-
-int yl_hfusion_rows8(const uint16_t* A, int64_t lda, int64_t N, int64_t D, const uint16_t* Wf, const float* tf,
-                     const int32_t* seg, float* pool, int64_t ld_pool, int64_t F, const float* As, int64_t lda_s, int64_t P,
-                     const uint16_t* Wfs, const float* tfs, float* sup_out, int64_t ld_sup, hipStream_t st);
 
 static int yl_edge_uv_mlp2_mean_bf16_impl(const u16* UV, long ld_uv, const int* src, const int* dst, const float* attr,
                                           const int* row_ptr, long N, long E, const float* Wc4, const float* s1,
@@ -948,11 +938,9 @@ static int forward_eval_bf16_impl(const yolat_model_eval_bf16* mh, const float* 
       const int tn = yl_cdiv(F, 64);
       // measured at cfg 5 (N = 200k): 64-row tiles x 4 column groups 160 us, x 1 group 166 us, 128-row tiles 181 us
       // (x 1) / 161 us (x 4); cfg 2 (N = 10k): 8 groups 16.1 us, 16 groups 16.8 us, 2 groups 21.2 us
-      bool big = false;
-      long min_wgs = 1024;
-      const int tm0 = yl_cdiv(N, big ? 128 : 64);
+      const int tm0 = yl_cdiv(N, 64);
       int groups = 4;
-      while ((long)tm0 * groups < min_wgs && groups < tn) groups *= 2;
+      while ((long)tm0 * groups < 1024 && groups < tn) groups *= 2;
       if (groups > tn) groups = tn;
       const int ng = yl_cdiv(tn, groups);
       groups = yl_cdiv(tn, ng);
@@ -962,8 +950,8 @@ static int forward_eval_bf16_impl(const yolat_model_eval_bf16* mh, const float* 
         hipLaunchKernelGGL(kern, dim3((unsigned)total), dim3(256), 0, st, a0, b0, e0, (int)N, (int)F, (int)D, tm0, groups, ng,
                            a1, b1, e1, (int)P, (int)F, (int)D, tm1, tn1);
       };
-      if (D <= 128) { if (big) go(k_hfusion_rows<2, 128>); else go(k_hfusion_rows<1, 128>); }
-      else { if (big) go(k_hfusion_rows<2, 256>); else go(k_hfusion_rows<1, 256>); }
+      if (D <= 128) go(k_hfusion_rows<1, 128>);
+      else go(k_hfusion_rows<1, 256>);
     } else {
     const bool big = N >= 65536;                       // 128x128 tiles once there are enough of them to fill the GPU
     const int tm0 = yl_cdiv(N, big ? 128 : 64), tn0 = yl_cdiv(F, big ? 128 : 64);
@@ -1084,7 +1072,7 @@ static __global__ void __launch_bounds__(256) k_hlin64_stream(const u16* __restr
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[r] += bv;
     const int row_base = tile * 64 + wm * 32;
-    if (stats != nullptr) {                                // wave_epilogue's arithmetic (common.hpp), per 32-row group
+    if (stats != nullptr) {                                // wave_epilogue's arithmetic (epilogue.hpp), per 32-row group
       int cnt = M - row_base;
       cnt = cnt > 32 ? 32 : cnt;
       float sm = 0.f;

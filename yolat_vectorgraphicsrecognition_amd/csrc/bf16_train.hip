@@ -24,6 +24,7 @@
 //                         column tile.  The pooled value and the arg row k_pool_finish decodes come from the same key,
 //                         i.e. from the same bf16 products.
 #include "segmax.hpp"
+#include "internal.hpp"
 
 typedef unsigned bt_u32x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bt_bf16x8 __attribute__((ext_vector_type(8)));

@@ -11,9 +11,12 @@
 //   yolat_linear_fwd_wt_csr  dA = dY . W                                          — dY formed in the NT GEMM's loader
 // = 5 passes.  The arithmetic per element is the one of k_csr_mean_bwd_v4 + k_bn_bwd_partial_v4 + k_bn_bwd_apply_v4
 // (same operations in the same order).
-#include "common.hpp"
+#include "operands.hpp"
+#include "epilogue.hpp"
+#include "gemm_nt.hpp"
+#include "gemm_tn.hpp"
 
-// dY rows formed on the fly (loader contract of the GEMM tile kernels, common.hpp)
+// dY rows formed on the fly (loader contract of the GEMM tile kernels, operands.hpp)
 template <class T>
 struct BnCsrOpT {
   const float* dout; long ldo;           // [N, C]

@@ -16,7 +16,7 @@
 //                           form is the CONCATENATION of the items' forms with the node / edge / proposal offsets added
 //                           — bit-identical to rebuilding it from the collated COO list (tests/test_abi_host.py).
 // No device code in this file.
-#include "common.hpp"
+#include "base.hpp"
 #include <string.h>
 #include <vector>
 

@@ -34,7 +34,8 @@
 //                mean of s -> Z (fp32), and once per tile Z[p, 0:F] = 0 (what k_pool_prepare_h did in a launch of its own).
 // A batch that is not proposal-local, or a proposal that does not fit a tile, raises `flag`; the caller keeps the per-layer
 // launches enqueued behind this one, gated on that word (bf16_eval.hip).
-#include "common.hpp"
+#include "base.hpp"
+#include "internal.hpp"
 #include <stdlib.h>
 
 typedef unsigned short u16;

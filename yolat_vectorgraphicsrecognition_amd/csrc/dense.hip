@@ -1,7 +1,13 @@
 // dense.hip — nn.Linear / BatchNorm1d / ReLU of gcn_lib/sparse/torch_nn.py:50-71 on gfx950.
 // Entry points: yolat_linear_fwd, yolat_linear_fwd_wt, yolat_linear_bwd_w, yolat_bn_finalize,
 // yolat_bn_eval_coeffs, yolat_scale_shift_relu, yolat_bn_relu_bwd.
-#include "common.hpp"
+#include "operands.hpp"
+#include "epilogue.hpp"
+#include "gemm_nt.hpp"
+#include "gemm_nt_two.hpp"
+#include "gemm_sk.hpp"
+#include "gemm_tn.hpp"
+#include "internal.hpp"
 #include <type_traits>
 
 // switch of the LDS-DMA skinny GEMM (tools/exp/lds_dma_bench.py, tests; not part of the C ABI header)
@@ -27,7 +33,7 @@ static int launch_gemm_nt(const AL& A, const BL& B, const Epilogue& ep, long M, 
     dim3 grid(yl_cdiv(M, 32), yl_cdiv(N, 32));
     bool dma = false;
     if constexpr (std::is_same<AL, DenseOp>::value && std::is_same<BL, DenseOp>::value && !NFAST) {
-      // the LDS-DMA experiment (common.hpp k_gemm_nt_sk_dma): plain operands with 16-byte rows, whole 128-deep chunks
+      // the LDS-DMA experiment (gemm_sk.hpp k_gemm_nt_sk_dma): plain operands with 16-byte rows, whole 128-deep chunks
       // measured at the cfg-2 classifier (P = 400, tools/exp/lds_dma_bench.py): 2304 -> 512: 20.7 us VGPR-staged, 20.1 us
       // LDS-DMA with 4 waves, 18.6 us with 8; 512 -> 256 (4 chunks): 8.9 / 9.2 / 9.3 us — the DMA pipeline needs a long K
       const int mode = yl_gemm_sk_dma_on() < 0 ? (K >= 1024 ? 8 : 0) : yl_gemm_sk_dma_on();
@@ -157,7 +163,7 @@ __global__ void __launch_bounds__(256) k_lin64_stream(const float* __restrict__ 
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[r] += bv;
     const int row_base = tile * 64 + wm * 32;
-    if (stats != nullptr) {                              // wave_epilogue's arithmetic (common.hpp), per 32-row group
+    if (stats != nullptr) {                              // wave_epilogue's arithmetic (epilogue.hpp), per 32-row group
       int cnt = M - row_base;
       cnt = cnt > 32 ? 32 : cnt;
       float sm = 0.f;
@@ -339,7 +345,7 @@ int yl_build_node_uv(NodeUv* a, const float* f_in, int64_t ld_f, const float* s_
   return 0;
 }
 
-// Node side of the first conv layer of a large graph as an output stream: launcher of common.hpp's node3_smallk_body
+// Node side of the first conv layer of a large graph as an output stream: launcher of gemm_nt.hpp's node3_smallk_body
 namespace {
 __global__ void __launch_bounds__(256) k_node3_smallk(NodeUv a) {
   node3_smallk_body(a, blockIdx.x);
@@ -447,12 +453,6 @@ extern "C" int yolat_linear_fwd_wt(const float* A, int64_t lda, int64_t M, int64
   ep.Y = Y; ep.ldy = ldy; ep.accumulate = accumulate; ep.stats = nullptr; ep.seg = nullptr; ep.pool = nullptr; ep.ldpool = 0;
   return launch_gemm_nt<DenseOp, TransOp, true>(a, b, ep, M, Nout, K, (hipStream_t)stream);
 }
-
-// gemm_x6.hip: the weight gradient of a wide Linear on the bf16x6 GEMM
-bool yl_bwd_w_x6_ok(int64_t M, int64_t Nout, int64_t K);
-size_t yl_bwd_w_x6_work_elems(int64_t M, int64_t Nout, int64_t K);
-int yl_bwd_w_x6(const float* dY, int64_t lddy, int64_t M, int64_t Nout, const float* A, int64_t lda, int64_t K, float* dW,
-                int64_t lddw, float* db, int accumulate_db, float* work, hipStream_t st);
 
 extern "C" size_t yolat_linear_bwd_w_work_elems(int64_t M, int64_t Nout, int64_t K) {
   TnPlan p = yl_tn_plan(M, Nout, K);

@@ -17,7 +17,7 @@
 // boxes kept in its own chunk, and the walk stops at the 300th keep: O(n * 300) IoU tests and O(n) memory, where the
 // n x n / 64 suppression mask of nms.hip is 112 MB per image at the 30 000-candidate cap.  The predicate is nms.hip's.
 // Workspace: 24 bytes per slot (keys and slots, in and out) + rocPRIM's own temporary storage.
-#include "common.hpp"
+#include "base.hpp"
 
 #include <rocprim/device/device_radix_sort.hpp>
 

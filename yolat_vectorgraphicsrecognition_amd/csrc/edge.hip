@@ -4,7 +4,10 @@
 // entries.  All [E,*] tensors are in destination-sorted (CSR) order, so aggregation reads contiguous rows and needs no
 // atomics.  The single-op edge kernels of training and of the eval fall-back (first edge Linear, CSR mean, scatter,
 // per-node sums and their backward) live in edge_ops.hip.
-#include "common.hpp"
+#include "operands.hpp"
+#include "epilogue.hpp"
+#include "gemm_nt_two.hpp"   // not launched here: see the header
+#include "internal.hpp"
 #include <stdlib.h>
 
 // ------------------------------------------------------------------------------------------------
@@ -281,7 +284,7 @@ __global__ void __launch_bounds__(256, NG == 1 ? 4 : 1) k_edge_uv_mlp2_mean(cons
                                                            const float* __restrict__ t2, float* f_out, long ld_fo,
                                                            int E, int tiles, PoolRider rider, EdgeNext nx) {
   // workgroups past the node tiles: the next layer's node-branch tiles (EdgeNext), then the pooling-prologue rider
-  // (common.hpp) — both independent of this layer's messages
+  // (internal.hpp) — both independent of this layer's messages
   if ((int)blockIdx.x >= tiles + nx.s_tiles) {
     yl_pool_rider(rider, blockIdx.x - tiles - nx.s_tiles, rider.blocks, threadIdx.x, 256);
     return;
@@ -459,7 +462,7 @@ __global__ void __launch_bounds__(256, NG == 1 ? 4 : 1) k_edge_uv_mlp2_mean(cons
     }
   }
   EDGE_STAMP(9);
-  // ---- node side of the NEXT layer for this tile's nodes (EdgeNext, common.hpp): [nn <= 16, 64] x [192, 64]^T
+  // ---- node side of the NEXT layer for this tile's nodes (EdgeNext, internal.hpp): [nn <= 16, 64] x [192, 64]^T
   if constexpr (NG == 1 && NEXT) {
     // the first column tile's B fragments are fetched here, after the pass loop, and the other two under the previous
     // tile's MFMAs: held from before the first barrier they cost 16 registers through the whole edge phase, which put
@@ -645,7 +648,7 @@ __device__ __forceinline__ void edge_s_tile(const EdgeNext& nx, int N, int r0, f
     if (row < N) nx.s_out[(long)row * nx.ld_so + colS] = fmaxf(fmaf(accS[r] + bS, scS, shS), 0.f);
   }
 }
-// node side of the NEXT layer for one tile's nodes (EdgeNext, common.hpp): [nn <= 16, 64] x [192, 64]^T.  Hs must be free
+// node side of the NEXT layer for one tile's nodes (EdgeNext, internal.hpp): [nn <= 16, 64] x [192, 64]^T.  Hs must be free
 // (the pass loop ended with a barrier, or never ran); fz = the thread's final f_out columns of node rb.
 __device__ __forceinline__ void edge_next_node_side(const EdgeNext& nx, int n0, int nn, int rb, int q, int wave, int lane,
                                                     const float4& fo0, float* Hs) {

@@ -28,7 +28,8 @@
 //       the start of the step), scale by 1/deg and store the bf16 output row with 8-byte stores.
 // Vector-ALU work per hidden element drops from ~13 to ~1 (ReLU/convert) + 2 per message (ReLU, add); 20 MFMAs per 32
 // edges.  Deterministic: fixed summation order, no float atomics.
-#include "common.hpp"
+#include "base.hpp"
+#include "internal.hpp"
 #include <stdlib.h>
 
 typedef unsigned short u16;

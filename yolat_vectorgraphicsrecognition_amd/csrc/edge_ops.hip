@@ -6,7 +6,10 @@
 //
 // Ops with a bfloat16-storage twin (`_h`: the [E,64] operand stored as bf16) have ONE host wrapper, a template on the
 // operand's element type T = float / yl_bf16_t; where the twins differ, an `if constexpr` names the difference.
-#include "common.hpp"
+#include "operands.hpp"
+#include "epilogue.hpp"
+#include "gemm_nt.hpp"
+#include "gemm_tn.hpp"
 #include <type_traits>
 
 // rows of T that the kernels read or write four elements at a time: 16 bytes of float, 8 of bfloat16

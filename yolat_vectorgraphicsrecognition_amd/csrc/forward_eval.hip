@@ -2,7 +2,8 @@
 // of cad_recognition/architecture3cc_rpn_gp_iter2.py:44-71,106-137 is enqueued from C++ with no
 // Python between launches (the cfg-2 forward is ~100-300 us of GPU time, i.e. launch-latency
 // territory: the host side has to be a tight loop of hipLaunchKernel calls).
-#include "common.hpp"
+#include "gemm_nt.hpp"
+#include "internal.hpp"
 
 namespace {
 struct Plan {
@@ -313,7 +314,7 @@ static int forward_eval_impl(const yolat_model_eval* m, const float* x, int64_t 
   const bool fold0 = cv0.Wuvf && cv0.uvb && cv0.Wc4f && cv0.t2f;
   // One launch per conv layer (small graphs on the <= 16-node tiles, every layer factorised + folded, packed next-layer
   // weights present): layer l's edge launch computes layer l + 1's UV / root rows for its own nodes and, in extra
-  // workgroups, layer l + 1's node branch (EdgeNext, common.hpp) — k_gemm_nt_node3 is not launched at all.
+  // workgroups, layer l + 1's node branch (EdgeNext, internal.hpp) — k_gemm_nt_node3 is not launched at all.
   // YOLAT_NODE_CHAIN=0: node side as a launch per layer.
   static const bool chain_on = []() { const char* v = getenv("YOLAT_NODE_CHAIN"); return !(v && v[0] == '0'); }();
   bool chain_mode = chain_on && node0_ok && fold0 && E > 0 && m->n_blocks >= 2 && p.UV2 != nullptr &&
@@ -343,7 +344,7 @@ static int forward_eval_impl(const yolat_model_eval* m, const float* x, int64_t 
 
   // ---- pooling prologue (segment.hip k_pool_prepare): a launch of its own for large graphs; for small ones
   // (YOLAT_POOL_RIDERS != 0, P * (F + 2 D) below ~1 M items) its parts ride in the last edge launch and the fusion
-  // launch (common.hpp PoolRider) — at cfg 2 that launch is 5 us of pure latency
+  // launch (internal.hpp PoolRider) — at cfg 2 that launch is 5 us of pure latency
   static const bool riders_on = []() { const char* v = getenv("YOLAT_POOL_RIDERS"); return !(v && v[0] == '0'); }();
   const bool fusion_x6 = m->Wf_hi && m->Wf_mid && m->Wf_lo && m->tf_fold && m->Wfs_hi && m->Wfs_mid && m->Wfs_lo &&
                          m->tfs_fold && (D == 64 || D == 128) && F % 64 == 0 && (long)P * ZW < (1LL << 32);

@@ -14,6 +14,7 @@
 // The small problem (fusion_block_super on the P per-proposal means, fp32 rows converted while loading, plain ReLU
 // store) rides in the same launch, its workgroups first.
 #include "segmax.hpp"
+#include "internal.hpp"
 #include <stdlib.h>
 
 typedef unsigned short u16;

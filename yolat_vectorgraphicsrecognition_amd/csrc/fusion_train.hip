@@ -22,7 +22,11 @@
 //        dA[r,:] = sum_{c: arg[p(r),c]=r} s_c g[p,c] w_c  -  sum_c (s_c dbeta_c/N) w_c  -  (A[r]-mean_A) . (W^T diag(s rstd dgamma/N) W)
 //        db = 0 (BatchNorm removes the Linear bias from the loss)
 //    i.e. two sparse P*F-term kernels plus K x K / F x K sized dense algebra.
-#include "common.hpp"
+#include "operands.hpp"
+#include "epilogue.hpp"
+#include "gemm_nt.hpp"
+#include "gemm_tn.hpp"
+#include "internal.hpp"
 #include <stdlib.h>
 
 constexpr int CS_ROWS = 512;    // rows per column-sum workgroup

@@ -23,6 +23,8 @@ extern __device__ long long fx_stamps_d[4096 * 32];
 #define FX_EPI_STAMP(k) do { if (threadIdx.x == 0 && blockIdx.x < 4096) fx_stamps_d[blockIdx.x * 32 + 25 + (k)] = wall_clock64(); } while (0)
 #endif
 #include "segmax.hpp"
+#include "operands.hpp"
+#include "internal.hpp"
 #include <algorithm>
 #include <map>
 #include <queue>
@@ -102,7 +104,7 @@ __global__ void __launch_bounds__(FxShape<KD>::T, 2) k_fusion_rows_x6(FxProb p0,
   // id % 8 = XCD alignment): they start with the first round of workgroups instead of forming a tail
   const int n1 = p1.tm * p1.groups, n1p = (n1 + 7) & ~7;
   const int id = blockIdx.x;
-  // workgroups past both problems: pooling-prologue rider (common.hpp; reads A like the GEMM, writes columns of the
+  // workgroups past both problems: pooling-prologue rider (internal.hpp; reads A like the GEMM, writes columns of the
   // pooled rows that nothing in this launch reads)
   // the big problem: p0.full whole-row-tile workgroups first, then the remaining row tiles split into column groups
   const int n0t = (p0.tm - p0.full) * p0.groups, n0 = p0.full + n0t;
@@ -308,7 +310,7 @@ __global__ void __launch_bounds__(FxShape<KD>::T, 2) k_fusion_rows_x6(FxProb p0,
       unsigned rb = (unsigned)(row0 + 4 * lhi);
       asm volatile("" : "+v"(rb));
       if (P.stats != nullptr) {
-        // BatchNorm partial statistics of this wave's 32-row group, as wave_epilogue (common.hpp) takes them
+        // BatchNorm partial statistics of this wave's 32-row group, as wave_epilogue (epilogue.hpp) takes them
         int cnt = N - row0;
         cnt = cnt > 32 ? 32 : cnt;
         if (cnt > 0) {

@@ -19,6 +19,8 @@
 // fragments conflict-free.  Few rows (P = a few hundred): the launch splits K over gridDim.y workgroups writing fp32
 // partials, summed in a fixed order by k_gemm_x6_reduce (deterministic; no atomics).
 #include "x6.hpp"
+#include "operands.hpp"
+#include "internal.hpp"
 
 #define GX_BM 128
 #define GX_BN 128

@@ -5,7 +5,8 @@
 // Counting sort = histogram (int atomics: order-independent result) -> single-workgroup exclusive
 // scan -> cursor fill (unordered) -> per-row insertion sort by edge id (restores the stable order;
 // rows are short: in-degree of a Bezier end point is a handful).
-#include "common.hpp"
+#include "gemm_nt.hpp"
+#include "internal.hpp"
 
 __global__ void k_edge_count(const int64_t* edge, long se, long sc, int E, int N, int* src32,
                              int* dst32, int* cnt, int* status) {
@@ -807,7 +808,7 @@ int yl_graph_prepare_impl(const int64_t* edge, int64_t stride_e, int64_t stride_
   }
   const int rows_blocks = yl_cdiv(E > n1 ? E : n1, 256);
   if (extra != nullptr && yl_node3_smallk_ok(*extra)) {
-    // large graph: the K = in_channels node side is an output stream of its own (common.hpp node3_smallk_body), not tiles
+    // large graph: the K = in_channels node side is an output stream of its own (gemm_nt.hpp node3_smallk_body), not tiles
     // of this launch.  (Riding in the COUNTING launch instead, interleaved with its blocks, was measured: the stream slows
     // the returning atomics down — fp32 38.8 + 51 us as two launches, 109 us as one; bf16 34.6 + 43.5 vs 75.)
     hipLaunchKernelGGL(k_prep_rows, dim3(rows_blocks), dim3(256), 0, st, local, btot, (int)N, (int)E, items, src32, dst32,

@@ -1,0 +1,169 @@
+// internal.hpp — what one .hip of libyolat_hip.so defines and another one uses: the structures that cross files and EVERY
+// non-static function that does.  A function is declared here once, with the file that defines it; the definer and
+// every caller include this header, and default arguments appear only here.  No .hip declares such a function by hand
+// (tests/test_csrc_decls_host.py).  The C ABI itself is include/yolat_hip.h.
+#pragma once
+#include "base.hpp"
+
+struct NodeUv;        // gemm_nt.hpp: operands / epilogues of the node side of a factorised conv layer
+
+// fills the node side of a factorised conv layer (dense.hip)
+int yl_build_node_uv(NodeUv* a, const float* f_in, int64_t ld_f, const float* s_in, int64_t ld_s, int64_t N,
+                     int64_t Cin, const float* Wuv, const float* uv_bias, const float* Wr, const float* br,
+                     const float* Wn, const float* bn, const float* sn, const float* tn, int64_t C, float* UV,
+                     int64_t ld_uv, float* f_out, int64_t ld_fo, float* s_out, int64_t ld_so);
+// the node side of the first conv layer (K = in_channels <= 8) of a large graph as an output stream (dense.hip)
+bool yl_node3_smallk_ok(const NodeUv& a);
+bool yl_node3_smallk_shape_ok(const NodeUv& a);
+int yl_node3_smallk(const NodeUv& a, hipStream_t st, YlGate gate = YlGate{nullptr, 0});
+// training-mode fusion GEMM with the key64 pooling epilogue on the bf16x6 rows kernel (fusion_x6.hip)
+int yl_fusion_rows_x6_key64(const float* A, long lda, long N, long K, const float* W, const float* bias, long F,
+                            const float* sgn, const int* node_seg, unsigned long long* keys, uint16_t* wsplit,
+                            yolat_stream_t stream);
+// the same on bf16 operands ("bf16_dense" training precision, bf16_train.hip): K == 128; wimg = F * K bfloat16
+int yl_fusion_rows_bf16_key64(const float* A, long lda, long N, long K, const float* W, const float* bias, long F,
+                              const float* sgn, const int* node_seg, unsigned long long* keys, uint16_t* wimg,
+                              yolat_stream_t stream);
+// ------------------------------------------------------------------------------------------------
+// Pooling prologue as a RIDER of other launches (small graphs, where a launch of its own is ~5 us of latency):
+// the parts of k_pool_prepare (segment.hip) done by `blocks` extra workgroups appended to a kernel whose own
+// workgroups do not depend on them:
+//   YL_POOL_ZERO  Z[p, 0:F] = 0                      } ride in the LAST conv layer's edge kernel (need the node branch
+//   YL_POOL_MEAN  Z[p, 2F+D:2F+2D] = mean(fsup rows)  } of that layer, ready one launch earlier; read by the fusion launch)
+//   YL_POOL_MAX   Z[p, F:F+D] = max(feats rows)        ride in the fusion launch itself (reads feats, like its GEMM)
+// Same arithmetic, in the same (row) order, as k_pool_prepare.
+// ------------------------------------------------------------------------------------------------
+#define YL_POOL_ZERO 1
+#define YL_POOL_MAX 2
+#define YL_POOL_MEAN 4
+struct PoolRider {
+  const float* feats; const float* fsup; long ld; int D, F, P; const int* seg_ptr; float* Z; long ldz;
+  int parts, blocks;
+};
+// virtual block vb of nvb, thread tid of nthreads (grid-stride over the items of the selected parts)
+__device__ __forceinline__ void yl_pool_rider(const PoolRider& r, int vb, int nvb, int tid, int nthreads) {
+  const int wz = (r.parts & YL_POOL_ZERO) ? r.F : 0, wx = (r.parts & YL_POOL_MAX) ? r.D : 0,
+            wm = (r.parts & YL_POOL_MEAN) ? r.D : 0;
+  const int W = wz + wx + wm;
+  const long total = (long)r.P * W;
+  for (long i = (long)vb * nthreads + tid; i < total; i += (long)nvb * nthreads) {
+    const int p = (int)(i / W), c = (int)(i - (long)p * W);
+    float* z = r.Z + (long)p * r.ldz;
+    if (c < wz) { z[c] = 0.f; continue; }
+    const bool is_max = c < wz + wx;
+    const int k = is_max ? c - wz : c - wz - wx;
+    const float* src = (is_max ? r.feats : r.fsup) + k;
+    const int r0 = r.seg_ptr[p], r1 = r.seg_ptr[p + 1];
+    float best = 0.f, sm = 0.f;
+    bool any = false;
+    int q = r0;
+    for (; q + 8 <= r1; q += 8) {
+      float v[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) v[j] = src[(long)(q + j) * r.ld];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        if (!any || v[j] > best) { best = v[j]; any = true; }
+        sm += v[j];
+      }
+    }
+    for (; q < r1; ++q) {
+      const float v = src[(long)q * r.ld];
+      if (!any || v > best) { best = v; any = true; }
+      sm += v;
+    }
+    if (is_max) z[r.F + k] = best;
+    else {
+      const int cnt = r1 - r0;
+      z[2 * r.F + r.D + k] = sm / (float)(cnt > 1 ? cnt : 1);
+    }
+  }
+}
+// The node side of the NEXT conv layer computed inside the edge launch (small graphs, node tiles of <= 16 nodes), so
+// that a conv layer is ONE launch instead of two (k_gemm_nt_node3 was ~10 us of latency at N = 10 k):
+//  * UV' / root': a tile owns its destination nodes, so once their rows of f_out are final it multiplies them by the next
+//    layer's stacked [Wuv' ; Wr'] (192 x 64) — 12 column tiles x 16 v_mfma_f32_16x16x4_f32, B fragments prefetched from the
+//    packed weight — and writes the next UV rows and the next root term;
+//      Wp   Wp[(ct * 16 + ks) * 64 + l] = W'[ct * 16 + (l & 15)][4 * ks + (l >> 4)]   (coalesced B fragments)
+//      bias [192] = [uvb' ; br'];  UV [N, 2C] of the next layer (NOT the buffer this launch gathers from), root = next f_out
+//  * the node branch s' = relu(bn(s . Wn'^T)) of the next layer does not depend on this layer's messages at all: s_tiles
+//    extra workgroups run it as 64 x 64 x 64 tiles on the edge kernel's own LDS tiles and MFMA loop.
+struct EdgeNext {
+  const float* Wp; const float* bias; float* UV; long ld_uv; float* root; long ld_root;
+  const float* s_in; long ld_si; const float* Wn; const float* bn; const float* sn; const float* tn;
+  float* s_out; long ld_so; int s_tiles;
+};
+// 0: the automatic choice is not the node-tile kernel; 1 / 4: node tiles with <= 16 / <= 64 nodes (edge.hip)
+int yl_edge_tile_groups(int64_t N, int64_t E);
+// nodes per workgroup of the node-tile edge kernels, fp32 and bf16 (edge.hip); 64 for a graph without edges
+long yl_edge_tile_npt(long N, long E);
+// yolat_edge_uv_mlp2_mean_eval_variant with an optional rider / next-layer node side (edge.hip): *rode = 1 when the
+// launched kernel carried the rider, *did_next = 1 when it computed `next`; tiles_per_wg > 1: the several-tiles-per-workgroup
+// kernel where the tiles hold <= 16 nodes (the throughput regime's shape, same results)
+int yl_edge_uv_mlp2_mean_eval_impl(const float* UV, int64_t ld_uv, const int32_t* src_csr, const int32_t* dst_csr,
+                                   const float* attr_csr, const int32_t* row_ptr, int64_t N, int64_t E, const float* Wc4,
+                                   const float* b1, const float* s1, const float* t1, const float* W2, const float* b2,
+                                   const float* s2, const float* t2, int64_t C, float* f_out, int64_t ld_fo, int variant,
+                                   const PoolRider* rider, int* rode, const EdgeNext* next, int* did_next,
+                                   yolat_stream_t stream, int tiles_per_wg = 1);
+// yolat_fusion_pair_eval_x6 with an optional rider (fusion_x6.hip)
+int yl_fusion_pair_eval_x6_impl(const float* A, int64_t lda, int64_t N, int64_t D, const uint16_t* Wh, const uint16_t* Wm,
+                                const uint16_t* Wl, const float* tfold, int64_t F, const int32_t* node_seg, float* pool,
+                                int64_t ldpool, const float* S, int64_t lds, int64_t P, const uint16_t* Wsh,
+                                const uint16_t* Wsm, const uint16_t* Wsl, const float* tsfold, float* Ys, int64_t ldys,
+                                const PoolRider* rider, yolat_stream_t stream);
+// k_pool_prepare restricted to `parts` (segment.hip)
+int yl_pool_prepare_parts(const float* feats, const float* fsup, int64_t ld, int64_t D, int64_t F, const int32_t* seg_ptr,
+                          int64_t P, float* Z, int64_t ldz, int parts, yolat_stream_t stream);
+// stage profiler hooks (forward_eval.hip): HIP-event pair around one stage of a whole-forward entry point
+bool yl_profile_on();
+void yl_stage_begin(const char* name, double flops, double bytes, yolat_stream_t stream);
+void yl_stage_end(yolat_stream_t stream);
+
+// inputs of the one-launch conv stack (conv_local.hip): a prepared destination-sorted graph (row_ptr / src / dst / attr in
+// CSR order), or — edge != nullptr — the raw COO list (attr in COO order) with per-proposal edge ranges eptr
+struct YlLocalIn {
+  const int32_t *row_ptr, *src, *dst; const float* attr; const int32_t* seg_ptr;
+  const int64_t* edge; int64_t se, sc; const int32_t* eptr;
+  int32_t* status;         // non-null: the caller vouched for the batch, a violation is reported as YOLAT_STATUS_NOT_LOCAL
+};
+// seg_ptr / node_seg / eptr of a COO batch grouped by proposal + YOLAT_LOC_* violations (conv_local.hip)
+int yl_local_prep(const int64_t* edge, int64_t se, int64_t sc, const int64_t* bbox_idx, int64_t N, int64_t E, int64_t P,
+                  int32_t* seg_ptr, int32_t* node_seg, int32_t* eptr, int32_t* status, int32_t* info, bool vouched,
+                  hipStream_t st);
+
+// The launch regime of the fp32 eval forward (forward_eval.hip, yolat_eval_regime_observe): one forward at a time, or
+// several in flight on several streams.  Every shape a regime selects computes bit-identical results.
+#define YL_REGIME_LATENCY 0
+#define YL_REGIME_THROUGHPUT 1
+// yolat_graph_prepare with an optional co-scheduled node-side GEMM set (graph.hip); `regime` plans k_prep_small
+int yl_graph_prepare_impl(const int64_t* edge, int64_t stride_e, int64_t stride_c, const float* e_attr,
+                          const int64_t* bbox_idx, int64_t E, int64_t N, int64_t P, int32_t* row_ptr, int32_t* perm,
+                          int32_t* src_csr, int32_t* dst_csr, float* attr_csr, int32_t* seg_ptr, int32_t* node_seg,
+                          int32_t* work, int32_t* status, const NodeUv* extra, bool primed, yolat_stream_t stream,
+                          int regime = YL_REGIME_LATENCY);
+
+// register-chained MFMA edge stage of the bf16 forward on folded weights (edge_chain.hip)
+int yl_edge_chain_bf16(const uint16_t* UV, int64_t ld_uv, const int32_t* src_csr, const int32_t* dst_csr,
+                       const float* attr_csr, const int32_t* row_ptr, int64_t N, int64_t E, const float* Wc4,
+                       const float* s1, const uint16_t* W2f, const float* t2f, const float* root, int64_t ld_r,
+                       uint16_t* f_out, int64_t ld_fo, hipStream_t st, YlGate gate);
+// can the one-launch conv stack run this model at all (conv_local.hip)
+bool yl_conv_local_model_ok(const yolat_model_eval_bf16* mh);
+// the one-launch conv stack; *flag = flag_val when the batch turns out not to be proposal-local (conv_local.hip)
+int yl_conv_local_bf16(const yolat_model_eval_bf16* mh, const void* pack, const float* x, int64_t ldx, const YlLocalIn& in,
+                       int64_t N, int64_t E, int64_t P, uint16_t* feats, int64_t ld_feats, float* Z, int64_t ldz, int32_t* flag,
+                       int32_t flag_val, hipStream_t st);
+// bf16 fusion block with the per-proposal max, nodes and proposals in one launch (fusion_h8.hip)
+int yl_hfusion_rows8(const uint16_t* A, int64_t lda, int64_t N, int64_t D, const uint16_t* Wf, const float* tf,
+                     const int32_t* seg, float* pool, int64_t ld_pool, int64_t F, const float* As, int64_t lda_s, int64_t P,
+                     const uint16_t* Wfs, const float* tfs, float* sup_out, int64_t ld_sup, hipStream_t st);
+// the weight gradient of a wide Linear on the bf16x6 GEMM: worthwhile?, its workspace, the launch (gemm_x6.hip)
+bool yl_bwd_w_x6_ok(int64_t M, int64_t Nout, int64_t K);
+size_t yl_bwd_w_x6_work_elems(int64_t M, int64_t Nout, int64_t K);
+int yl_bwd_w_x6(const float* dY, int64_t lddy, int64_t M, int64_t Nout, const float* A, int64_t lda, int64_t K, float* dW,
+                int64_t lddw, float* db, int accumulate_db, float* work, hipStream_t st);
+// per-workgroup clock stamps of k_gemm_nt_sk_dma, nullptr unless a measurement asked for them (dense.hip)
+long long* yl_gemm_sk_dma_stamps();
+// switch of the LDS-DMA skinny GEMM and its stamps; exported for tools and tests, not part of the C ABI header (dense.hip)
+extern "C" void yolat_debug_gemm_sk_dma(int on, long long* stamps);

@@ -1,5 +1,5 @@
 // linear_sk_x6.hip — the skinny split-K Linear (few rows x long K: classifier 1 of the eval forward, P x 2304 -> 512) with
-// its fp32 operand tiles brought in by LDS-DMA, as k_gemm_nt_sk_dma<8> (common.hpp), and the products on the bf16 matrix
+// its fp32 operand tiles brought in by LDS-DMA, as k_gemm_nt_sk_dma<8> (gemm_sk.hpp), and the products on the bf16 matrix
 // cores as a bf16x6-emulated fp32 GEMM (x6.hpp) instead of the fp32-input MFMA.
 // Entry point: yolat_linear_sk_x6.
 //
@@ -20,6 +20,11 @@
 // Results: different summation grouping than the fp32 MFMA kernels (16 k per MFMA, three partial products per (i, j) pair
 // dropped at O(2^-24) relative), deterministic: fixed product order, fixed-order 8-wave reduction.  Inf / NaN as x6.hpp says.
 #include "x6.hpp"
+#include "operands.hpp"
+#include "epilogue.hpp"
+#include "gemm_nt_two.hpp"   // not launched here: see the header
+#include "gemm_sk.hpp"
+#include "internal.hpp"
 
 __global__ void __launch_bounds__(512) k_gemm_nt_sk_x6dma(const float* __restrict__ A, long lda, int rowsA,
                                                          const float* __restrict__ B, long ldb, int rowsB, Epilogue ep,

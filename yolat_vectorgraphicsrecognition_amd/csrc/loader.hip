@@ -11,7 +11,7 @@
 // device buffer with the field offsets; yolat_loader_release records an event on the consumer's stream after which the
 // slot's buffers may be rewritten.  Nothing here computes: the bytes are those of yolat_collate_batch (bit-exact tests
 // in tests/test_gpu_loader.py).
-#include "common.hpp"
+#include "base.hpp"
 #include <condition_variable>
 #include <deque>
 #include <mutex>

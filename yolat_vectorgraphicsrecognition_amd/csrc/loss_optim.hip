@@ -1,7 +1,7 @@
 // loss_optim.hip — nn.CrossEntropyLoss of DetectionLoss (architecture3cc_rpn_gp_iter2.py:363,376), the sigmoid /
 // nn.BCELoss head of classifier != 'softmax' (:132-133,362-376), and the torch.optim.Adam step of
 // cad_recognition/train.py:212,284 over one flat buffer.
-#include "common.hpp"
+#include "base.hpp"
 
 // One 1024-thread workgroup; thread t owns rows t, t+1024, ...; fixed-order tree reduction.
 __global__ void __launch_bounds__(1024) k_softmax_ce(const float* logits, long ld,

@@ -13,7 +13,7 @@
 //   3. k_nms_reduce: ONE workgroup walks the sorted boxes 64 at a time — the intra-chunk dependency is resolved by
 //      one wave on the diagonal 64 x 64 bit block, then 16 waves OR the kept rows' words into the removed-set
 //      (LDS) of the later chunks.  n <= 524 288 (the reference caps at max_nms = 30 000, train.py:47).
-#include "common.hpp"
+#include "base.hpp"
 
 #include <string.h>
 #include <rocprim/device/device_radix_sort.hpp>

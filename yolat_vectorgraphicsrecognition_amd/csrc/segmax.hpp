@@ -2,7 +2,7 @@
 // fusion_h8.hip: bf16 storage).  Replaces torch_scatter.scatter(reduce='max') of architecture3cc_rpn_gp_iter2.py:122 on
 // the fusion block's activations, which are never written to memory.
 #pragma once
-#include "common.hpp"
+#include "base.hpp"
 #ifndef FX_EPI_STAMP
 #define FX_EPI_STAMP(k) do { } while (0)      // debug builds of fusion_x6.hip define it (tools/exp/r06_fx_stamps.sh)
 #endif
@@ -203,7 +203,7 @@ __device__ __forceinline__ void fx_tab_drain(int* tab, const FxTile& t, float* p
 
 namespace {
 // training-mode epilogue: the extreme of s*z per run with its (lowest) row, as the key of wave_epilogue's key64 branch
-// (common.hpp) — same key, same tie rule
+// (epilogue.hpp) — same key, same tie rule
 __device__ __forceinline__ unsigned long long fx_key(float z, bool neg, unsigned row) {
   unsigned u = __float_as_uint(neg ? -z : z);
   u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);                // order-preserving float -> uint

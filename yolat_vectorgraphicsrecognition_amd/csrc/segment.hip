@@ -3,7 +3,8 @@
 // bbox_idx is non-decreasing (Datasets/graph_dict3.py:732) so a proposal is a contiguous row range
 // [seg_ptr[p], seg_ptr[p+1]).  One thread per (proposal, column): threads of a workgroup cover 256
 // consecutive columns -> every row read is a coalesced 1 KiB burst; no atomics, fixed row order.
-#include "common.hpp"
+#include "base.hpp"
+#include "internal.hpp"
 
 __global__ void __launch_bounds__(256) k_segment_mean_fwd(const float* X, long ldx, int D,
                                                           const float* xs, const float* xb,

@@ -9,7 +9,8 @@
 //   edge'[q]     = (o2n[edge[eid[q],0]], o2n[edge[eid[q],1]]);  an endpoint outside the subset raises the
 //                  YOLAT_STATUS_EDGE_RANGE flag (the reference raises KeyError)
 //   bbox_idx'[i] = number of positions 0 < t <= i with bbox_idx[node_ids[t]] != bbox_idx[node_ids[t-1]]
-#include "common.hpp"
+#include "base.hpp"
+#include "internal.hpp"
 
 static __global__ void k_expand_ranges(const int* __restrict__ start, const int* __restrict__ prefix, int S,
                                        int total, int* out) {
@@ -223,10 +224,6 @@ extern "C" int yolat_fixup_offsets(int64_t* edge, int64_t E, const int64_t* edge
 //   k_predict_gather    logits / boxes of those rows, boxes enlarged by 5 % about their centre (:341-346, same fp32 steps)
 // One host read (out[]: total, flag, slice_image_bbox, rows) ends the call.
 // ------------------------------------------------------------------------------------------------
-int yl_local_prep(const int64_t* edge, int64_t se, int64_t sc, const int64_t* bbox_idx, int64_t N, int64_t E, int64_t P,
-                  int32_t* seg_ptr, int32_t* node_seg, int32_t* eptr, int32_t* status, int32_t* info, bool vouched,
-                  hipStream_t st);
-
 static __global__ void k_predict_zero(int* p, int n) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) p[i] = 0;

@@ -32,7 +32,7 @@
 // Phases (for the data-parallel exchange, which stays with the caller's process group): 1 = everything up to the point
 // where the gradients of the fusion blocks and the classifier (the "head" bucket, 93 % of the bytes) are final on `stream`;
 // 2 = the conv layers' backward; 4 = Adam.  The caller issues its all-reduces between the calls.
-#include "common.hpp"
+#include "base.hpp"
 #include <stdlib.h>
 #include <string.h>
 

@@ -11,11 +11,11 @@
 //   * |x| < 2^-110 or so: the low terms underflow bfloat16's normal range only when x itself is within 2^16 of the
 //     smallest normal fp32 (bf16 shares fp32's exponent range), i.e. products that are far below fp32's own rounding of
 //     any sum they enter.
-// Strict-parity runs select the fp32-input MFMA kernels everywhere with ONE switch, YOLAT_STRICT_FP32=1 (common.hpp
+// Strict-parity runs select the fp32-input MFMA kernels everywhere with ONE switch, YOLAT_STRICT_FP32=1 (base.hpp
 // yl_strict_fp32; plan.py / ops.py read the same variable): IEEE propagation and the fp32 MFMA summation order, at the
 // fp32 vector-ALU rate (DESIGN.md "fp32 MFMA and the vector ALU").
 #pragma once
-#include "common.hpp"
+#include "base.hpp"
 
 typedef __bf16 fx_bf16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned fx_u32x4 __attribute__((ext_vector_type(4)));

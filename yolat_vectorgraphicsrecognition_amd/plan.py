@@ -164,7 +164,7 @@ class EvalPlan(object):
             tfr = torch.cat([uvb, cv.lin_r.bias.detach()], 0)
             keep += [wfr, tfr]
         if chain:
-            # ... in the form the PREVIOUS layer's edge kernel consumes (small graphs: EdgeNext, csrc/common.hpp):
+            # ... in the form the PREVIOUS layer's edge kernel consumes (small graphs: EdgeNext, csrc/internal.hpp):
             # the weight in 16x16x4 MFMA B-fragment order
             wnx = wfr.view(12, 16, 16, 4).permute(0, 2, 3, 1).contiguous()                 # [ct, ks, k & 3, row]
             keep.append(wnx)
