@@ -6,13 +6,13 @@ mean of the node branch) + the segment max of :122 over the concat columns; Attr
 gcn_lib/sparse/torch_vertex.py:319-337.  Oracle: oracle/oracle_torch.py (fp32 / fp64 on the CPU).  Tolerances are the
 bf16-storage ones of tests/test_gpu_bf16.py (<= 1e-2 of the scale, rms)."""
 import ctypes
-import os
 
 import numpy as np
 import pytest
 import torch
 
 import golden_util as gu
+from conv_local_util import _mode, _run_stack, _run_stack_coo
 from oracle import oracle_torch as orc
 
 pytestmark = pytest.mark.gpu
@@ -28,23 +28,6 @@ def _yv():
 
 def _model(yv, optkw, seed):
     return gu.fill_state_(yv.SparseCADGCN(yv.Opt(**optkw)), seed).cuda().eval().set_eval_precision("bf16")
-
-
-class _mode(object):
-    """YOLAT_CONV_LOCAL for the duration of a block (read per call by yolat_forward_eval_bf16)."""
-
-    def __init__(self, v):
-        self.v = str(v)
-
-    def __enter__(self):
-        self.old = os.environ.get("YOLAT_CONV_LOCAL")
-        os.environ["YOLAT_CONV_LOCAL"] = self.v
-
-    def __exit__(self, *a):
-        if self.old is None:
-            os.environ.pop("YOLAT_CONV_LOCAL", None)
-        else:
-            os.environ["YOLAT_CONV_LOCAL"] = self.old
 
 
 def _rel(got, want):
@@ -67,33 +50,6 @@ def _ragged(yv, P, seed, lo=2, hi=40, edge_factor=2.1, classes=17, edges_per_pro
     d = yv.synth_graph(num_proposals=P, nodes_lo=lo, nodes_hi=hi, edge_factor=edge_factor, n_classes=classes, seed=seed,
                        edges_per_proposal=edges_per_proposal)
     return d
-
-
-def _run_stack(yv, model, d):
-    """yolat_conv_stack_local_bf16 on the model's packed weights: (feats [N,D] bf16, Z [P, 2(F+D)] fp32, flag)."""
-    from yolat_vectorgraphicsrecognition_amd import ops
-    from yolat_vectorgraphicsrecognition_amd._lib import lib, check, GraphCsr
-    with torch.no_grad():
-        model(d, None)                      # builds the plan (weights folded / packed)
-    plan = model._yolat_plan
-    h = plan._desc_h
-    assert h is not None and h.conv_local, "the plan did not pack the conv stack"
-    base = plan._desc
-    N, P = d.x.shape[0], d.bbox.shape[0]
-    dev = torch.device("cuda")
-    g = ops.build_graph(d.edge.to(dev), d.e_attr.to(dev), d.bbox_idx.to(dev), N, P)
-    g.check_status()
-    D, F = base.C * base.n_blocks_out, base.F
-    feats = torch.full((N, D), float("nan"), dtype=torch.bfloat16, device=dev)
-    Z = torch.full((P, 2 * (F + D)), float("nan"), dtype=torch.float32, device=dev)
-    flag = torch.zeros(1, dtype=torch.int32, device=dev)
-    x = d.x.to(dev).contiguous()
-    gc = GraphCsr(*g.device_pointers())
-    check(lib.yolat_conv_stack_local_bf16(ctypes.byref(h), h.conv_local, x.data_ptr(), x.stride(0), ctypes.byref(gc), N, g.E,
-                                          P, feats.data_ptr(), D, Z.data_ptr(), Z.stride(0), flag.data_ptr(),
-                                          torch.cuda.current_stream().cuda_stream), "yolat_conv_stack_local_bf16")
-    torch.cuda.synchronize()
-    return feats, Z, int(flag.item()), (F, D)
 
 
 def _oracle_backbone(optkw, seed, d):
@@ -303,33 +259,6 @@ def _shuffle_inside_proposals(d, seed):
     d.edge = d.edge[perm].contiguous()
     d.e_attr = d.e_attr[perm].contiguous()
     return d
-
-
-def _run_stack_coo(yv, model, d):
-    """yolat_conv_stack_local_bf16_coo on the raw edge list: (feats, Z, flag, status)"""
-    from yolat_vectorgraphicsrecognition_amd import ops
-    from yolat_vectorgraphicsrecognition_amd._lib import lib, check
-    with torch.no_grad():
-        model(d, None)
-    plan = model._yolat_plan
-    h, base = plan._desc_h, plan._desc
-    N, P, E = d.x.shape[0], d.bbox.shape[0], d.edge.shape[0]
-    dev = torch.device("cuda")
-    D, F = base.C * base.n_blocks_out, base.F
-    feats = torch.full((N, D), float("nan"), dtype=torch.bfloat16, device=dev)
-    Z = torch.full((P, 2 * (F + D)), float("nan"), dtype=torch.float32, device=dev)
-    flag = torch.zeros(1, dtype=torch.int32, device=dev)
-    status = torch.zeros(1, dtype=torch.int32, device=dev)
-    x, edge, attr, bb = d.x.to(dev).contiguous(), d.edge.to(dev), d.e_attr.to(dev).contiguous(), d.bbox_idx.to(dev)
-    need = int(lib.yolat_batch_locality_workspace_bytes(N, E, P))
-    ws = torch.empty(need + 16, dtype=torch.uint8, device=dev)
-    check(lib.yolat_conv_stack_local_bf16_coo(ctypes.byref(h), h.conv_local, x.data_ptr(), x.stride(0), edge.data_ptr(),
-                                              edge.stride(0), edge.stride(1), attr.data_ptr(), bb.data_ptr(), N, E, P,
-                                              feats.data_ptr(), D, Z.data_ptr(), Z.stride(0), flag.data_ptr(),
-                                              status.data_ptr(), ws.data_ptr(), ws.numel(),
-                                              torch.cuda.current_stream().cuda_stream), "yolat_conv_stack_local_bf16_coo")
-    torch.cuda.synchronize()
-    return feats, Z, int(flag.item()), int(status.item()), (F, D)
 
 
 @pytest.mark.parametrize("blocks,blocks_out,P,seed,shape", [

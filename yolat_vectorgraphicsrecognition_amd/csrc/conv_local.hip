@@ -11,16 +11,19 @@
 // (~135 MB at N = 200 k / E = 1.2 M instead of the ~1.8 GB the per-layer launches move: UV [N,128] + root [N,64] + f / s
 // [N,64] written and re-gathered per layer).
 //
-// Structure.  A workgroup (256 threads = 4 waves, 65.5 KB of LDS: two per CU) is PERSISTENT over a contiguous group of
-// proposals and packs them greedily into tiles of <= 64 nodes / <= 640 edges.  Per tile, everything lives in LDS:
-//   UV [64][128] bf16 (per-node products U' | V' of the factorised first edge Linear), R [64][64] fp32 (root Linear),
-//   f [64][64] bf16 (layer output = next layer's input), s [64][64] bf16 (node branch), packed edge ids, e_attr as bf16
+// Structure.  A workgroup of NW waves (NW = 4: 256 threads, 77 KB of LDS, two per CU; NW = 8: 512 threads, 141 KB, one
+// per CU) is PERSISTENT over a contiguous group of proposals and packs them greedily into tiles of <= T = 16 NW nodes /
+// <= ET = 128 NW edges (64 / 512 or 128 / 1024).  Per tile, everything lives in LDS:
+//   UV [T][128] bf16 (per-node products U' | V' of the factorised first edge Linear), R [T][64] fp32 (root Linear),
+//   f [T][64] bf16 (layer output = next layer's input), s [T][64] bf16 (node branch), packed edge ids, e_attr as bf16
 //   (hi, lo) MFMA fragments, the tile's row_ptr.
 // Per layer:
-//   node phase   wave g computes output group g of OUT^T[256 ch][64 nodes] = W' . f^T (g: U | V | root | node branch) on
+//   node phase   wave g (NW = 8: g & 3, on the 64-node half g >> 2) computes output group g of OUT^T[256 ch][64 nodes] =
+//                W' . f^T (g: U | V | root | node branch) on
 //                v_mfma_f32_32x32x16_bf16 — transposed, so a lane holds 4 CONSECUTIVE channels of one node and writes
 //                8-byte (bf16) / 16-byte (fp32) LDS rows; BatchNorm scales are folded into the packed weights, shifts are
-//                the accumulators' start values.  Layer 0 (K = in_channels <= 8 raw features): fp32 FMAs.
+//                the accumulators' start values.  Layer 0 (K = in_channels <= 8 raw features): x and W' as bf16 (hi, lo)
+//                pairs in one k-step, three of the four cross terms.
 //   edge phase   the register-chained MFMA pipeline of edge_chain.hip (layer 1 transposed through identity fragments on
 //                the gathered 16-byte row chunks, ReLU + bf16 in registers = layer 2's A operand), with the gathers served
 //                by LDS.  A wave owns two edge streams = the in-edges of two runs of <= 16 consecutive nodes.  NEW: the
