@@ -231,6 +231,60 @@ int yolat_bn_relu_bwd(const float* dZ, int64_t lddz, const float* Y, int64_t ldy
                       float* work, yolat_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The leaky activations of gcn_lib/sparse/torch_nn.py:9-20 — LeakyReLU(0.2), PReLU(num_parameters = 1):
+ *   act(y) = y > 0 ? y : a * y.   `slope` points to the ONE float a in device memory (a PReLU weight, or a constant the
+ * caller owns): every launch reads it, so an in-place edit is seen by the next call and by a hipGraph replay.  a may be
+ * negative or above 1 (the activation is then not monotone); NaN propagates.  csrc/act.hip.
+ * ------------------------------------------------------------------------------------------ */
+#define YOLAT_ACT_RELU 0
+#define YOLAT_ACT_LEAKYRELU 1
+#define YOLAT_ACT_PRELU 2
+/* Z[M,C] = act(Y*scale + shift); scale == NULL: Z = act(Y).  Z may be Y.                           */
+int yolat_scale_shift_act(const float* Y, int64_t ldy, int64_t M, int64_t C, const float* scale,
+                          const float* shift, const float* slope, float* Z, int64_t ldz,
+                          yolat_stream_t stream);
+/* Y [N,F]; out[p, 0:F] = max over the rows [seg_ptr[p], seg_ptr[p+1]) of act(Y[r, 0:F]), 0 for a proposal without rows:
+ * the maximum of the ACTIVATED values, exact for signed ones (no atomics: one writer per element).              */
+int yolat_segment_act_max(const float* Y, int64_t ldy, int64_t N, int64_t F, const float* slope,
+                          const int32_t* seg_ptr, int64_t P, float* out, int64_t ldo, yolat_stream_t stream);
+/* Backward of Z = act(BN_train(Y)) given dZ, as yolat_bn_relu_bwd: with y' = scale*Y + shift RECOMPUTED (never the sign
+ * of a stored activation), dyh = y' > 0 ? dZ : a*dZ; dgamma, dbeta, dY as there; dslope (nullable, 1 float)
+ * (+)= sum_{y' <= 0} dZ*y'.  Every sum in a fixed order: two calls give identical bits.
+ *   work: fp32 scratch of yolat_bn_act_bwd_work_elems(M,C).                                                       */
+size_t yolat_bn_act_bwd_work_elems(int64_t M, int64_t C);
+int yolat_bn_act_bwd(const float* dZ, int64_t lddz, const float* Y, int64_t ldy, int64_t M, int64_t C,
+                     const float* save_mean, const float* save_invstd, const float* scale, const float* shift,
+                     const float* slope, float* dgamma, float* dbeta, float* dslope, int accumulate, float* dY,
+                     int64_t lddy, float* work, yolat_stream_t stream);
+/* yolat_fusion_pair_eval (any D, F) for a leaky activation, the materialising form: pool[p, 0:F] = max over the nodes of proposal p of
+ * act_f(sf*(A.Wf^T + bf) + tf) — written, not merged: needs no zeroed pool; Ys[P,F] = act_s(ss*(S.Wfs^T + bfs) + ts)
+ * (S == NULL: the node half alone).  The BatchNorm output of a column range is materialised in `work`
+ * (yolat_fusion_pair_eval_act_work_elems(N,F) floats, at most 64 MiB) and pooled by yolat_segment_act_max: 2 launches
+ * per range + 2 for the super half, where the ReLU pair is one launch.  seg_ptr [P+1]: proposal row ranges.        */
+/* Start values of the SIGNED per-proposal maximum of yolat_fusion_pair_eval_x6_act: pool[p, 0:F] = -inf for a proposal
+ * with rows, 0 for one without (which nothing touches afterwards).                                                  */
+int yolat_pool_init_signed(const int32_t* seg_ptr, int64_t P, int64_t F, float* pool, int64_t ldpool,
+                           yolat_stream_t stream);
+/* yolat_fusion_pair_eval_x6 for a leaky activation — the activation-aware instantiation of the bf16x6 rows kernel
+ * (D in {64, 128}, F % 64 == 0, operands as there; tfold / tsfold the folded shifts): the activation is applied per
+ * element BEFORE the run-length maximum, and a run is merged into the pool by atomicMax on the int bits (sign bit clear)
+ * or atomicMin on the unsigned bits (sign bit set) — exact for signed values, order-independent, no decode pass.  The
+ * call enqueues yolat_pool_init_signed (one extra launch over the ReLU pair), then the kernel; the super half stores
+ * act_s(.).  node_seg [N]: proposal of each row; seg_ptr [P+1]: the same as row ranges.                             */
+int yolat_fusion_pair_eval_x6_act(const float* A, int64_t lda, int64_t N, int64_t D, const uint16_t* Wh,
+                                  const uint16_t* Wm, const uint16_t* Wl, const float* tfold, int64_t F,
+                                  const float* slope_f, const int32_t* node_seg, const int32_t* seg_ptr, float* pool,
+                                  int64_t ldpool, const float* S, int64_t lds, int64_t P, const uint16_t* Wsh,
+                                  const uint16_t* Wsm, const uint16_t* Wsl, const float* tsfold, const float* slope_s,
+                                  float* Ys, int64_t ldys, yolat_stream_t stream);
+size_t yolat_fusion_pair_eval_act_work_elems(int64_t N, int64_t F);
+int yolat_fusion_pair_eval_act(const float* A, int64_t lda, int64_t N, int64_t D, const float* Wf, const float* bf,
+                               const float* sf, const float* tf, int64_t F, const float* slope_f,
+                               const int32_t* seg_ptr, float* pool, int64_t ldpool, const float* S, int64_t lds,
+                               int64_t P, const float* Wfs, const float* bfs, const float* sfs, const float* tfs,
+                               const float* slope_s, float* Ys, int64_t ldys, float* work, yolat_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Edge convolution AttrRelativeEdgeConvGlobalPool2 (gcn_lib/sparse/torch_vertex.py:288-341):
  *   m_e = nn([x_i, x_j - x_i, a_e]);  out_i = mean_{e->i} m_e + lin_r(x_i)
  * All [E,*] tensors are in CSR (destination-sorted) order.
@@ -544,7 +598,10 @@ typedef struct {
 #define YOLAT_CLS1_X6_MIN_ROWS 1024
 #define YOLAT_NODE_X6_MIN_ROWS 65536
 typedef struct {
-  int32_t n_blocks, n_blocks_out, n_classes, reserved;
+  int32_t n_blocks, n_blocks_out, n_classes;
+  int32_t act;                                /* YOLAT_ACT_*: the activation of fusion_block, fusion_block_super,
+                                               * prediction_cls.0 and .1 (the conv layers' MLPs are always ReLU); 0 = ReLU:
+                                               * exactly the launches of a descriptor that never heard of the field          */
   int64_t C;                                  /* n_filters (64)                                  */
   int64_t F;                                  /* fusion width (1024)                             */
   int64_t H1, H2;                             /* classifier hidden widths (512, 256)             */
@@ -570,6 +627,9 @@ typedef struct {
    * (sc1 (rows) * Wc1), tc1_gx = sc1*bc1 + tc1.  Used when P >= YOLAT_CLS1_X6_MIN_ROWS.                          */
   const uint16_t *Wc1_gx;
   const float *tc1_gx;
+  /* act != 0: the slope of each of the four sites (device pointers to one float, read by every launch) in the order
+   * fusion_block, fusion_block_super, prediction_cls.0, prediction_cls.1.  Not read when act == 0.                  */
+  const float *act_slope[4];
 } yolat_model_eval;
 
 /* workspace (bytes) needed by yolat_forward_eval for a batch of N nodes / E edges / P proposals */

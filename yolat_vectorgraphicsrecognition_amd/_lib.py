@@ -31,12 +31,12 @@ class ConvEval(ctypes.Structure):
 class ModelEval(ctypes.Structure):
     """yolat_model_eval (include/yolat_hip.h)"""
     _fields_ = ([("n_blocks", ctypes.c_int32), ("n_blocks_out", ctypes.c_int32), ("n_classes", ctypes.c_int32),
-                 ("reserved", ctypes.c_int32), ("C", c_i64), ("F", c_i64), ("H1", c_i64), ("H2", c_i64),
+                 ("act", ctypes.c_int32), ("C", c_i64), ("F", c_i64), ("H1", c_i64), ("H2", c_i64),
                  ("conv", ConvEval * YOLAT_MAX_LAYERS)] +
                 [(n, c_p) for n in ("Wf", "bf", "sf", "tf", "Wf_hi", "Wf_mid", "Wf_lo", "tf_fold", "Wfs_hi", "Wfs_mid",
                                     "Wfs_lo", "tfs_fold", "Wfs", "bfs", "sfs", "tfs", "Wc1", "bc1", "sc1", "tc1", "Wc2",
                                     "bc2", "sc2", "tc2", "Wc3", "bc3")] +
-                [("Wc_x6", c_p * 3), ("tc_fold", c_p * 3), ("Wc1_gx", c_p), ("tc1_gx", c_p)])
+                [("Wc_x6", c_p * 3), ("tc_fold", c_p * 3), ("Wc1_gx", c_p), ("tc1_gx", c_p), ("act_slope", c_p * 4)])
 
 
 class BnCsrGrad(ctypes.Structure):
@@ -195,6 +195,18 @@ SIGNATURES = {
     "yolat_eval_regime_counts": (c_int, [c_p]),
     "yolat_gather_rows": (c_int, [c_p, c_i64, c_p, c_i64, c_i64, c_p, c_i64, c_p]),
     "yolat_bn_stats_elems": (c_sz, [c_i64, c_i64]),
+    # leaky activations (act.hip)
+    "yolat_scale_shift_act": (c_int, [c_p, c_i64, c_i64, c_i64, c_p, c_p, c_p, c_p, c_i64, c_p]),
+    "yolat_segment_act_max": (c_int, [c_p, c_i64, c_i64, c_i64, c_p, c_p, c_i64, c_p, c_i64, c_p]),
+    "yolat_bn_act_bwd_work_elems": (c_sz, [c_i64, c_i64]),
+    "yolat_bn_act_bwd": (c_int, [c_p, c_i64, c_p, c_i64, c_i64, c_i64, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_int, c_p,
+                                  c_i64, c_p, c_p]),
+    "yolat_pool_init_signed": (c_int, [c_p, c_i64, c_i64, c_p, c_i64, c_p]),
+    "yolat_fusion_pair_eval_x6_act": (c_int, [c_p, c_i64, c_i64, c_i64, c_p, c_p, c_p, c_p, c_i64, c_p, c_p, c_p, c_p, c_i64,
+                                               c_p, c_i64, c_i64, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_p]),
+    "yolat_fusion_pair_eval_act_work_elems": (c_sz, [c_i64, c_i64]),
+    "yolat_fusion_pair_eval_act": (c_int, [c_p, c_i64, c_i64, c_i64, c_p, c_p, c_p, c_p, c_i64, c_p, c_p, c_p, c_i64, c_p,
+                                            c_i64, c_i64, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_p, c_p]),
     "yolat_linear_fwd": (c_int, [c_p, c_i64, c_i64, c_i64, c_p, c_p, c_int,
                                  c_p, c_i64, c_p, c_i64, c_p, c_p, c_int,
                                  c_p, c_i64, c_int, c_p, c_p]),

@@ -127,6 +127,7 @@ class SparseCADGCN(nn.Module):
         self.n_classes = opt.n_classes
         self.classifier = opt.classifier
         self.class_specific = opt.class_specific
+        self.act = str(act).lower()
         self.dim_stat = 0
         self.cls_net = Backbone(opt)
         d = (self.cls_net.fusion_dims + 1024) * 2 + self.dim_stat
@@ -384,6 +385,9 @@ class SparseCADGCN(nn.Module):
         Training always runs in fp32."""
         if precision not in ("fp32", "bf16"):
             raise ValueError("precision must be 'fp32' or 'bf16'")
+        if precision != "fp32" and not engine.model_is_relu(self):
+            raise ValueError("eval precision %r covers act = relu only; this model was built with act = %r "
+                             "(fp32 runs it)" % (precision, self.act))
         if self.__dict__.get("_yolat_precision", "fp32") != precision:
             self.__dict__["_yolat_precision"] = precision
             self.__dict__.pop("_yolat_plans", None)
@@ -405,6 +409,9 @@ class SparseCADGCN(nn.Module):
             other shapes raise ValueError at the first step.  Numerics contract: INTEGRATION.md."""
         if precision not in ("fp32", "bf16", "bf16_dense"):
             raise ValueError("precision must be 'fp32', 'bf16' or 'bf16_dense'")
+        if precision != "fp32" and not engine.model_is_relu(self):
+            raise ValueError("train precision %r covers act = relu only; this model was built with act = %r "
+                             "(fp32 runs it)" % (precision, self.act))
         self.__dict__["_yolat_train_precision"] = precision
         return self
 

@@ -12,6 +12,7 @@ struct Plan {
   float* feats; float* fsup; float* Z; float* c1; float* c2;
   float* gx_work;                                      // split-K partials of cls1 on yolat_gemm_x6 (few proposals)
   uint16_t* Zs;                                        // Z pre-split for the skinny bf16x6 classifier (few proposals)
+  float* act_work;                                     // leaky activation: BatchNorm output of a fusion column range
   size_t bytes;
 };
 
@@ -36,6 +37,10 @@ Plan carve(const yolat_model_eval* m, long N, long E, long P, void* ws) {
   p.gx_work = gxw ? c.take<float>((long)gxw) : nullptr;
   p.Zs = (P <= YOLAT_CLS_X6_MAX_ROWS && m->Wc_x6[0] && (2 * (F + D)) % 16 == 0)
              ? c.take<uint16_t>((long)yolat_split_bf16x3_packed_elems(P, 2 * (F + D))) : nullptr;
+  // (carved last and only for a leaky activation: a ReLU descriptor's layout and size are what they were)
+  const bool act_x6 = m->Wf_hi && m->Wf_mid && m->Wf_lo && m->tf_fold && m->Wfs_hi && m->Wfs_mid && m->Wfs_lo && m->tfs_fold &&
+                      (D == 64 || D == 128) && F % 64 == 0 && (long)P * 2 * (F + D) < (1LL << 32);     // (forward_eval_impl's fusion_x6)
+  p.act_work = m->act != YOLAT_ACT_RELU && !act_x6 ? c.take<float>((long)yolat_fusion_pair_eval_act_work_elems(N, F)) : nullptr;
   p.bytes = c.off + 256;
   return p;
 }
@@ -231,10 +236,10 @@ extern "C" int yolat_eval_regime_counts(int64_t out[2]) {
 
 // cls1 on the skinny bf16x6 kernel: K = 2304 is long enough that splitting Z once (a small launch) beats splitting it
 // on the fly in each of the H1/32 column tiles
-static int cls1_x6(const float* Z, long ZW, long P, uint16_t* Zs, const uint16_t* Wp, const float* shift, long H1,
+static int cls1_x6(const float* Z, long ZW, long P, uint16_t* Zs, const uint16_t* Wp, const float* shift, int relu, long H1,
                    float* c1, yolat_stream_t stream) {
   YL_TRY(yolat_split_bf16x3_packed(Z, ZW, P, ZW, nullptr, Zs, stream));
-  return yolat_linear_x6_pre(Zs, P, ZW, Wp, shift, 1, H1, c1, H1, stream);
+  return yolat_linear_x6_pre(Zs, P, ZW, Wp, shift, relu, H1, c1, H1, stream);
 }
 
 extern "C" size_t yolat_forward_eval_workspace_bytes(const yolat_model_eval* m, int64_t N, int64_t E,
@@ -292,6 +297,14 @@ static int forward_eval_impl(const yolat_model_eval* m, const float* x, int64_t 
   if (m->n_blocks < 1 || m->n_blocks > YOLAT_MAX_LAYERS || m->n_blocks_out < 1 ||
       m->n_blocks_out > m->n_blocks)
     return YOLAT_E_INVALID;
+  // leaky activation (act.hip) at the four sites behind the conv stack: every GEMM below runs with its ReLU switched off
+  // and the activation follows as a launch of its own; act == 0 takes none of these branches
+  const bool leaky = m->act != YOLAT_ACT_RELU;
+  if (leaky) {
+    if (m->act != YOLAT_ACT_LEAKYRELU && m->act != YOLAT_ACT_PRELU) return YOLAT_E_INVALID;
+    for (int i = 0; i < 4; ++i) if (!m->act_slope[i]) return YOLAT_E_INVALID;
+  }
+  const int relu = leaky ? 0 : 1;
   Plan p = carve(m, N, E, P, workspace);
   if (p.bytes > workspace_bytes) return YOLAT_E_INVALID;
   if (g != nullptr) YL_TRY(yl_adopt_graph(g, E, &p));      // prepared graph: the kernels read the caller's arrays
@@ -486,7 +499,9 @@ static int forward_eval_impl(const yolat_model_eval* m, const float* x, int64_t 
   // ---- fusion over nodes + per-proposal max (arch:61-63,122)
   float* sup = p.Z + 2 * F + D;
   const bool ride_max = ride_b.blocks > 0 && (pool_done & YL_POOL_ZERO);       // riders all the way, or not at all
-  const int pool_left = (YL_POOL_ZERO | YL_POOL_MAX | YL_POOL_MEAN) & ~pool_done & ~(ride_max ? YL_POOL_MAX : 0);
+  // (leaky: the pooled fusion maxima start from yolat_pool_init_signed or are written outright — no zero pass)
+  const int pool_left = (YL_POOL_ZERO | YL_POOL_MAX | YL_POOL_MEAN) & ~pool_done & ~(ride_max ? YL_POOL_MAX : 0) &
+                        ~(leaky ? YL_POOL_ZERO : 0);
   if (pool_left) {
     YL_STAGE("pool_prepare[max(feats), mean(fsup), zero]", 2.0 * N * D, 8.0 * N * D + 4.0 * P * (F + 2 * D),
              yl_pool_prepare_parts(p.feats, p.fsup, D, D, F, p.seg_ptr, P, p.Z, ZW, pool_left, stream));
@@ -494,6 +509,22 @@ static int forward_eval_impl(const yolat_model_eval* m, const float* x, int64_t 
   // fusion block over the nodes + per-proposal max, and fusion_block_super over the per-proposal means
   // (arch:61-63,65-69,122): two independent GEMMs in one flattened launch
   snprintf(nm, sizeof nm, "fusion_gemm+segmax[N x %ld -> %ld -> P] | super[P x %ld -> %ld]", D, F, D, F);
+  if (leaky && fusion_x6) {
+    // signed pooling (segmax.hpp fx_signed_max): the activation-aware instantiation of the rows kernel on start values of
+    // -inf / 0 per proposal — one launch more than the ReLU pair
+    YL_STAGE("pool_init_signed[P x F]", 0, 4.0 * P * F, yolat_pool_init_signed(p.seg_ptr, P, F, p.Z, ZW, stream));
+    YL_STAGE(nm, 2.0 * (N + P) * D * F, 4.0 * (N * D + 2.0 * D * F + 2.0 * P * F + N + P * D),
+             yl_fusion_pair_eval_x6_impl(p.feats, D, N, D, m->Wf_hi, m->Wf_mid, m->Wf_lo, m->tf_fold, F, p.node_seg, p.Z, ZW,
+                                         sup, ZW, P, m->Wfs_hi, m->Wfs_mid, m->Wfs_lo, m->tfs_fold, p.Z + F + D, ZW,
+                                         ride_max ? &ride_b : nullptr, stream, m->act_slope[0], m->act_slope[1]));
+  } else if (leaky) {
+    // other widths: the BatchNorm output of the fusion block materialised per column range, activated and pooled by
+    // yolat_segment_act_max (the activation is applied per element BEFORE the maximum either way)
+    YL_STAGE(nm, 2.0 * (N + P) * D * F, 4.0 * (N * D + 2.0 * D * F + 2.0 * P * F + N + P * D + 2.0 * N * F),
+             yolat_fusion_pair_eval_act(p.feats, D, N, D, m->Wf, m->bf, m->sf, m->tf, F, m->act_slope[0], p.seg_ptr, p.Z, ZW,
+                                        sup, ZW, P, m->Wfs, m->bfs, m->sfs, m->tfs, m->act_slope[1], p.Z + F + D, ZW,
+                                        p.act_work, stream));
+  } else
   YL_STAGE(nm, 2.0 * (N + P) * D * F, 4.0 * (N * D + 2.0 * D * F + 2.0 * P * F + N + P * D),
            fusion_x6 ? yl_fusion_pair_eval_x6_impl(p.feats, D, N, D, m->Wf_hi, m->Wf_mid, m->Wf_lo, m->tf_fold, F,
                                                    p.node_seg, p.Z, ZW, sup, ZW, P, m->Wfs_hi, m->Wfs_mid, m->Wfs_lo,
@@ -515,16 +546,22 @@ static int forward_eval_impl(const yolat_model_eval* m, const float* x, int64_t 
                        (long)yl_cdiv(P, 64) * yl_cdiv(m->H1, 64) < 160 && yl_aligned16(p.Z) && yl_aligned16(m->Wc1);
   snprintf(nm, sizeof nm, "cls1[P x %ld -> %ld]", ZW, (long)m->H1);
   YL_STAGE(nm, 2.0 * P * ZW * m->H1, 4.0 * (P * ZW + ZW * m->H1 + P * m->H1),
-           cls1_gx ? yolat_gemm_x6(p.Z, ZW, P, ZW, m->Wc1_gx, m->tc1_gx, 1, m->H1, p.c1, m->H1, p.gx_work, stream)
-           : cls_x6 ? cls1_x6(p.Z, ZW, P, p.Zs, m->Wc_x6[0], m->tc_fold[0], m->H1, p.c1, stream)
-           : cls1_sk ? yolat_linear_sk_x6(p.Z, ZW, P, ZW, m->Wc1, ZW, m->bc1, m->H1, m->sc1, m->tc1, 1, p.c1, m->H1, stream)
-                  : yolat_linear_fwd(p.Z, ZW, P, ZW, nullptr, nullptr, 0, m->Wc1, ZW, m->bc1, m->H1, m->sc1, m->tc1, 1,
+           cls1_gx ? yolat_gemm_x6(p.Z, ZW, P, ZW, m->Wc1_gx, m->tc1_gx, relu, m->H1, p.c1, m->H1, p.gx_work, stream)
+           : cls_x6 ? cls1_x6(p.Z, ZW, P, p.Zs, m->Wc_x6[0], m->tc_fold[0], relu, m->H1, p.c1, stream)
+           : cls1_sk ? yolat_linear_sk_x6(p.Z, ZW, P, ZW, m->Wc1, ZW, m->bc1, m->H1, m->sc1, m->tc1, relu, p.c1, m->H1, stream)
+                  : yolat_linear_fwd(p.Z, ZW, P, ZW, nullptr, nullptr, 0, m->Wc1, ZW, m->bc1, m->H1, m->sc1, m->tc1, relu,
                                      p.c1, m->H1, 0, nullptr, stream));
+  if (leaky)
+    YL_STAGE("cls1_act[P x H1]", 1.0 * P * m->H1, 8.0 * P * m->H1,
+             yolat_scale_shift_act(p.c1, m->H1, P, m->H1, nullptr, nullptr, m->act_slope[2], p.c1, m->H1, stream));
   snprintf(nm, sizeof nm, "cls2[P x %ld -> %ld]", (long)m->H1, (long)m->H2);
   YL_STAGE(nm, 2.0 * P * m->H1 * m->H2, 4.0 * (P * m->H1 + m->H1 * m->H2 + P * m->H2),
-           cls_x6 ? yolat_linear_x6(p.c1, m->H1, P, m->H1, m->Wc_x6[1], m->tc_fold[1], 1, m->H2, p.c2, m->H2, stream)
+           cls_x6 ? yolat_linear_x6(p.c1, m->H1, P, m->H1, m->Wc_x6[1], m->tc_fold[1], relu, m->H2, p.c2, m->H2, stream)
                   : yolat_linear_fwd(p.c1, m->H1, P, m->H1, nullptr, nullptr, 0, m->Wc2, m->H1, m->bc2, m->H2, m->sc2,
-                                     m->tc2, 1, p.c2, m->H2, 0, nullptr, stream));
+                                     m->tc2, relu, p.c2, m->H2, 0, nullptr, stream));
+  if (leaky)
+    YL_STAGE("cls2_act[P x H2]", 1.0 * P * m->H2, 8.0 * P * m->H2,
+             yolat_scale_shift_act(p.c2, m->H2, P, m->H2, nullptr, nullptr, m->act_slope[3], p.c2, m->H2, stream));
   snprintf(nm, sizeof nm, "cls3[P x %ld -> %d]", (long)m->H2, (int)m->n_classes);
   YL_STAGE(nm, 2.0 * P * m->H2 * m->n_classes, 4.0 * (P * m->H2 + m->H2 * m->n_classes + P * m->n_classes),
            cls_x6 ? yolat_linear_x6(p.c2, m->H2, P, m->H2, m->Wc_x6[2], m->tc_fold[2], 0, m->n_classes, logits,

@@ -85,8 +85,15 @@ struct FxProb {
 // 256 threads = 128 rows and 75 KB of LDS, so that TWO workgroups share a CU and one's prologue / stores run under the
 // other's MFMAs.
 template <int KD> struct FxShape { static constexpr int T = KD == 64 ? 256 : 512, ROWS = T / 2; };
-template <int KD, bool RIDER = false>
-__global__ void __launch_bounds__(FxShape<KD>::T, 2) k_fusion_rows_x6(FxProb p0, FxProb p1, PoolRider rider) {
+// ACT != 0: the activation-aware instantiation (leaky activations, act.hip) of the eval pair launch — act(y) = y > 0 ? y :
+// a * y per element, signed pooling (segmax.hpp fx_segmax2_off_act) for the problem with seg, act in the plain store of
+// the other.  The slopes (device pointers to one float each, read by every workgroup) are an argument only that
+// instantiation has: FxSlopes<0> is empty, and nothing in the ACT == 0 code reads it.
+template <int ACT> struct FxSlopes {};
+template <> struct FxSlopes<1> { const float* s0; const float* s1; };
+template <int KD, bool RIDER = false, int ACT = 0>
+__global__ void __launch_bounds__(FxShape<KD>::T, 2) k_fusion_rows_x6(FxProb p0, FxProb p1, PoolRider rider,
+                                                                      FxSlopes<ACT> slopes) {
   constexpr int T = FxShape<KD>::T, NWAVE = T / 64;
   constexpr int KS = KD / 16, RS = KD + 8, CPR = KD / 8;    // k steps, LDS row stride (bf16), 16-byte chunks per row
   constexpr int CHUNKS = 3 * 64 * CPR, NW = CHUNKS / T;     // 16-byte chunks of one W tile, per thread
@@ -158,6 +165,8 @@ __global__ void __launch_bounds__(FxShape<KD>::T, 2) k_fusion_rows_x6(FxProb p0,
   const float* __restrict__ A = P.A;
   const int N = P.N;
   const int tn = (F + 63) >> 6;
+  float slope = 0.f;
+  if constexpr (ACT != 0) slope = *(small ? slopes.s1 : slopes.s0);
   const int rt = whole ? logical : (small ? 0 : p0.full) + logical / P.groups;
   const int cg = whole ? 0 : logical % P.groups;
   const int ct0 = cg * P.ng;
@@ -303,7 +312,21 @@ __global__ void __launch_bounds__(FxShape<KD>::T, 2) k_fusion_rows_x6(FxProb p0,
     if (pooling && P.key64 != nullptr) {
       fx_key64(acc0, acc1, P.key64, roff, (unsigned)c0, c0 < F, c1 < F, m0, m1, (unsigned)(row0 + 4 * lhi), runs);
     } else if (pooling) {
-      fx_segmax2_off(acc0, acc1, P.out, roff, (unsigned)c0, c0 < F, c1 < F, runs);
+      if constexpr (ACT != 0) fx_segmax2_off_act(acc0, acc1, P.out, roff, (unsigned)c0, c0 < F, c1 < F, runs, slope);
+      else fx_segmax2_off(acc0, acc1, P.out, roff, (unsigned)c0, c0 < F, c1 < F, runs);
+    } else if constexpr (ACT != 0) {
+      // plain store of act(.) (fusion_block_super: P rows): the accumulator layout as it is — a few row tiles per launch
+      unsigned rb = (unsigned)(row0 + 4 * lhi);
+      asm volatile("" : "+v"(rb));
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const unsigned row = rb + (r & 3) + 8 * (r >> 2);
+        if ((int)row < N) {
+          float* o = P.out + (unsigned long)row * (unsigned long)P.ldo;
+          if (c0 < F) o[c0] = acc0[r] > 0.f ? acc0[r] : slope * acc0[r];
+          if (c1 < F) o[c1] = acc1[r] > 0.f ? acc1[r] : slope * acc1[r];
+        }
+      }
     } else {
       // the row base goes through an opaque asm so that the 16 row addresses are recomputed here instead of being
       // kept in 32 registers across the MFMA loop
@@ -478,7 +501,9 @@ int yl_fusion_pair_eval_x6_impl(const float* A, int64_t lda, int64_t N, int64_t 
                                 const uint16_t* Wl, const float* tfold, int64_t F, const int32_t* node_seg, float* pool,
                                 int64_t ldpool, const float* S, int64_t lds, int64_t P, const uint16_t* Wsh,
                                 const uint16_t* Wsm, const uint16_t* Wsl, const float* tsfold, float* Ys, int64_t ldys,
-                                const PoolRider* rider, yolat_stream_t stream) {
+                                const PoolRider* rider, yolat_stream_t stream, const float* slope_f,
+                                const float* slope_s) {
+  if ((slope_f == nullptr) != (slope_s == nullptr)) return YOLAT_E_INVALID;
   if (N <= 0 || P <= 0 || F <= 0 || !A || !Wh || !Wm || !Wl || !tfold || !node_seg || !pool || !S || !Wsh || !Wsm || !Wsl ||
       !tsfold || !Ys)
     return YOLAT_E_INVALID;
@@ -509,12 +534,26 @@ int yl_fusion_pair_eval_x6_impl(const float* A, int64_t lda, int64_t N, int64_t 
   const long total = (long)p0.full + (long)(p0.tm - p0.full) * p0.groups + n1 + pr.blocks;
   if (total >= (1LL << 31)) return YOLAT_E_UNSUPPORTED;
   hipStream_t st = (hipStream_t)stream;
+  if (slope_f != nullptr) {
+    // leaky activation: `pool` holds -inf / 0 per proposal (yolat_pool_init_signed), not zeros
+    const FxSlopes<1> sl{slope_f, slope_s};
+    p0.relu = 0; p1.relu = 0;
+    if (pr.blocks > 0) {
+      if (D == 128) hipLaunchKernelGGL((k_fusion_rows_x6<128, true, 1>), dim3((unsigned)total), dim3(FxShape<128>::T), 0, st, p0, p1, pr, sl);
+      else hipLaunchKernelGGL((k_fusion_rows_x6<64, true, 1>), dim3((unsigned)total), dim3(FxShape<64>::T), 0, st, p0, p1, pr, sl);
+    } else {
+      if (D == 128) hipLaunchKernelGGL((k_fusion_rows_x6<128, false, 1>), dim3((unsigned)total), dim3(FxShape<128>::T), 0, st, p0, p1, pr, sl);
+      else hipLaunchKernelGGL((k_fusion_rows_x6<64, false, 1>), dim3((unsigned)total), dim3(FxShape<64>::T), 0, st, p0, p1, pr, sl);
+    }
+    YL_LAUNCH_CHECK();
+    return 0;
+  }
   if (pr.blocks > 0) {
-    if (D == 128) hipLaunchKernelGGL((k_fusion_rows_x6<128, true>), dim3((unsigned)total), dim3(FxShape<128>::T), 0, st, p0, p1, pr);
-    else hipLaunchKernelGGL((k_fusion_rows_x6<64, true>), dim3((unsigned)total), dim3(FxShape<64>::T), 0, st, p0, p1, pr);
+    if (D == 128) hipLaunchKernelGGL((k_fusion_rows_x6<128, true>), dim3((unsigned)total), dim3(FxShape<128>::T), 0, st, p0, p1, pr, FxSlopes<0>{});
+    else hipLaunchKernelGGL((k_fusion_rows_x6<64, true>), dim3((unsigned)total), dim3(FxShape<64>::T), 0, st, p0, p1, pr, FxSlopes<0>{});
   } else {
-    if (D == 128) hipLaunchKernelGGL((k_fusion_rows_x6<128>), dim3((unsigned)total), dim3(FxShape<128>::T), 0, st, p0, p1, pr);
-    else hipLaunchKernelGGL((k_fusion_rows_x6<64>), dim3((unsigned)total), dim3(FxShape<64>::T), 0, st, p0, p1, pr);
+    if (D == 128) hipLaunchKernelGGL((k_fusion_rows_x6<128>), dim3((unsigned)total), dim3(FxShape<128>::T), 0, st, p0, p1, pr, FxSlopes<0>{});
+    else hipLaunchKernelGGL((k_fusion_rows_x6<64>), dim3((unsigned)total), dim3(FxShape<64>::T), 0, st, p0, p1, pr, FxSlopes<0>{});
   }
   YL_LAUNCH_CHECK();
   return 0;
@@ -528,6 +567,22 @@ extern "C" int yolat_fusion_pair_eval_x6(const float* A, int64_t lda, int64_t N,
                                          yolat_stream_t stream) {
   return yl_fusion_pair_eval_x6_impl(A, lda, N, D, Wh, Wm, Wl, tfold, F, node_seg, pool, ldpool, S, lds, P, Wsh, Wsm, Wsl,
                                      tsfold, Ys, ldys, nullptr, stream);
+}
+
+// The activation-aware pair launch (leaky activations, act.hip): pool[p, 0:F] = max over the rows of proposal p of
+// act_f(A . (sf (.) Wf)^T + tfold), 0 for an empty proposal; Ys = act_s(S . (sfs (.) Wfs)^T + tsfold).  Two launches: the
+// signed start values of `pool` from seg_ptr (-inf / 0), then the ACT instantiation of the rows kernel.
+extern "C" int yolat_fusion_pair_eval_x6_act(const float* A, int64_t lda, int64_t N, int64_t D, const uint16_t* Wh,
+                                             const uint16_t* Wm, const uint16_t* Wl, const float* tfold, int64_t F,
+                                             const float* slope_f, const int32_t* node_seg, const int32_t* seg_ptr,
+                                             float* pool, int64_t ldpool, const float* S, int64_t lds, int64_t P,
+                                             const uint16_t* Wsh, const uint16_t* Wsm, const uint16_t* Wsl,
+                                             const float* tsfold, const float* slope_s, float* Ys, int64_t ldys,
+                                             yolat_stream_t stream) {
+  if (!slope_f || !slope_s || !seg_ptr) return YOLAT_E_INVALID;
+  YL_TRY(yolat_pool_init_signed(seg_ptr, P, F, pool, ldpool, stream));
+  return yl_fusion_pair_eval_x6_impl(A, lda, N, D, Wh, Wm, Wl, tfold, F, node_seg, pool, ldpool, S, lds, P, Wsh, Wsm, Wsl,
+                                     tsfold, Ys, ldys, nullptr, stream, slope_f, slope_s);
 }
 
 // Training-mode fusion GEMM (fusion_train.hip step 4) on the rows kernel: z = A . W^T + bias never stored, per
@@ -558,8 +613,8 @@ int yl_fusion_rows_x6_key64(const float* A, long lda, long N, long K, const floa
   const long total = (long)p0.full + (long)(p0.tm - p0.full) * p0.groups;
   if (total >= (1LL << 31)) return YOLAT_E_UNSUPPORTED;
   hipStream_t st = (hipStream_t)stream;
-  if (K == 128) hipLaunchKernelGGL(k_fusion_rows_x6<128>, dim3((unsigned)total), dim3(FxShape<128>::T), 0, st, p0, p1, PoolRider{});
-  else hipLaunchKernelGGL(k_fusion_rows_x6<64>, dim3((unsigned)total), dim3(FxShape<64>::T), 0, st, p0, p1, PoolRider{});
+  if (K == 128) hipLaunchKernelGGL(k_fusion_rows_x6<128>, dim3((unsigned)total), dim3(FxShape<128>::T), 0, st, p0, p1, PoolRider{}, FxSlopes<0>{});
+  else hipLaunchKernelGGL(k_fusion_rows_x6<64>, dim3((unsigned)total), dim3(FxShape<64>::T), 0, st, p0, p1, PoolRider{}, FxSlopes<0>{});
   YL_LAUNCH_CHECK();
   return 0;
 }
@@ -593,8 +648,8 @@ extern "C" int yolat_linear_fwd_rows_x6(const float* A, int64_t lda, int64_t M, 
   const long total = (long)p0.tm;
   if (total >= (1LL << 31)) return YOLAT_E_UNSUPPORTED;
   hipStream_t st = (hipStream_t)stream;
-  if (K == 128) hipLaunchKernelGGL(k_fusion_rows_x6<128>, dim3((unsigned)total), dim3(FxShape<128>::T), 0, st, p0, p1, PoolRider{});
-  else hipLaunchKernelGGL(k_fusion_rows_x6<64>, dim3((unsigned)total), dim3(FxShape<64>::T), 0, st, p0, p1, PoolRider{});
+  if (K == 128) hipLaunchKernelGGL(k_fusion_rows_x6<128>, dim3((unsigned)total), dim3(FxShape<128>::T), 0, st, p0, p1, PoolRider{}, FxSlopes<0>{});
+  else hipLaunchKernelGGL(k_fusion_rows_x6<64>, dim3((unsigned)total), dim3(FxShape<64>::T), 0, st, p0, p1, PoolRider{}, FxSlopes<0>{});
   YL_LAUNCH_CHECK();
   return 0;
 }
@@ -627,7 +682,7 @@ extern "C" int yolat_node_uv_eval_x6(const float* f_in, int64_t ld_f, const floa
   p1.tm = yl_cdiv(N, FxShape<64>::ROWS); p1.groups = 1; p1.ng = 1;
   const long total = (long)p0.tm * p0.groups + (((long)p1.tm * p1.groups + 7) & ~7L);
   if (total >= (1LL << 31)) return YOLAT_E_UNSUPPORTED;
-  hipLaunchKernelGGL(k_fusion_rows_x6<64>, dim3((unsigned)total), dim3(FxShape<64>::T), 0, (hipStream_t)stream, p0, p1, PoolRider{});
+  hipLaunchKernelGGL(k_fusion_rows_x6<64>, dim3((unsigned)total), dim3(FxShape<64>::T), 0, (hipStream_t)stream, p0, p1, PoolRider{}, FxSlopes<0>{});
   YL_LAUNCH_CHECK();
   return 0;
 }

@@ -106,12 +106,14 @@ int yl_edge_uv_mlp2_mean_eval_impl(const float* UV, int64_t ld_uv, const int32_t
                                    const float* s2, const float* t2, int64_t C, float* f_out, int64_t ld_fo, int variant,
                                    const PoolRider* rider, int* rode, const EdgeNext* next, int* did_next,
                                    yolat_stream_t stream, int tiles_per_wg = 1);
-// yolat_fusion_pair_eval_x6 with an optional rider (fusion_x6.hip)
+// yolat_fusion_pair_eval_x6 with an optional rider (fusion_x6.hip); slope_f / slope_s (both or none): the activation-aware
+// instantiation for a leaky activation — `pool` then starts from yolat_pool_init_signed, not from zeros
 int yl_fusion_pair_eval_x6_impl(const float* A, int64_t lda, int64_t N, int64_t D, const uint16_t* Wh, const uint16_t* Wm,
                                 const uint16_t* Wl, const float* tfold, int64_t F, const int32_t* node_seg, float* pool,
                                 int64_t ldpool, const float* S, int64_t lds, int64_t P, const uint16_t* Wsh,
                                 const uint16_t* Wsm, const uint16_t* Wsl, const float* tsfold, float* Ys, int64_t ldys,
-                                const PoolRider* rider, yolat_stream_t stream);
+                                const PoolRider* rider, yolat_stream_t stream, const float* slope_f = nullptr,
+                                const float* slope_s = nullptr);
 // k_pool_prepare restricted to `parts` (segment.hip)
 int yl_pool_prepare_parts(const float* feats, const float* fsup, int64_t ld, int64_t D, int64_t F, const int32_t* seg_ptr,
                           int64_t P, float* Z, int64_t ldz, int parts, yolat_stream_t stream);

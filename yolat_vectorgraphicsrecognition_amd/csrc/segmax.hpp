@@ -68,6 +68,44 @@ __device__ __forceinline__ void fx_segmax2_off(const f32x16& acc0, const f32x16&
   }
 }
 
+// ---- signed pooling (leaky activations, act.hip) -----------------------------------------------------------------------
+// The pooled element of a NON-EMPTY proposal starts at -inf (yolat_pool_init_signed; an empty one at 0 and is never
+// touched), and a run's maximum v of ACTIVATED values is merged with ONE atomic chosen by v's sign bit:
+//   sign bit clear: atomicMax on the int bits   — such floats order like their int bits, and every float with the sign bit
+//                                                 set is a negative int: v wins over any negative content;
+//   sign bit set:   atomicMin on the unsigned bits — such floats order INVERSELY to their unsigned bits (-inf = 0xFF800000
+//                                                 is the largest non-NaN pattern), and every float without the sign bit is a
+//                                                 smaller unsigned number: a non-negative content stays.
+// Either way the element ends at the float maximum of everything merged, exact and order-independent, with no decode
+// pass.  A NaN is merged as the positive quiet NaN 0x7FC00000: above +inf as an int and below every sign-bit pattern as
+// an unsigned, so it wins and stays (torch's scatter-max propagates it).
+__device__ __forceinline__ void fx_signed_max(float* o, float v) {
+  if (v != v) v = __int_as_float(0x7FC00000);
+  if (__float_as_int(v) >= 0) atomicMax(reinterpret_cast<int*>(o), __float_as_int(v));
+  else atomicMin(reinterpret_cast<unsigned*>(o), __float_as_uint(v));
+}
+// fx_segmax2_off for act(y) = y > 0 ? y : a * y applied per element BEFORE the run-length maximum (a < 0 is not monotone:
+// the maximum of the activated rows is not the activation of the maximum).  The running maximum is a float that starts at
+// -inf and keeps a NaN; every run is flushed (there is no "nothing above the start value" shortcut for signed values).
+__device__ __forceinline__ void fx_segmax2_off_act(const f32x16& acc0, const f32x16& acc1, float* pool, const unsigned off[16],
+                                                   unsigned c0, bool ok0, bool ok1, const FxRuns& sr, float a) {
+  float cur0 = -INFINITY, cur1 = -INFINITY;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const float v0 = acc0[r] > 0.f ? acc0[r] : a * acc0[r], v1 = acc1[r] > 0.f ? acc1[r] : a * acc1[r];
+    cur0 = (v0 > cur0 || v0 != v0) ? v0 : cur0;
+    cur1 = (v1 > cur1 || v1 != v1) ? v1 : cur1;
+    if ((sr.uflush >> r) & 1u) {
+      if ((sr.flush_bits >> r) & 1u) {
+        float* o = pool + (off[r] + c0);
+        if (ok0) fx_signed_max(o, cur0);
+        if (ok1) fx_signed_max(o + 32, cur1);
+        cur0 = -INFINITY; cur1 = -INFINITY;              // the lane's next row starts a new run
+      }
+    }
+  }
+}
+
 // values = relu(acc) (the shift is the accumulator's initial value, the scale is inside the weights).  Both column
 // blocks in one pass: two independent running-max chains (the chain is latency bound) and one test per row.
 __device__ __forceinline__ void fx_segmax2(const f32x16& acc0, const f32x16& acc1, float* pool, unsigned ldpool,

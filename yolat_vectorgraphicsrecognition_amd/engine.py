@@ -124,10 +124,67 @@ def _bn_eval(bn, dev):
 # Linear (+ BatchNorm1d + ReLU)
 # ---------------------------------------------------------------------------------------------
 
-def lbr_fwd(a, lin, bn, relu, training, out=None, coef_out=None, dense=False):
+def block_act(mlp):
+    """The activation of a gcn_lib MLP block [Linear, BatchNorm1d, act, (Dropout2d)] as lbr_fwd takes it: True for the
+    ReLU, the nn.LeakyReLU / nn.PReLU module for a leaky one (csrc/act.hip), False for none."""
+    for m in mlp.children():
+        if isinstance(m, torch.nn.ReLU):
+            return True
+        if isinstance(m, (torch.nn.LeakyReLU, torch.nn.PReLU)):
+            return m
+    return False
+
+
+def model_act(model):
+    """The four activations behind the conv stack (fusion_block, fusion_block_super, prediction_cls.0, .1), in that order."""
+    net = model.cls_net
+    return tuple(block_act(b) for b in (net.fusion_block, net.fusion_block_super, model.prediction_cls[0],
+                                        model.prediction_cls[1]))
+
+
+def model_is_relu(model):
+    return all(a is True for a in model_act(model))
+
+
+def _lbr_fwd_leaky(a, lin, bn, act, training, out, coef_out, act_out):
+    """lbr_fwd for a leaky activation: the BatchNorm output is never handed on lazily — the activation is materialised by
+    ops.scale_shift_act (into ``act_out`` when given), the backward recomputes the BatchNorm output from the saved
+    pre-BatchNorm tensor (ops.bn_act_bwd), so a slope <= 0 is as good as any."""
+    A = a.t
+    M, dev = A.shape[0], A.device
+    C = lin.out_features
+    if bn is None:
+        raise NotImplementedError("Linear + act %s without BatchNorm is not on the reference path" % act.__class__.__name__)
+    slope = ops.act_slope(act, dev)
+    sv = {"a": a, "lin": lin, "bn": bn, "relu": False, "act": act, "slope": slope}
+    if training:
+        if M == 0:
+            raise ValueError("BatchNorm1d in training mode needs at least one row")
+        y = _empty(M, C, dev) if out is None else out
+        stats = ops.stats_buffer(M, C, dev)
+        ops.linear_fwd(A, lin.weight, lin.bias, y, a_pro=a.pro, a_relu=a.relu, stats=stats)
+        coef = _bn_train(stats, M, bn, dev, coef_out)
+        z = _empty(M, C, dev) if act_out is None else act_out
+        ops.scale_shift_act(y, coef[0], coef[1], slope, z)
+        sv.update(y=y, coef=coef)
+        return Lazy(z), sv
+    z = act_out if act_out is not None else (_empty(M, C, dev) if out is None else out)
+    coef = _bn_eval(bn, dev)
+    ops.linear_fwd(A, lin.weight, lin.bias, z, a_pro=a.pro, a_relu=a.relu, o_pro=(coef[0], coef[1]), o_relu=False)
+    ops.scale_shift_act(z, None, None, slope, z)
+    sv["y"] = z
+    return Lazy(z), sv
+
+
+def lbr_fwd(a, lin, bn, relu, training, out=None, coef_out=None, dense=False, act_out=None):
     """a: Lazy input [M,K].  Returns (Lazy output, saved).  ``out`` optionally names the [M,C]
     destination (may be a column slice of a wider buffer).  dense: the training GEMMs of this layer (forward, dX, dW)
-    on bf16 operands ("bf16_dense" training precision, ops.bt_*)."""
+    on bf16 operands ("bf16_dense" training precision, ops.bt_*).  relu: True / False, or the nn.LeakyReLU / nn.PReLU
+    module of the block (block_act) — then the output is materialised, into ``act_out`` when given."""
+    if relu is not True and relu is not False:
+        if dense:
+            raise ValueError("bf16_dense training covers act = relu only: this block's act is %s" % relu.__class__.__name__)
+        return _lbr_fwd_leaky(a, lin, bn, relu, training, out, coef_out, act_out)
     A = a.t
     M, dev = A.shape[0], A.device
     C = lin.out_features
@@ -326,7 +383,14 @@ def lbr_bwd(sv, dz, sink, dx_out=None, dx_accumulate=False, need_dx=True, dz_inp
     producer's post-activation output), written to ``dx_out`` if given."""
     a, lin, bn, relu, y = sv["a"], sv["lin"], sv["bn"], sv["relu"], sv["y"]
     M, dev = y.shape[0], y.device
-    if bn is not None:
+    act = sv.get("act")
+    if act is not None:
+        coef = sv["coef"]
+        dy = dz if dz_inplace else torch.empty(M, y.shape[1], dtype=torch.float32, device=dev)
+        dslope = sink.get(act.weight) if isinstance(act, torch.nn.PReLU) else None
+        ops.bn_act_bwd(dz, y, coef[2], coef[3], coef[0], coef[1], sv["slope"], sink.get(bn.weight), sink.get(bn.bias),
+                       dslope, dy)
+    elif bn is not None:
         coef = sv["coef"]
         dy = dz if dz_inplace else torch.empty(M, y.shape[1], dtype=torch.float32, device=dev)
         ops.bn_relu_bwd(dz, y, bn.weight, coef[2], coef[3], coef[0], coef[1], relu,
@@ -535,6 +599,9 @@ def model_fwd(model, g, x, training):
     D = C * n_out                       # fusion_dims
     # "bf16_dense": fusion_block, fusion_block_super and classifier layers 0 / 1 on bf16 operands (csrc/bf16_train.hip)
     dense = training and precision == "bf16_dense"
+    act_f, act_s, act_1, act_2 = model_act(model)
+    if training and half and not model_is_relu(model):
+        raise ValueError("train precision %r covers act = relu only (this model's act is not): use 'fp32'" % precision)
     if dense:
         check_bf16_dense_shapes(model)
 
@@ -557,7 +624,7 @@ def model_fwd(model, g, x, training):
     # fusion block over nodes, then per-proposal max                                  (arch:61-63,122)
     arg_fus = None
     arg_feat = torch.empty(P, D, dtype=torch.int32, device=dev) if training else None
-    if training and FUSED_FUSION_TRAIN and D == 128 and net.fusion_block[0].weight.is_contiguous():
+    if training and FUSED_FUSION_TRAIN and D == 128 and net.fusion_block[0].weight.is_contiguous() and act_f is True:
         # no [N,F] activation: batch statistics from the Gram matrix of feats, extreme-of-z GEMM epilogue,
         # sparse backward (csrc/fusion_train.hip)
         sv_fus = ops.fusion_pool_train_fwd(feats, net.fusion_block[0], net.fusion_block[1], g, Z[:, 0:F], bf16=dense)
@@ -565,7 +632,9 @@ def model_fwd(model, g, x, training):
         if net.fusion_block[1].num_batches_tracked is not None:
             _PENDING_NBT.append(net.fusion_block[1].num_batches_tracked)
     else:
-        fus, sv_fus = lbr_fwd(Lazy(feats), net.fusion_block[0], net.fusion_block[1], True, training)
+        # (a leaky activation always comes here: activated per element, THEN the maximum with its argmax — right for
+        # any slope, where pooling the pre-activation is not)
+        fus, sv_fus = lbr_fwd(Lazy(feats), net.fusion_block[0], net.fusion_block[1], act_f, training)
         arg_fus = torch.empty(P, F, dtype=torch.int32, device=dev) if training else None
         ops.segment_max_fwd(fus.t, g, Z[:, 0:F], arg_fus, x_pro=fus.pro, x_relu=fus.relu)
     ops.segment_max_fwd(feats, g, Z[:, F:F + D], arg_feat)
@@ -576,14 +645,15 @@ def model_fwd(model, g, x, training):
         ops.segment_mean_fwd(fsup, g, sup, x_pro=(sup_coef[0], sup_coef[1]), x_relu=True)
     else:
         ops.segment_mean_fwd(fsup, g, sup)
-    fs, sv_fs = lbr_fwd(Lazy(sup), net.fusion_block_super[0], net.fusion_block_super[1], True, training,
-                        out=(None if training else Z[:, F + D:2 * F + D]), dense=dense)
-    if training:
+    fs, sv_fs = lbr_fwd(Lazy(sup), net.fusion_block_super[0], net.fusion_block_super[1], act_s, training,
+                        out=(None if training else Z[:, F + D:2 * F + D]), dense=dense,
+                        act_out=Z[:, F + D:2 * F + D])
+    if training and act_s is True:
         ops.scale_shift_relu(fs.t, fs.scale, fs.shift, True, Z[:, F + D:2 * F + D])
     # classifier                                                                      (arch:91-93,128)
     m1, m2, m3 = model.prediction_cls[0], model.prediction_cls[1], model.prediction_cls[2]
-    c1, sv1 = lbr_fwd(Lazy(Z), m1[0], m1[1], True, training, dense=dense)
-    c2, sv2 = lbr_fwd(c1, m2[0], m2[1], True, training, dense=dense)
+    c1, sv1 = lbr_fwd(Lazy(Z), m1[0], m1[1], act_1, training, dense=dense)
+    c2, sv2 = lbr_fwd(c1, m2[0], m2[1], act_2, training, dense=dense)
     p_drop = _drop_p(m2) if training else 0.0                     # arch:92: only prediction_cls.1 carries dropout
     sv_drop = None
     if p_drop > 0:

@@ -23,12 +23,19 @@ from .engine import Lazy, GradSink
 # ---------------------------------------------------------------------------------------------
 
 def act_layer(act_type, inplace=False, neg_slope=0.2, n_prelu=1):
-    """torch_nn.py:9-20.  Only 'relu' has a HIP implementation (the only one the arch uses)."""
+    """torch_nn.py:9-20.  Parameter containers: 'relu' runs in the GEMM epilogues / operand prologues, 'leakyrelu' and
+    'prelu' on the kernels of csrc/act.hip (the slope is read from device memory: a PReLU weight may be edited in place,
+    trained, negative or above 1)."""
     act = act_type.lower()
     if act == "relu":
         return nn.ReLU(inplace)
-    if act in ("leakyrelu", "prelu"):
-        raise NotImplementedError("activation layer [%s] has no MI355X kernel (arch uses relu)" % act)
+    if act == "leakyrelu":
+        return nn.LeakyReLU(neg_slope, inplace)
+    if act == "prelu":
+        if n_prelu != 1:
+            raise ValueError("act prelu: n_prelu must be 1 (one slope per site, as the reference builds it), got %r"
+                             % (n_prelu,))
+        return nn.PReLU(num_parameters=n_prelu, init=neg_slope)
     raise NotImplementedError("activation layer [%s] is not found" % act)
 
 
@@ -58,7 +65,8 @@ class MultiSeq(nn.Sequential):
 
 
 def _groups(seq):
-    """Split an MLP's children into (Linear, BatchNorm1d|None, relu, dropout_p) groups."""
+    """Split an MLP's children into (Linear, BatchNorm1d|None, act, dropout_p) groups; act: False (none), True (ReLU) or
+    the nn.LeakyReLU / nn.PReLU module itself (engine.lbr_fwd takes the kind and the slope from it)."""
     groups = []
     for m in seq.children():
         if isinstance(m, nn.Linear):
@@ -67,6 +75,8 @@ def _groups(seq):
             groups[-1][1] = m
         elif isinstance(m, nn.ReLU):
             groups[-1][2] = True
+        elif isinstance(m, (nn.LeakyReLU, nn.PReLU)):
+            groups[-1][2] = m
         elif isinstance(m, (nn.Dropout, nn.Dropout2d)):
             groups[-1][3] = float(m.p)
         else:

@@ -608,6 +608,84 @@ def bn_relu_bwd(dZ, Y, gamma, save_mean, save_invstd, scale, shift, relu, dgamma
 
 
 # ---------------------------------------------------------------------------------------------
+# leaky activations (csrc/act.hip): act(y) = y > 0 ? y : a * y, the slope a read from device memory
+# ---------------------------------------------------------------------------------------------
+
+ACT_RELU, ACT_LEAKYRELU, ACT_PRELU = 0, 1, 2
+
+
+def act_kind(mod):
+    """YOLAT_ACT_* of an activation module (torch_nn.py:9-20)."""
+    if isinstance(mod, torch.nn.PReLU):
+        return ACT_PRELU
+    if isinstance(mod, torch.nn.LeakyReLU):
+        return ACT_LEAKYRELU
+    if isinstance(mod, torch.nn.ReLU):
+        return ACT_RELU
+    raise NotImplementedError("act layer %s has no MI355X kernel" % mod.__class__.__name__)
+
+
+def act_slope(mod, dev):
+    """The one-float device tensor a kernel reads the slope of `mod` from: a PReLU's weight itself (in-place edits and
+    Adam steps are seen by the next launch), for a LeakyReLU a constant cached on the module per device."""
+    if isinstance(mod, torch.nn.PReLU):
+        w = mod.weight
+        if w.numel() != 1:
+            raise ValueError("act prelu: num_parameters must be 1 (the reference's n_prelu), got %d" % w.numel())
+        if not w.is_cuda or w.dtype != torch.float32:
+            raise RuntimeError("act prelu: the slope must be a float32 CUDA (ROCm) tensor")
+        return w
+    cache = mod.__dict__.setdefault("_yolat_slope", {})
+    t = cache.get(dev)
+    if t is None or float(mod.negative_slope) != cache.get("value"):
+        cache.clear()
+        t = cache[dev] = torch.full((1,), float(mod.negative_slope), dtype=torch.float32, device=dev)
+        cache["value"] = float(mod.negative_slope)
+    return t
+
+
+def scale_shift_act(Y, scale, shift, slope, Z):
+    """Z = act(Y * scale + shift) (scale None: act(Y)); Z may be Y."""
+    M, C = Y.shape
+    check(lib.yolat_scale_shift_act(_f(Y), _ld(Y), M, C, _f(scale, "scale", True), _f(shift, "shift", True),
+                                    _f(slope, "slope"), _f(Z), _ld(Z), _stream()), "yolat_scale_shift_act")
+    return Z
+
+
+def segment_act_max(Y, slope, g, out):
+    """out[p] = max over the rows of proposal p of act(Y[r]) (0 for an empty proposal): signed values, no atomics."""
+    check(lib.yolat_segment_act_max(_f(Y), _ld(Y), Y.shape[0], Y.shape[1], _f(slope, "slope"), g.seg_ptr.data_ptr(), g.P, _f(out),
+                                    _ld(out), _stream()), "yolat_segment_act_max")
+    return out
+
+
+def bn_act_bwd(dZ, Y, save_mean, save_invstd, scale, shift, slope, dgamma, dbeta, dslope, dY, accumulate=False):
+    """Backward of act(BN_train(Y)): bn_relu_bwd with the slope, and dslope (None for a LeakyReLU) = sum_{y' <= 0} dZ * y'."""
+    M, C = Y.shape
+    work = torch.empty(int(lib.yolat_bn_act_bwd_work_elems(M, C)), dtype=torch.float32, device=Y.device)
+    check(lib.yolat_bn_act_bwd(_f(dZ), _ld(dZ), _f(Y), _ld(Y), M, C, _f(save_mean), _f(save_invstd), _f(scale), _f(shift),
+                               _f(slope, "slope"), _f(dgamma), _f(dbeta), _f(dslope, "dslope", True), int(accumulate),
+                               _f(dY), _ld(dY), work.data_ptr(), _stream()), "yolat_bn_act_bwd")
+    return dY
+
+
+def fusion_pair_eval_act(A, lin_f, fold_f, slope_f, g, pool, S=None, lin_s=None, fold_s=None, slope_s=None, Ys=None):
+    """yolat_fusion_pair_eval_act: pool[P,F] = per-proposal max of act(bn(lin_f(A))), Ys = act(bn(lin_s(S))); fold_* = the
+    eval BatchNorm as (scale, shift)."""
+    N, D = A.shape
+    F = lin_f.weight.shape[0]
+    work = torch.empty(int(lib.yolat_fusion_pair_eval_act_work_elems(N, F)), dtype=torch.float32, device=A.device)
+    has_s = S is not None
+    check(lib.yolat_fusion_pair_eval_act(
+        _f(A), _ld(A), N, D, _f(lin_f.weight), _f(lin_f.bias, "bias", True), _f(fold_f[0]), _f(fold_f[1]), F, _f(slope_f),
+        g.seg_ptr.data_ptr(), _f(pool), _ld(pool), _f(S, "S", True), _ld(S) if has_s else 0, g.P,
+        _f(lin_s.weight) if has_s else None, _f(lin_s.bias, "bias", True) if has_s else None,
+        _f(fold_s[0]) if has_s else None, _f(fold_s[1]) if has_s else None, _f(slope_s) if has_s else None,
+        _f(Ys, "Ys", True), _ld(Ys) if has_s else 0, work.data_ptr(), _stream()), "yolat_fusion_pair_eval_act")
+    return pool
+
+
+# ---------------------------------------------------------------------------------------------
 # edge convolution
 # ---------------------------------------------------------------------------------------------
 

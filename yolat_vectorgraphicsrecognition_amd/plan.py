@@ -92,10 +92,16 @@ class EvalPlan(object):
     def __init__(self, model, precision="fp32"):
         if precision not in ("fp32", "bf16"):
             raise ValueError("precision must be 'fp32' or 'bf16'")
+        from .engine import model_is_relu
+        if precision != "fp32" and not model_is_relu(model):
+            raise ValueError("the %s eval plan covers act = relu only (this model's act is not)" % precision)
         self.precision = precision
         self._desc_h = None
         self.model = model
-        self._tensors = [t for t in model.parameters()] + [b for b in model.buffers()]
+        # (PReLU slopes are not part of the weight version: the kernels read them through their address, so an in-place
+        # edit neither rebuilds the descriptor nor drops a captured graph)
+        slopes = set(id(p) for mod in model.modules() if isinstance(mod, torch.nn.PReLU) for p in mod.parameters())
+        self._tensors = [t for t in model.parameters() if id(t) not in slopes] + [b for b in model.buffers()]
         self._key = None
         self._desc = None
         self._keep = None
@@ -182,6 +188,20 @@ class EvalPlan(object):
         m, net = self.model, self.model.cls_net
         fp32 = self.precision == "fp32"
         fb, fs = net.fusion_block, net.fusion_block_super
+        # the activation of the four sites behind the conv stack (csrc/act.hip).  The descriptor holds the ADDRESS of each
+        # slope — a PReLU weight itself, or a constant cached on the LeakyReLU module — so an in-place edit needs no rebuild
+        # and is seen by a hipGraph replay; ReLU leaves the fields zero
+        from .engine import model_act
+        acts = model_act(m)
+        kinds = set(ops.act_kind(a) for a in acts if a is not True)
+        if any(a is False for a in acts) or len(kinds) > 1:
+            raise NotImplementedError("the eval plan needs one act (relu, leakyrelu or prelu) at all four sites")
+        if kinds:
+            d.act = kinds.pop()
+            for i, a in enumerate(acts):
+                t = ops.act_slope(a, dev)
+                keep.append(t)
+                d.act_slope[i] = t.data_ptr()
         (d.Wf, d.bf, d.sf, d.tf), ff = _lin_bn(fb[0], fb[1], dev, keep)
         (d.Wfs, d.bfs, d.sfs, d.tfs), ffs = _lin_bn(fs[0], fs[1], dev, keep)
         # Linear + BatchNorm for the bf16x6-emulated fusion kernel: BatchNorm scale folded into the weight rows, exact 3-way

@@ -29,21 +29,30 @@ class FlatParams(object):
         if not params:
             raise ValueError("model has no parameters")
         dev = params[0].device
-        n = sum(p.numel() for p in params)
+        # Parameters lie back to back, except behind a PReLU slope: its ONE element would push every later view off
+        # 16-byte alignment (kernels then decline their vector paths), so the next parameter starts at the next multiple
+        # of 4 elements.  The padding elements are zero, keep a zero gradient (Adam leaves a zero parameter with a zero
+        # gradient at zero, weight decay included), belong to no state_dict; a model without PReLU has none.
+        slopes = {id(p) for m in model.modules() if isinstance(m, torch.nn.PReLU) for p in m.parameters()}
+        self.offsets = []
+        n = 0
+        for p in params:
+            self.offsets.append(n)
+            n += p.numel()
+            if id(p) in slopes:
+                n = (n + 3) // 4 * 4
         self.numel = n
-        self.param = torch.empty(n, dtype=torch.float32, device=dev)
+        self.param = torch.zeros(n, dtype=torch.float32, device=dev)
         self.grad = torch.zeros(n, dtype=torch.float32, device=dev)
         self.grad_views = {}
         self.params = params
-        off = 0
-        for p in params:
+        for p, off in zip(params, self.offsets):
             k = p.numel()
             self.param[off:off + k].copy_(p.data.reshape(-1))
             p.data = self.param[off:off + k].view(p.shape)
             gv = self.grad[off:off + k].view(p.shape)
             self.grad_views[id(p)] = gv
             p.grad = gv
-            off += k
         self.direct_grads = True      # _ModelFn.backward writes straight into self.grad
         self.grads_ready = False
         # [0, conv_end) = parameters of the conv layers (cls_net.head / cls_net.backbone come first in
@@ -56,7 +65,7 @@ class FlatParams(object):
             while lead < len(params) and id(params[lead]) in conv_ids:
                 lead += 1
             if 0 < lead < len(params) and not any(id(p) in conv_ids for p in params[lead:]):
-                self.conv_end = sum(p.numel() for p in params[:lead])
+                self.conv_end = self.offsets[lead]
         self.on_head_done = None
         model._yolat_flat = self
 
@@ -101,10 +110,8 @@ class FlatAdam(torch.optim.Optimizer):
         return loss
 
     def _slices(self):
-        off = 0
-        for i, p in enumerate(self.flat.params):
+        for i, (p, off) in enumerate(zip(self.flat.params, self.flat.offsets)):
             yield i, p, off, off + p.numel()
-            off += p.numel()
 
     def state_dict(self):
         """torch.optim.Adam layout: {'state': {i: {'step', 'exp_avg', 'exp_avg_sq'}}, 'param_groups': [...]}."""
@@ -332,6 +339,8 @@ class TrainPlan(object):
         try:
             convs = engine.model_convs(net)
             m1, m2, m3 = m.prediction_cls[0], m.prediction_cls[1], m.prediction_cls[2]
+            if not engine.model_is_relu(m):       # act = leakyrelu / prelu: the Python schedule (engine.py) runs the step
+                return False
             if engine._drop_p(m2) > 0 or len(list(m3.children())) != 1:
                 return False
             for cv in convs:
