@@ -285,6 +285,61 @@ int yolat_fusion_pair_eval_act(const float* A, int64_t lda, int64_t N, int64_t D
                                const float* slope_s, float* Ys, int64_t ldys, float* work, yolat_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The row norms of gcn_lib/sparse/torch_nn.py:23-34 — nn.LayerNorm(nc, elementwise_affine=True) and
+ * nn.InstanceNorm1d(nc, affine=False) on a 2-D [M, nc] input: ONE per-row arithmetic, the same in train() and eval():
+ *   z = (y - mean) / sqrt(var + eps) * gamma + beta,  mean / biased variance over the nc columns of the row;
+ * gamma / beta [nc] are both NULL for the instance norm.  The variance is the mean of centred squares.  csrc/rownorm.hip.
+ * ------------------------------------------------------------------------------------------ */
+#define YOLAT_NORM_BATCH 0
+#define YOLAT_NORM_LAYER 1
+#define YOLAT_NORM_INSTANCE 2
+/* Z[M,C] = relu?(rownorm(Y) * gamma + beta); any C; Z may be Y; save_mean / save_rstd [M] nullable (training).  One wave per
+ * row, the row in registers for C <= 1024.  A constant row gives exactly beta.                                       */
+int yolat_rownorm_act(const float* Y, int64_t ldy, int64_t M, int64_t C, const float* gamma, const float* beta, float eps,
+                      int relu, float* Z, int64_t ldz, float* save_mean, float* save_rstd, yolat_stream_t stream);
+/* Backward of Z = relu?(rownorm(Y) * gamma + beta) given dZ, from the saved pre-norm Y, mean and rstd: xh = (Y - mean) rstd and
+ * z' = gamma xh + beta are RECOMPUTED (never the sign of a stored activation), g = relu ? (z' > 0 ? dZ : 0) : dZ,
+ *   dY = rstd (g gamma - mean_c(g gamma) - xh mean_c(g gamma xh));  dgamma (+)= sum_rows g xh,  dbeta (+)= sum_rows g
+ * (both skipped when gamma == NULL; per-256-row-block partials summed in block order: two calls give identical bits).
+ * dY may be dZ.  work: fp32 scratch of yolat_rownorm_act_bwd_work_elems(M,C) (unused when gamma == NULL).             */
+size_t yolat_rownorm_act_bwd_work_elems(int64_t M, int64_t C);
+int yolat_rownorm_act_bwd(const float* dZ, int64_t lddz, const float* Y, int64_t ldy, int64_t M, int64_t C,
+                          const float* save_mean, const float* save_rstd, const float* gamma, const float* beta, int relu,
+                          float* dgamma, float* dbeta, int accumulate, float* dY, int64_t lddy, float* work,
+                          yolat_stream_t stream);
+/* Eval fusion pair behind a row norm in ONE launch (D in {64, 128}, F % 64 == 0, else YOLAT_E_UNSUPPORTED): the counterpart of
+ * yolat_fusion_pair_eval_x6,
+ *   pool[p, 0:F] = max over the rows of proposal p of relu(rownorm(A . Wf^T + bf) gamma_f + beta_f)   (merged by integer
+ *                  atomicMax: `pool` must be zero-filled),   Ys[P,F] = relu(rownorm(S . Wfs^T + bfs) gamma_s + beta_s);
+ * the [N,F] matrix is never written.  The weights arrive CENTRED over the F outputs and split (yolat_split_bf16x3, no row
+ * scale): (Wh, Wm, Wl) = split of Wf - mean_rows(Wf), tcen = bf - mean(bf) — the product then IS y - rowmean(y), whatever the
+ * row mean.  A workgroup owns YOLAT_RN_ROWS whole rows and walks the F/64 column tiles twice (sum of squares, then
+ * normalise + ReLU + pool).  node_seg [N]: proposal of each row (< 0: pooled nowhere).                                */
+#define YOLAT_RN_ROWS 128
+/* yolat_forward_eval* runs the fused kernel from this many nodes on and the materialising route below (measured crossover:
+ * the fused launch takes a flat 93 us up to 32 k rows, the other 41 us at 1250 rows, 86 at 10 k, 104 at 15 k) — unless the
+ * descriptor's rn_route names one of them.                                                                            */
+#define YOLAT_RN_FUSED_MIN_ROWS 12288
+#define YOLAT_RN_ROUTE_AUTO 0
+#define YOLAT_RN_ROUTE_FUSED 1
+#define YOLAT_RN_ROUTE_MATERIALISE 2
+int yolat_fusion_pair_eval_x6_rn(const float* A, int64_t lda, int64_t N, int64_t D, const uint16_t* Wh, const uint16_t* Wm,
+                                 const uint16_t* Wl, const float* tcen, int64_t F, const float* gamma_f, const float* beta_f,
+                                 const int32_t* node_seg, float* pool, int64_t ldpool, const float* S, int64_t lds, int64_t P,
+                                 const uint16_t* Wsh, const uint16_t* Wsm, const uint16_t* Wsl, const float* tscen,
+                                 const float* gamma_s, const float* beta_s, float* Ys, int64_t ldys, float eps,
+                                 yolat_stream_t stream);
+/* The same for any D, F on plain fp32 weights, the materialising form: per row range yolat_linear_fwd -> yolat_rownorm_act in
+ * place -> per-proposal maximum merged into the zero-filled `pool` (a range may cut a proposal: integer atomicMax).  work:
+ * yolat_fusion_pair_eval_rn_work_elems(N,F) floats, at most 64 MiB.  S == NULL: the node half alone.                  */
+size_t yolat_fusion_pair_eval_rn_work_elems(int64_t N, int64_t F);
+int yolat_fusion_pair_eval_rn(const float* A, int64_t lda, int64_t N, int64_t D, const float* Wf, const float* bf, int64_t F,
+                              const float* gamma_f, const float* beta_f, const int32_t* node_seg, float* pool,
+                              int64_t ldpool, const float* S, int64_t lds, int64_t P, const float* Wfs, const float* bfs,
+                              const float* gamma_s, const float* beta_s, float* Ys, int64_t ldys, float eps, float* work,
+                              yolat_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Edge convolution AttrRelativeEdgeConvGlobalPool2 (gcn_lib/sparse/torch_vertex.py:288-341):
  *   m_e = nn([x_i, x_j - x_i, a_e]);  out_i = mean_{e->i} m_e + lin_r(x_i)
  * All [E,*] tensors are in CSR (destination-sorted) order.
@@ -630,6 +685,18 @@ typedef struct {
   /* act != 0: the slope of each of the four sites (device pointers to one float, read by every launch) in the order
    * fusion_block, fusion_block_super, prediction_cls.0, prediction_cls.1.  Not read when act == 0.                  */
   const float *act_slope[4];
+  /* YOLAT_NORM_*: the norm of the same four sites (csrc/rownorm.hip).  0 = BatchNorm: none of the fields below is read, the
+   * launches, the workspace and the logits are those of a descriptor that never heard of them.  norm != 0 (act must be 0,
+   * else YOLAT_E_INVALID; the bf16 descriptor declines such a base): the BatchNorm scale / shift pointers of the four sites are
+   * not read; Wf_hi.. / Wfs_hi.. hold the split of the CENTRED weights and tf_fold / tfs_fold the centred bias
+   * (yolat_fusion_pair_eval_x6_rn); Wc1_gx / Wc_x6 are packed without a row scale and tc1_gx / tc_fold are the bias.
+   * rn_gamma / rn_beta: LayerNorm weight / bias per site (site order as act_slope), NULL for the instance norm.       */
+  int32_t norm;
+  float rn_eps;
+  const float *rn_gamma[4];
+  const float *rn_beta[4];
+  int32_t rn_route;                           /* YOLAT_RN_ROUTE_*: which fusion-pair route a row-norm forward takes; part of the
+                                               * descriptor, so that the workspace sizing and the forward cannot disagree     */
 } yolat_model_eval;
 
 /* workspace (bytes) needed by yolat_forward_eval for a batch of N nodes / E edges / P proposals */

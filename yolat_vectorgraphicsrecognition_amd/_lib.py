@@ -36,7 +36,9 @@ class ModelEval(ctypes.Structure):
                 [(n, c_p) for n in ("Wf", "bf", "sf", "tf", "Wf_hi", "Wf_mid", "Wf_lo", "tf_fold", "Wfs_hi", "Wfs_mid",
                                     "Wfs_lo", "tfs_fold", "Wfs", "bfs", "sfs", "tfs", "Wc1", "bc1", "sc1", "tc1", "Wc2",
                                     "bc2", "sc2", "tc2", "Wc3", "bc3")] +
-                [("Wc_x6", c_p * 3), ("tc_fold", c_p * 3), ("Wc1_gx", c_p), ("tc1_gx", c_p), ("act_slope", c_p * 4)])
+                [("Wc_x6", c_p * 3), ("tc_fold", c_p * 3), ("Wc1_gx", c_p), ("tc1_gx", c_p), ("act_slope", c_p * 4),
+                 ("norm", ctypes.c_int32), ("rn_eps", ctypes.c_float), ("rn_gamma", c_p * 4), ("rn_beta", c_p * 4),
+                 ("rn_route", ctypes.c_int32)])
 
 
 class BnCsrGrad(ctypes.Structure):
@@ -207,6 +209,16 @@ SIGNATURES = {
     "yolat_fusion_pair_eval_act_work_elems": (c_sz, [c_i64, c_i64]),
     "yolat_fusion_pair_eval_act": (c_int, [c_p, c_i64, c_i64, c_i64, c_p, c_p, c_p, c_p, c_i64, c_p, c_p, c_p, c_i64, c_p,
                                             c_i64, c_i64, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_p, c_p]),
+    # row norms (rownorm.hip)
+    "yolat_rownorm_act": (c_int, [c_p, c_i64, c_i64, c_i64, c_p, c_p, c_f, c_int, c_p, c_i64, c_p, c_p, c_p]),
+    "yolat_rownorm_act_bwd_work_elems": (c_sz, [c_i64, c_i64]),
+    "yolat_rownorm_act_bwd": (c_int, [c_p, c_i64, c_p, c_i64, c_i64, c_i64, c_p, c_p, c_p, c_p, c_int, c_p, c_p, c_int, c_p,
+                                       c_i64, c_p, c_p]),
+    "yolat_fusion_pair_eval_x6_rn": (c_int, [c_p, c_i64, c_i64, c_i64, c_p, c_p, c_p, c_p, c_i64, c_p, c_p, c_p, c_p, c_i64,
+                                              c_p, c_i64, c_i64, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_f, c_p]),
+    "yolat_fusion_pair_eval_rn_work_elems": (c_sz, [c_i64, c_i64]),
+    "yolat_fusion_pair_eval_rn": (c_int, [c_p, c_i64, c_i64, c_i64, c_p, c_p, c_i64, c_p, c_p, c_p, c_p, c_i64, c_p, c_i64,
+                                           c_i64, c_p, c_p, c_p, c_p, c_p, c_i64, c_f, c_p, c_p]),
     "yolat_linear_fwd": (c_int, [c_p, c_i64, c_i64, c_i64, c_p, c_p, c_int,
                                  c_p, c_i64, c_p, c_i64, c_p, c_p, c_int,
                                  c_p, c_i64, c_int, c_p, c_p]),

@@ -128,6 +128,7 @@ class SparseCADGCN(nn.Module):
         self.classifier = opt.classifier
         self.class_specific = opt.class_specific
         self.act = str(act).lower()
+        self.norm = str(norm).lower()
         self.dim_stat = 0
         self.cls_net = Backbone(opt)
         d = (self.cls_net.fusion_dims + 1024) * 2 + self.dim_stat
@@ -388,6 +389,9 @@ class SparseCADGCN(nn.Module):
         if precision != "fp32" and not engine.model_is_relu(self):
             raise ValueError("eval precision %r covers act = relu only; this model was built with act = %r "
                              "(fp32 runs it)" % (precision, self.act))
+        if precision != "fp32" and engine.model_norm(self) != "batch":
+            raise ValueError("eval precision %r covers norm = batch only; this model was built with norm = %r "
+                             "(fp32 runs it)" % (precision, engine.model_norm(self)))
         if self.__dict__.get("_yolat_precision", "fp32") != precision:
             self.__dict__["_yolat_precision"] = precision
             self.__dict__.pop("_yolat_plans", None)
@@ -412,6 +416,9 @@ class SparseCADGCN(nn.Module):
         if precision != "fp32" and not engine.model_is_relu(self):
             raise ValueError("train precision %r covers act = relu only; this model was built with act = %r "
                              "(fp32 runs it)" % (precision, self.act))
+        if precision != "fp32" and engine.model_norm(self) != "batch":
+            raise ValueError("train precision %r covers norm = batch only; this model was built with norm = %r "
+                             "(fp32 runs it)" % (precision, engine.model_norm(self)))
         self.__dict__["_yolat_train_precision"] = precision
         return self
 

@@ -676,6 +676,7 @@ int model_ok(const yolat_model_eval_bf16* mh) {
   const yolat_model_eval* m = mh->base;
   if (m->n_blocks < 1 || m->n_blocks > YOLAT_MAX_LAYERS || m->n_blocks_out < 1 || m->n_blocks_out > m->n_blocks)
     return YOLAT_E_INVALID;
+  if (m->norm != YOLAT_NORM_BATCH) return YOLAT_E_UNSUPPORTED;     // a row-norm base (rownorm.hip) runs on the fp32 forward only
   const long D = m->C * m->n_blocks_out;
   // shapes the bf16 kernels are written for (the reference's: n_filters 64, fusion 1024, classifier 512/256)
   if (m->C != 64 || m->F % 64 != 0 || D % 64 != 0 || (2 * (m->F + D)) % 64 != 0 || m->H1 % 64 != 0 || m->H2 % 64 != 0)

@@ -13,6 +13,7 @@ struct Plan {
   float* gx_work;                                      // split-K partials of cls1 on yolat_gemm_x6 (few proposals)
   uint16_t* Zs;                                        // Z pre-split for the skinny bf16x6 classifier (few proposals)
   float* act_work;                                     // leaky activation: BatchNorm output of a fusion column range
+  float* rn_work;                                      // row norm, generic route: a row range of the fusion block's output
   size_t bytes;
 };
 
@@ -41,6 +42,8 @@ Plan carve(const yolat_model_eval* m, long N, long E, long P, void* ws) {
   const bool act_x6 = m->Wf_hi && m->Wf_mid && m->Wf_lo && m->tf_fold && m->Wfs_hi && m->Wfs_mid && m->Wfs_lo && m->tfs_fold &&
                       (D == 64 || D == 128) && F % 64 == 0 && (long)P * 2 * (F + D) < (1LL << 32);     // (forward_eval_impl's fusion_x6)
   p.act_work = m->act != YOLAT_ACT_RELU && !act_x6 ? c.take<float>((long)yolat_fusion_pair_eval_act_work_elems(N, F)) : nullptr;
+  // (likewise: only a row-norm descriptor whose fusion block takes the materialising route carves this)
+  p.rn_work = m->norm != YOLAT_NORM_BATCH && !(act_x6 && yl_rn_fused(m, N)) ? c.take<float>((long)yolat_fusion_pair_eval_rn_work_elems(N, F)) : nullptr;
   p.bytes = c.off + 256;
   return p;
 }
@@ -304,7 +307,18 @@ static int forward_eval_impl(const yolat_model_eval* m, const float* x, int64_t 
     if (m->act != YOLAT_ACT_LEAKYRELU && m->act != YOLAT_ACT_PRELU) return YOLAT_E_INVALID;
     for (int i = 0; i < 4; ++i) if (!m->act_slope[i]) return YOLAT_E_INVALID;
   }
-  const int relu = leaky ? 0 : 1;
+  // row norm (rownorm.hip) at the same four sites: the GEMMs run with scale = 1, shift = bias and no ReLU, the norm + ReLU
+  // follows in place; the fusion block has a kernel of its own.  norm == 0 takes none of these branches
+  const bool rn = m->norm != YOLAT_NORM_BATCH;
+  if (rn) {
+    if ((m->norm != YOLAT_NORM_LAYER && m->norm != YOLAT_NORM_INSTANCE) || leaky) return YOLAT_E_INVALID;
+    if (m->rn_route < YOLAT_RN_ROUTE_AUTO || m->rn_route > YOLAT_RN_ROUTE_MATERIALISE) return YOLAT_E_INVALID;
+    for (int i = 0; i < 4; ++i) {
+      if ((m->rn_gamma[i] == nullptr) != (m->rn_beta[i] == nullptr)) return YOLAT_E_INVALID;
+      if ((m->norm == YOLAT_NORM_LAYER) != (m->rn_gamma[i] != nullptr)) return YOLAT_E_INVALID;
+    }
+  }
+  const int relu = (leaky || rn) ? 0 : 1;
   Plan p = carve(m, N, E, P, workspace);
   if (p.bytes > workspace_bytes) return YOLAT_E_INVALID;
   if (g != nullptr) YL_TRY(yl_adopt_graph(g, E, &p));      // prepared graph: the kernels read the caller's arrays
@@ -367,7 +381,7 @@ static int forward_eval_impl(const yolat_model_eval* m, const float* x, int64_t 
   ride_a.D = ride_b.D = (int)D; ride_a.F = ride_b.F = (int)F; ride_a.P = ride_b.P = (int)P;
   ride_a.seg_ptr = ride_b.seg_ptr = p.seg_ptr; ride_a.Z = ride_b.Z = p.Z; ride_a.ldz = ride_b.ldz = ZW;
   ride_a.parts = YL_POOL_ZERO | YL_POOL_MEAN; ride_a.blocks = small_pool && fusion_x6 ? 256 : 0;
-  ride_b.parts = YL_POOL_MAX; ride_b.blocks = small_pool && fusion_x6 ? 64 : 0;
+  ride_b.parts = YL_POOL_MAX; ride_b.blocks = small_pool && fusion_x6 && !rn ? 64 : 0;   // (rides in the ReLU / leaky fusion launch)
   int pool_done = 0;
 
   // ---- conv layers (torch_vertex.py:319-337), outputs written into their concat slots
@@ -509,7 +523,20 @@ static int forward_eval_impl(const yolat_model_eval* m, const float* x, int64_t 
   // fusion block over the nodes + per-proposal max, and fusion_block_super over the per-proposal means
   // (arch:61-63,65-69,122): two independent GEMMs in one flattened launch
   snprintf(nm, sizeof nm, "fusion_gemm+segmax[N x %ld -> %ld -> P] | super[P x %ld -> %ld]", D, F, D, F);
-  if (leaky && fusion_x6) {
+  if (rn && fusion_x6 && yl_rn_fused(m, N)) {
+    // GEMM + row norm + ReLU + per-proposal max in one launch; Wf_hi.. are the centred weights (yolat_hip.h).  Its time is
+    // flat in N up to one workgroup per CU (93 us), the materialising route's grows with N: below ~12 k rows that one wins
+    YL_STAGE(nm, 4.0 * N * D * F + 2.0 * P * D * F, 4.0 * (N * D + 2.0 * D * F + 2.0 * P * F + N + P * D),
+             yolat_fusion_pair_eval_x6_rn(p.feats, D, N, D, m->Wf_hi, m->Wf_mid, m->Wf_lo, m->tf_fold, F, m->rn_gamma[0],
+                                          m->rn_beta[0], p.node_seg, p.Z, ZW, sup, ZW, P, m->Wfs_hi, m->Wfs_mid, m->Wfs_lo,
+                                          m->tfs_fold, m->rn_gamma[1], m->rn_beta[1], p.Z + F + D, ZW, m->rn_eps, stream));
+  } else if (rn) {
+    // few rows, or other widths: row ranges of the fusion block's output materialised, normalised in place and pooled
+    YL_STAGE(nm, 2.0 * (N + P) * D * F, 4.0 * (N * D + 2.0 * D * F + 2.0 * P * F + N + P * D + 4.0 * N * F),
+             yolat_fusion_pair_eval_rn(p.feats, D, N, D, m->Wf, m->bf, F, m->rn_gamma[0], m->rn_beta[0], p.node_seg, p.Z, ZW,
+                                       sup, ZW, P, m->Wfs, m->bfs, m->rn_gamma[1], m->rn_beta[1], p.Z + F + D, ZW, m->rn_eps,
+                                       p.rn_work, stream));
+  } else if (leaky && fusion_x6) {
     // signed pooling (segmax.hpp fx_signed_max): the activation-aware instantiation of the rows kernel on start values of
     // -inf / 0 per proposal — one launch more than the ReLU pair
     YL_STAGE("pool_init_signed[P x F]", 0, 4.0 * P * F, yolat_pool_init_signed(p.seg_ptr, P, F, p.Z, ZW, stream));
@@ -542,23 +569,32 @@ static int forward_eval_impl(const yolat_model_eval* m, const float* x, int64_t 
   // launch_gemm_nt) runs the same tiles with the products on the bf16 matrix cores (linear_sk_x6.hip).
   // YOLAT_CLS1_SK_X6=0: the fp32-input MFMA kernel, as YOLAT_STRICT_FP32=1 selects it.
   static const bool sk_x6_on = []() { const char* v = getenv("YOLAT_CLS1_SK_X6"); return !(v && v[0] == '0'); }();
+  const float *sc1 = rn ? nullptr : m->sc1, *tc1 = rn ? nullptr : m->tc1, *sc2 = rn ? nullptr : m->sc2, *tc2 = rn ? nullptr : m->tc2;
   const bool cls1_sk = sk_x6_on && !cls1_gx && !cls_x6 && !yl_strict_fp32() && ZW >= 1024 && ZW % 128 == 0 &&
                        (long)yl_cdiv(P, 64) * yl_cdiv(m->H1, 64) < 160 && yl_aligned16(p.Z) && yl_aligned16(m->Wc1);
   snprintf(nm, sizeof nm, "cls1[P x %ld -> %ld]", ZW, (long)m->H1);
   YL_STAGE(nm, 2.0 * P * ZW * m->H1, 4.0 * (P * ZW + ZW * m->H1 + P * m->H1),
            cls1_gx ? yolat_gemm_x6(p.Z, ZW, P, ZW, m->Wc1_gx, m->tc1_gx, relu, m->H1, p.c1, m->H1, p.gx_work, stream)
            : cls_x6 ? cls1_x6(p.Z, ZW, P, p.Zs, m->Wc_x6[0], m->tc_fold[0], relu, m->H1, p.c1, stream)
-           : cls1_sk ? yolat_linear_sk_x6(p.Z, ZW, P, ZW, m->Wc1, ZW, m->bc1, m->H1, m->sc1, m->tc1, relu, p.c1, m->H1, stream)
-                  : yolat_linear_fwd(p.Z, ZW, P, ZW, nullptr, nullptr, 0, m->Wc1, ZW, m->bc1, m->H1, m->sc1, m->tc1, relu,
+           : cls1_sk ? yolat_linear_sk_x6(p.Z, ZW, P, ZW, m->Wc1, ZW, m->bc1, m->H1, sc1, tc1, relu, p.c1, m->H1, stream)
+                  : yolat_linear_fwd(p.Z, ZW, P, ZW, nullptr, nullptr, 0, m->Wc1, ZW, m->bc1, m->H1, sc1, tc1, relu,
                                      p.c1, m->H1, 0, nullptr, stream));
+  if (rn)
+    YL_STAGE("cls1_rownorm[P x H1]", 8.0 * P * m->H1, 8.0 * P * m->H1,
+             yolat_rownorm_act(p.c1, m->H1, P, m->H1, m->rn_gamma[2], m->rn_beta[2], m->rn_eps, 1, p.c1, m->H1, nullptr, nullptr,
+                               stream));
   if (leaky)
     YL_STAGE("cls1_act[P x H1]", 1.0 * P * m->H1, 8.0 * P * m->H1,
              yolat_scale_shift_act(p.c1, m->H1, P, m->H1, nullptr, nullptr, m->act_slope[2], p.c1, m->H1, stream));
   snprintf(nm, sizeof nm, "cls2[P x %ld -> %ld]", (long)m->H1, (long)m->H2);
   YL_STAGE(nm, 2.0 * P * m->H1 * m->H2, 4.0 * (P * m->H1 + m->H1 * m->H2 + P * m->H2),
            cls_x6 ? yolat_linear_x6(p.c1, m->H1, P, m->H1, m->Wc_x6[1], m->tc_fold[1], relu, m->H2, p.c2, m->H2, stream)
-                  : yolat_linear_fwd(p.c1, m->H1, P, m->H1, nullptr, nullptr, 0, m->Wc2, m->H1, m->bc2, m->H2, m->sc2,
-                                     m->tc2, relu, p.c2, m->H2, 0, nullptr, stream));
+                  : yolat_linear_fwd(p.c1, m->H1, P, m->H1, nullptr, nullptr, 0, m->Wc2, m->H1, m->bc2, m->H2, sc2,
+                                     tc2, relu, p.c2, m->H2, 0, nullptr, stream));
+  if (rn)
+    YL_STAGE("cls2_rownorm[P x H2]", 8.0 * P * m->H2, 8.0 * P * m->H2,
+             yolat_rownorm_act(p.c2, m->H2, P, m->H2, m->rn_gamma[3], m->rn_beta[3], m->rn_eps, 1, p.c2, m->H2, nullptr, nullptr,
+                               stream));
   if (leaky)
     YL_STAGE("cls2_act[P x H2]", 1.0 * P * m->H2, 8.0 * P * m->H2,
              yolat_scale_shift_act(p.c2, m->H2, P, m->H2, nullptr, nullptr, m->act_slope[3], p.c2, m->H2, stream));

@@ -114,6 +114,10 @@ int yl_fusion_pair_eval_x6_impl(const float* A, int64_t lda, int64_t N, int64_t 
                                 const uint16_t* Wsm, const uint16_t* Wsl, const float* tsfold, float* Ys, int64_t ldys,
                                 const PoolRider* rider, yolat_stream_t stream, const float* slope_f = nullptr,
                                 const float* slope_s = nullptr);
+// the fusion pair behind a row norm (rownorm.hip): does a batch of N nodes run the fused kernel (true) or the materialising
+// route?  The descriptor's rn_route, or N >= YOLAT_RN_FUSED_MIN_ROWS when that is YOLAT_RN_ROUTE_AUTO: a function of the
+// descriptor and N alone, so the workspace sizing and the forward always agree.
+bool yl_rn_fused(const yolat_model_eval* m, int64_t N);
 // k_pool_prepare restricted to `parts` (segment.hip)
 int yl_pool_prepare_parts(const float* feats, const float* fsup, int64_t ld, int64_t D, int64_t F, const int32_t* seg_ptr,
                           int64_t P, float* Z, int64_t ldz, int parts, yolat_stream_t stream);

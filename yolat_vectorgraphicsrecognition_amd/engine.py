@@ -146,6 +146,49 @@ def model_is_relu(model):
     return all(a is True for a in model_act(model))
 
 
+def model_norm(model):
+    """The norm behind the conv stack: "batch", "layer" or "instance" — the four sites (fusion_block, fusion_block_super,
+    prediction_cls.0, .1) must agree (they are all built from opt.norm)."""
+    net = model.cls_net
+    kinds = set()
+    for b in (net.fusion_block, net.fusion_block_super, model.prediction_cls[0], model.prediction_cls[1]):
+        mods = [m for m in b.children() if isinstance(m, (torch.nn.BatchNorm1d, torch.nn.LayerNorm, torch.nn.InstanceNorm1d))]
+        if len(mods) != 1:
+            raise NotImplementedError("every fusion / classifier block needs one norm (batch, layer or instance)")
+        kinds.add(("batch", "layer", "instance")[ops.norm_kind(mods[0])])
+    if len(kinds) != 1:
+        raise NotImplementedError("the four sites behind the conv stack must share one norm, got %s" % sorted(kinds))
+    return kinds.pop()
+
+
+def _lbr_fwd_rownorm(a, lin, norm, relu, training, out, act_out):
+    """lbr_fwd behind nn.LayerNorm / nn.InstanceNorm1d (csrc/rownorm.hip): a per-row normalisation cannot ride along as a
+    per-column (scale, shift) prologue, so the output is materialised (into ``act_out`` when given); training saves the
+    pre-norm tensor and the per-row mean / rstd, the backward recomputes the rest.  The same arithmetic in train() and
+    eval(): no batch counters, no running statistics."""
+    if relu is not True and relu is not False:
+        raise NotImplementedError("norm %s with act %s has no MI355X kernel (relu only)"
+                                  % (norm.__class__.__name__, relu.__class__.__name__))
+    A = a.t
+    M, dev = A.shape[0], A.device
+    C = lin.out_features
+    gamma, beta, eps = ops.rownorm_params(norm)
+    sv = {"a": a, "lin": lin, "bn": norm, "relu": relu, "rownorm": True}
+    if training:
+        y = _empty(M, C, dev) if out is None else out
+        ops.linear_fwd(A, lin.weight, lin.bias, y, a_pro=a.pro, a_relu=a.relu)
+        z = _empty(M, C, dev) if act_out is None else act_out
+        stats = torch.empty(2, M, dtype=torch.float32, device=dev)            # mean, rstd
+        ops.rownorm_act(y, gamma, beta, eps, relu, z, stats[0], stats[1])
+        sv.update(y=y, stats=stats)
+        return Lazy(z), sv
+    z = act_out if act_out is not None else (_empty(M, C, dev) if out is None else out)
+    ops.linear_fwd(A, lin.weight, lin.bias, z, a_pro=a.pro, a_relu=a.relu)
+    ops.rownorm_act(z, gamma, beta, eps, relu, z)
+    sv["y"] = z
+    return Lazy(z), sv
+
+
 def _lbr_fwd_leaky(a, lin, bn, act, training, out, coef_out, act_out):
     """lbr_fwd for a leaky activation: the BatchNorm output is never handed on lazily — the activation is materialised by
     ops.scale_shift_act (into ``act_out`` when given), the backward recomputes the BatchNorm output from the saved
@@ -180,7 +223,12 @@ def lbr_fwd(a, lin, bn, relu, training, out=None, coef_out=None, dense=False, ac
     """a: Lazy input [M,K].  Returns (Lazy output, saved).  ``out`` optionally names the [M,C]
     destination (may be a column slice of a wider buffer).  dense: the training GEMMs of this layer (forward, dX, dW)
     on bf16 operands ("bf16_dense" training precision, ops.bt_*).  relu: True / False, or the nn.LeakyReLU / nn.PReLU
-    module of the block (block_act) — then the output is materialised, into ``act_out`` when given."""
+    module of the block (block_act) — then the output is materialised, into ``act_out`` when given.  bn: the block's
+    nn.BatchNorm1d, or its nn.LayerNorm / nn.InstanceNorm1d (materialised likewise), or None."""
+    if bn is not None and ops.is_rownorm(bn):
+        if dense:
+            raise ValueError("bf16_dense training covers norm = batch only: this block's norm is %s" % bn.__class__.__name__)
+        return _lbr_fwd_rownorm(a, lin, bn, relu, training, out, act_out)
     if relu is not True and relu is not False:
         if dense:
             raise ValueError("bf16_dense training covers act = relu only: this block's act is %s" % relu.__class__.__name__)
@@ -384,7 +432,12 @@ def lbr_bwd(sv, dz, sink, dx_out=None, dx_accumulate=False, need_dx=True, dz_inp
     a, lin, bn, relu, y = sv["a"], sv["lin"], sv["bn"], sv["relu"], sv["y"]
     M, dev = y.shape[0], y.device
     act = sv.get("act")
-    if act is not None:
+    if sv.get("rownorm"):
+        gamma, beta, _ = ops.rownorm_params(bn)
+        dy = dz if dz_inplace else torch.empty(M, y.shape[1], dtype=torch.float32, device=dev)
+        ops.rownorm_act_bwd(dz, y, sv["stats"][0], sv["stats"][1], gamma, beta, relu,
+                            sink.get(gamma) if gamma is not None else None, sink.get(beta) if beta is not None else None, dy)
+    elif act is not None:
         coef = sv["coef"]
         dy = dz if dz_inplace else torch.empty(M, y.shape[1], dtype=torch.float32, device=dev)
         dslope = sink.get(act.weight) if isinstance(act, torch.nn.PReLU) else None
@@ -602,6 +655,10 @@ def model_fwd(model, g, x, training):
     act_f, act_s, act_1, act_2 = model_act(model)
     if training and half and not model_is_relu(model):
         raise ValueError("train precision %r covers act = relu only (this model's act is not): use 'fp32'" % precision)
+    rownorm = ops.is_rownorm(net.fusion_block[1])                    # (plan.py / trainer.py check that the four sites agree)
+    if training and half and rownorm:
+        raise ValueError("train precision %r covers norm = batch only (this model's norm is %s): use 'fp32'"
+                         % (precision, model_norm(model)))
     if dense:
         check_bf16_dense_shapes(model)
 
@@ -624,7 +681,8 @@ def model_fwd(model, g, x, training):
     # fusion block over nodes, then per-proposal max                                  (arch:61-63,122)
     arg_fus = None
     arg_feat = torch.empty(P, D, dtype=torch.int32, device=dev) if training else None
-    if training and FUSED_FUSION_TRAIN and D == 128 and net.fusion_block[0].weight.is_contiguous() and act_f is True:
+    if (training and FUSED_FUSION_TRAIN and D == 128 and net.fusion_block[0].weight.is_contiguous() and act_f is True
+            and not rownorm):
         # no [N,F] activation: batch statistics from the Gram matrix of feats, extreme-of-z GEMM epilogue,
         # sparse backward (csrc/fusion_train.hip)
         sv_fus = ops.fusion_pool_train_fwd(feats, net.fusion_block[0], net.fusion_block[1], g, Z[:, 0:F], bf16=dense)
@@ -633,7 +691,7 @@ def model_fwd(model, g, x, training):
             _PENDING_NBT.append(net.fusion_block[1].num_batches_tracked)
     else:
         # (a leaky activation always comes here: activated per element, THEN the maximum with its argmax — right for
-        # any slope, where pooling the pre-activation is not)
+        # any slope, where pooling the pre-activation is not; a row norm too: its output is materialised)
         fus, sv_fus = lbr_fwd(Lazy(feats), net.fusion_block[0], net.fusion_block[1], act_f, training)
         arg_fus = torch.empty(P, F, dtype=torch.int32, device=dev) if training else None
         ops.segment_max_fwd(fus.t, g, Z[:, 0:F], arg_fus, x_pro=fus.pro, x_relu=fus.relu)
@@ -648,7 +706,7 @@ def model_fwd(model, g, x, training):
     fs, sv_fs = lbr_fwd(Lazy(sup), net.fusion_block_super[0], net.fusion_block_super[1], act_s, training,
                         out=(None if training else Z[:, F + D:2 * F + D]), dense=dense,
                         act_out=Z[:, F + D:2 * F + D])
-    if training and act_s is True:
+    if training and act_s is True and not rownorm:
         ops.scale_shift_relu(fs.t, fs.scale, fs.shift, True, Z[:, F + D:2 * F + D])
     # classifier                                                                      (arch:91-93,128)
     m1, m2, m3 = model.prediction_cls[0], model.prediction_cls[1], model.prediction_cls[2]

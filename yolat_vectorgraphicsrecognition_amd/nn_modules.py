@@ -40,12 +40,16 @@ def act_layer(act_type, inplace=False, neg_slope=0.2, n_prelu=1):
 
 
 def norm_layer(norm_type, nc):
-    """torch_nn.py:23-34.  Only 'batch' has a HIP implementation."""
+    """torch_nn.py:23-34.  Parameter containers: 'batch' is folded into the GEMM epilogues / operand prologues, 'layer' and
+    'instance' — on the [M, nc] inputs of an MLP one per-row normalisation over the nc columns, the same in train() and
+    eval() — run on the kernels of csrc/rownorm.hip."""
     norm = norm_type.lower()
     if norm == "batch":
         return nn.BatchNorm1d(nc, affine=True)
-    if norm in ("layer", "instance"):
-        raise NotImplementedError("normalization layer [%s] has no MI355X kernel (arch uses batch)" % norm)
+    if norm == "layer":
+        return nn.LayerNorm(nc, elementwise_affine=True)
+    if norm == "instance":
+        return nn.InstanceNorm1d(nc, affine=False)
     raise NotImplementedError("normalization layer [%s] is not found" % norm)
 
 
@@ -65,13 +69,14 @@ class MultiSeq(nn.Sequential):
 
 
 def _groups(seq):
-    """Split an MLP's children into (Linear, BatchNorm1d|None, act, dropout_p) groups; act: False (none), True (ReLU) or
-    the nn.LeakyReLU / nn.PReLU module itself (engine.lbr_fwd takes the kind and the slope from it)."""
+    """Split an MLP's children into (Linear, norm|None, act, dropout_p) groups; norm: the nn.BatchNorm1d, nn.LayerNorm or
+    nn.InstanceNorm1d module; act: False (none), True (ReLU) or the nn.LeakyReLU / nn.PReLU module itself (engine.lbr_fwd
+    takes the kind and the slope from it)."""
     groups = []
     for m in seq.children():
         if isinstance(m, nn.Linear):
             groups.append([m, None, False, 0.0])
-        elif isinstance(m, nn.BatchNorm1d):
+        elif isinstance(m, (nn.BatchNorm1d, nn.LayerNorm, nn.InstanceNorm1d)):
             groups[-1][1] = m
         elif isinstance(m, nn.ReLU):
             groups[-1][2] = True
@@ -119,6 +124,10 @@ class MLP(nn.Sequential):
     """torch_nn.py:50-71: [Linear, (norm), (act), (Dropout2d)] per layer."""
 
     def __init__(self, channels, act="relu", norm=None, bias=True, drop=0., last_lin=False):
+        if (norm is not None and norm.lower() in ("layer", "instance") and act is not None
+                and act.lower() in ("leakyrelu", "prelu")):
+            raise NotImplementedError("norm = %s with act = %s has no MI355X kernel: the row norms (csrc/rownorm.hip) pool and "
+                                      "gate behind a ReLU only; use act = relu, or norm = batch" % (norm, act))
         m = []
         for i in range(1, len(channels)):
             m.append(nn.Linear(channels[i - 1], channels[i], bias))

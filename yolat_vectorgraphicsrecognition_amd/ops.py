@@ -686,6 +686,111 @@ def fusion_pair_eval_act(A, lin_f, fold_f, slope_f, g, pool, S=None, lin_s=None,
 
 
 # ---------------------------------------------------------------------------------------------
+# row norms (csrc/rownorm.hip): nn.LayerNorm / nn.InstanceNorm1d(affine=False) on [M, nc] — one per-row arithmetic
+# ---------------------------------------------------------------------------------------------
+
+NORM_BATCH, NORM_LAYER, NORM_INSTANCE = 0, 1, 2
+RN_ROWS = 128          # YOLAT_RN_ROWS: rows per workgroup of the fused eval kernel
+RN_ROUTE_AUTO, RN_ROUTE_FUSED, RN_ROUTE_MATERIALISE = 0, 1, 2       # YOLAT_RN_ROUTE_*
+
+
+def is_rownorm(mod):
+    return isinstance(mod, (torch.nn.LayerNorm, torch.nn.InstanceNorm1d))
+
+
+def norm_kind(mod):
+    """YOLAT_NORM_* of a norm module (torch_nn.py:23-34)."""
+    if isinstance(mod, torch.nn.BatchNorm1d):
+        return NORM_BATCH
+    if isinstance(mod, torch.nn.LayerNorm):
+        if len(mod.normalized_shape) != 1 or mod.weight is None or mod.bias is None:
+            raise NotImplementedError("norm layer: LayerNorm over one dimension with weight and bias (the reference's)")
+        return NORM_LAYER
+    if isinstance(mod, torch.nn.InstanceNorm1d):
+        if mod.affine or mod.track_running_stats:
+            raise NotImplementedError("norm instance: InstanceNorm1d(affine=False, track_running_stats=False) (the reference's)")
+        return NORM_INSTANCE
+    raise NotImplementedError("norm layer %s has no MI355X kernel" % mod.__class__.__name__)
+
+
+def rownorm_params(mod):
+    """(gamma, beta, eps) of a row-norm module; gamma / beta None for the instance norm."""
+    if norm_kind(mod) == NORM_LAYER:
+        return mod.weight, mod.bias, float(mod.eps)
+    return None, None, float(mod.eps)
+
+
+def rownorm_act(Y, gamma, beta, eps, relu, Z, save_mean=None, save_rstd=None):
+    """Z = relu?(rownorm(Y) * gamma + beta); Z may be Y; save_mean / save_rstd [M] optional."""
+    M, C = Y.shape
+    check(lib.yolat_rownorm_act(_f(Y), _ld(Y), M, C, _f(gamma, "gamma", True), _f(beta, "beta", True), float(eps), int(bool(relu)),
+                                _f(Z), _ld(Z), _f(save_mean, "save_mean", True), _f(save_rstd, "save_rstd", True), _stream()),
+          "yolat_rownorm_act")
+    return Z
+
+
+def rownorm_act_bwd(dZ, Y, save_mean, save_rstd, gamma, beta, relu, dgamma, dbeta, dY, accumulate=False):
+    """Backward of rownorm_act from the saved pre-norm Y, mean and rstd; dgamma / dbeta None with gamma None."""
+    M, C = Y.shape
+    work = None
+    if gamma is not None:
+        work = torch.empty(int(lib.yolat_rownorm_act_bwd_work_elems(M, C)), dtype=torch.float32, device=Y.device)
+    check(lib.yolat_rownorm_act_bwd(_f(dZ), _ld(dZ), _f(Y), _ld(Y), M, C, _f(save_mean), _f(save_rstd), _f(gamma, "gamma", True),
+                                    _f(beta, "beta", True), int(bool(relu)), _f(dgamma, "dgamma", True), _f(dbeta, "dbeta", True),
+                                    int(accumulate), _f(dY), _ld(dY), work.data_ptr() if work is not None else None,
+                                    _stream()), "yolat_rownorm_act_bwd")
+    return dY
+
+
+def rownorm_center(weight, bias):
+    """The operands of yolat_fusion_pair_eval_x6_rn from a Linear [F, D]: Wc = W - mean over the F outputs, bc = b - mean(b)
+    (taken in float64, rounded once), so that A . Wc^T + bc is the product with its row mean already removed."""
+    w = weight.detach().double()
+    wc = (w - w.mean(0, keepdim=True)).float().contiguous()
+    b = bias.detach().double() if bias is not None else torch.zeros(weight.shape[0], dtype=torch.float64, device=weight.device)
+    return wc, (b - b.mean()).float().contiguous()
+
+
+def split_bf16x3(w, row_scale=None):
+    """Exact 3-way bfloat16 split (hi, mid, lo) of a contiguous fp32 matrix, rows scaled first when row_scale is given
+    (yolat_split_bf16x3) — the one caller of that entry point (plan.py's weight splits come here too)."""
+    rows, cols = w.shape
+    parts = [torch.empty(rows * cols, dtype=torch.bfloat16, device=w.device) for _ in range(3)]
+    check(lib.yolat_split_bf16x3(_f(w), cols, rows, cols, _f(row_scale, "row_scale", True), parts[0].data_ptr(), parts[1].data_ptr(), parts[2].data_ptr(),
+                                 _stream()), "yolat_split_bf16x3")
+    return parts
+
+
+def fusion_pair_eval_x6_rn(A, lin_f, gb_f, node_seg, pool, S, lin_s, gb_s, Ys, eps):
+    """yolat_fusion_pair_eval_x6_rn: pool[P,F] (zero-filled by the caller) = per-proposal max of relu(rownorm(lin_f(A)) g + b),
+    Ys = the same of lin_s(S) stored; gb_* = (gamma, beta) or (None, None)."""
+    N, D = A.shape
+    F = lin_f.weight.shape[0]
+    wf, tf = rownorm_center(lin_f.weight, lin_f.bias)
+    ws, ts = rownorm_center(lin_s.weight, lin_s.bias)
+    pf, ps = split_bf16x3(wf), split_bf16x3(ws)
+    check(lib.yolat_fusion_pair_eval_x6_rn(
+        _f(A), _ld(A), N, D, pf[0].data_ptr(), pf[1].data_ptr(), pf[2].data_ptr(), _f(tf), F, _f(gb_f[0], "gamma", True),
+        _f(gb_f[1], "beta", True), node_seg.data_ptr(), _f(pool), _ld(pool), _f(S), _ld(S), S.shape[0], ps[0].data_ptr(),
+        ps[1].data_ptr(), ps[2].data_ptr(), _f(ts), _f(gb_s[0], "gamma", True), _f(gb_s[1], "beta", True), _f(Ys), _ld(Ys),
+        float(eps), _stream()), "yolat_fusion_pair_eval_x6_rn")
+    return pool
+
+
+def fusion_pair_eval_rn(A, lin_f, gb_f, node_seg, pool, S, lin_s, gb_s, Ys, eps):
+    """yolat_fusion_pair_eval_rn: the materialising form of fusion_pair_eval_x6_rn, any D / F."""
+    N, D = A.shape
+    F = lin_f.weight.shape[0]
+    work = torch.empty(int(lib.yolat_fusion_pair_eval_rn_work_elems(N, F)), dtype=torch.float32, device=A.device)
+    check(lib.yolat_fusion_pair_eval_rn(
+        _f(A), _ld(A), N, D, _f(lin_f.weight), _f(lin_f.bias, "bias", True), F, _f(gb_f[0], "gamma", True),
+        _f(gb_f[1], "beta", True), node_seg.data_ptr(), _f(pool), _ld(pool), _f(S), _ld(S), S.shape[0], _f(lin_s.weight),
+        _f(lin_s.bias, "bias", True), _f(gb_s[0], "gamma", True), _f(gb_s[1], "beta", True), _f(Ys), _ld(Ys), float(eps),
+        work.data_ptr(), _stream()), "yolat_fusion_pair_eval_rn")
+    return pool
+
+
+# ---------------------------------------------------------------------------------------------
 # edge convolution
 # ---------------------------------------------------------------------------------------------
 

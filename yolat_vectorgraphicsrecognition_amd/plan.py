@@ -75,9 +75,8 @@ def _split3(w, row_scale, packed, keep):
         check(lib.yolat_split_bf16x3_packed(_ptr(w), cols, rows, cols, scale, parts[0].data_ptr(), ops._stream()),
               "yolat_split_bf16x3_packed")
     else:
-        parts = [torch.empty(rows * cols, dtype=torch.bfloat16, device=w.device) for _ in range(3)]
-        check(lib.yolat_split_bf16x3(_ptr(w), cols, rows, cols, scale, parts[0].data_ptr(), parts[1].data_ptr(),
-                                     parts[2].data_ptr(), ops._stream()), "yolat_split_bf16x3")
+        _ptr(w)
+        parts = ops.split_bf16x3(w, row_scale)
     keep.extend(parts)
     return [p.data_ptr() for p in parts]
 
@@ -92,9 +91,12 @@ class EvalPlan(object):
     def __init__(self, model, precision="fp32"):
         if precision not in ("fp32", "bf16"):
             raise ValueError("precision must be 'fp32' or 'bf16'")
-        from .engine import model_is_relu
+        from .engine import model_is_relu, model_norm
         if precision != "fp32" and not model_is_relu(model):
             raise ValueError("the %s eval plan covers act = relu only (this model's act is not)" % precision)
+        if precision != "fp32" and model_norm(model) != "batch":
+            raise ValueError("the %s eval plan covers norm = batch only (this model's norm is %s)"
+                             % (precision, model_norm(model)))
         self.precision = precision
         self._desc_h = None
         self.model = model
@@ -202,6 +204,9 @@ class EvalPlan(object):
                 t = ops.act_slope(a, dev)
                 keep.append(t)
                 d.act_slope[i] = t.data_ptr()
+        from .engine import model_norm
+        if model_norm(m) != "batch":
+            return self._build_head_rownorm(d, dev, keep, bool(kinds))
         (d.Wf, d.bf, d.sf, d.tf), ff = _lin_bn(fb[0], fb[1], dev, keep)
         (d.Wfs, d.bfs, d.sfs, d.tfs), ffs = _lin_bn(fs[0], fs[1], dev, keep)
         # Linear + BatchNorm for the bf16x6-emulated fusion kernel: BatchNorm scale folded into the weight rows, exact 3-way
@@ -232,6 +237,55 @@ class EvalPlan(object):
                 d.Wc_x6[i] = _split3(lin.weight, fold[0] if fold is not None else None, True, keep)[0]
                 d.tc_fold[i] = _shift(lin, fold, keep).data_ptr()
         return ff, ffs
+
+    def _build_head_rownorm(self, d, dev, keep, leaky):
+        """_build_head for norm = layer / instance (csrc/rownorm.hip): a row norm does not fold into its Linear, so the
+        descriptor carries plain weights and biases (the BatchNorm scale / shift fields stay NULL and are not read), the
+        LayerNorm weight / bias of each site by ADDRESS, and for the fused fusion kernel the split of the weights centred over
+        their outputs (ops.rownorm_center) with the centred bias."""
+        m, net = self.model, self.model.cls_net
+        if leaky:
+            raise NotImplementedError("norm = layer / instance with act = leakyrelu / prelu has no MI355X kernel")
+        fb, fs = net.fusion_block, net.fusion_block_super
+        m1, m2, m3 = m.prediction_cls[0], m.prediction_cls[1], m.prediction_cls[2]
+        sites = (fb, fs, m1, m2)
+        d.norm = ops.norm_kind(sites[0][1])
+        eps = set()
+        for i, blk in enumerate(sites):
+            gamma, beta, e = ops.rownorm_params(blk[1])
+            eps.add(e)
+            if gamma is not None:
+                d.rn_gamma[i], d.rn_beta[i] = _ptr(gamma), _ptr(beta)
+        if len(eps) != 1:
+            raise NotImplementedError("the eval plan needs one eps at all four norm sites, got %s" % sorted(eps))
+        d.rn_eps = eps.pop()
+        # which fusion-pair route: by the node count (DESIGN.md 3i) unless YOLAT_RN_FUSED=1 | 0 names one — read HERE, once
+        # per descriptor build, so a plan's workspace sizing and its forwards cannot disagree (the tests and
+        # tools/rownorm_ab.py run both routes on one graph)
+        d.rn_route = {"1": ops.RN_ROUTE_FUSED, "0": ops.RN_ROUTE_MATERIALISE}.get(os.environ.get("YOLAT_RN_FUSED", ""),
+                                                                                   ops.RN_ROUTE_AUTO)
+        d.Wf, d.bf = _ptr(fb[0].weight), _ptr(fb[0].bias)
+        d.Wfs, d.bfs = _ptr(fs[0].weight), _ptr(fs[0].bias)
+        if _x6_on() and fb[0].in_features in (64, 128) and d.F % 64 == 0:
+            for lin, names in ((fb[0], ("Wf_hi", "Wf_mid", "Wf_lo", "tf_fold")), (fs[0], ("Wfs_hi", "Wfs_mid", "Wfs_lo", "tfs_fold"))):
+                wc, bc = ops.rownorm_center(lin.weight, lin.bias)
+                keep += [wc, bc]
+                hi, mid, lo = _split3(wc, None, False, keep)
+                for n, v in zip(names, (hi, mid, lo, bc.data_ptr())):
+                    setattr(d, n, v)
+        d.H1, d.H2 = m1[0].out_features, m2[0].out_features
+        d.Wc1, d.bc1 = _ptr(m1[0].weight), _ptr(m1[0].bias)
+        d.Wc2, d.bc2 = _ptr(m2[0].weight), _ptr(m2[0].bias)
+        d.Wc3, d.bc3 = _ptr(m3[0].weight), _ptr(m3[0].bias)
+        # prediction_cls.0 on the LDS-tiled bf16x6 GEMM (yolat_gemm_x6): packed without a row scale, shift = bias
+        if _x6_on() and m1[0].in_features % 16 == 0:
+            rows, cols = m1[0].out_features, m1[0].in_features
+            packed = torch.empty(lib.yolat_gemm_x6_packed_elems(rows, cols), dtype=torch.bfloat16, device=dev)
+            check(lib.yolat_gemm_x6_pack(_ptr(m1[0].weight), cols, rows, cols, None, packed.data_ptr(), ops._stream()),
+                  "yolat_gemm_x6_pack")
+            keep.append(packed)
+            d.Wc1_gx, d.tc1_gx = packed.data_ptr(), _shift(m1[0], None, keep).data_ptr()
+        return None, None
 
     def _build_bf16(self, d, convs, layers, ff, ffs, dev, keep):
         """The bf16-storage descriptor on top of `d`, from the folds computed for it (layers: _build_conv's results)."""

@@ -341,6 +341,8 @@ class TrainPlan(object):
             m1, m2, m3 = m.prediction_cls[0], m.prediction_cls[1], m.prediction_cls[2]
             if not engine.model_is_relu(m):       # act = leakyrelu / prelu: the Python schedule (engine.py) runs the step
                 return False
+            if engine.model_norm(m) != "batch":   # norm = layer / instance: likewise
+                return False
             if engine._drop_p(m2) > 0 or len(list(m3.children())) != 1:
                 return False
             for cv in convs:
