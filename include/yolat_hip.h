@@ -1098,6 +1098,31 @@ int yolat_detect_match(const float* det, const int32_t* det_count, int64_t B, co
                        const float* gt_labels, int64_t G, const int32_t* gt_ptr, const float* thresholds, int64_t T,
                        uint8_t* tp_out, yolat_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * The detection of one batch in ONE call (csrc/detect.hip; SparseCADGCN.detect_submit): logits -> det, nothing read
+ * back, nothing sized by a number the device computes.  On `stream`, in this order: the launches of
+ * yolat_predict_select (same arguments, same record in sel [4 + B + 1 + R_cap] int32, R_cap = tree->R + tree->Ctot;
+ * sel[1] / sel[2] keep their meaning), the rows kernel, then keys / radix sort / walk of yolat_nms_batched over R_cap
+ * rows with image_ptr = sel + 4.
+ *   The rows kernel reads total = sel[0] on the device.  Row r < total of pred [R_cap, 4 + K] is bit for bit the row
+ *   yolat_predict_gather -> yolat_detect_scores produce (box enlarged by 5 %, times scale[image]; scores); a spare row
+ *   r >= total is all zero, belongs to no image and is never a candidate.  bbox [P, 4] fp32 contiguous, scale [B, 4] on
+ *   the device, tree->B >= 1.
+ *   det_out [B, 300, 6], det_count [B]: as yolat_nms_batched writes them, equal to what it gives on the first `total`
+ *   rows.  workspace: yolat_detect_workspace_bytes(N, P, R, Ctot, K, B) bytes, 256-byte aligned; the query returns 0 and
+ *   the call YOLAT_E_UNSUPPORTED for the shapes yolat_nms_batched (R_cap rows, nc = K - 1) or yolat_predict_select
+ *   decline — decided in front of the first launch.
+ * yolat_detect_rows: the rows kernel alone, on a record yolat_predict_select has written.
+ * ------------------------------------------------------------------------------------------ */
+size_t yolat_detect_workspace_bytes(int64_t N, int64_t P, int64_t R, int64_t Ctot, int64_t K, int64_t B);
+int yolat_detect(const float* logits, int64_t ld_logits, int64_t P, int64_t K, const float* bbox, const int64_t* edge,
+                 int64_t stride_e, int64_t stride_c, const int64_t* bbox_idx, int64_t N, int64_t E,
+                 const yolat_predict_tree* tree, const float* scale, int softmax, float conf_thres, float iou_thres,
+                 int agnostic, int32_t* sel, float* pred, float* det_out, int32_t* det_count, void* workspace,
+                 size_t workspace_bytes, yolat_stream_t stream);
+int yolat_detect_rows(const float* logits, int64_t ld_logits, int64_t P, int64_t K, const float* bbox, const int32_t* sel,
+                      int64_t B, int64_t R_cap, const float* scale, int softmax, float* pred_out, yolat_stream_t stream);
+
 /* Stage profiler of yolat_forward_eval: when enabled, a hipEvent pair is recorded on `stream` around
  * every stage (each stage = the launch(es) of one kernel family); totals accumulate across calls until
  * reset.  yolat_profile_get must be called after the stream has been synchronised.  `flops` / `bytes`

@@ -118,6 +118,60 @@ class _SigmoidFn(torch.autograd.Function):
 # False: always the two-pass sub-graph extraction (module flag; the tests run both)
 PREDICT_ONE_SUBMISSION = True
 
+_PREPARED_BATCH = ("predict() cuts sub-graphs out of the raw edge list: batches from collate_to_device(csr=True) "
+                   "carry the prepared CSR only and support forward() — collate with csr=False for predict()")
+
+
+class DetectHandle(object):
+    """One batch of ``SparseCADGCN.detect_submit`` in flight.  It owns the device tensors of its batch — ``sel`` (the
+    record of yolat_predict_select), ``pred`` [R + Ctot, 4 + K], ``det`` [B, 300, 6], ``det_count`` [B] and the workspace —
+    allocated on the submitting stream and released with the handle, and keeps the batch for the fall-back.
+
+    ``ready()``   the event behind the batch's last launch has completed (a query, no wait)
+    ``result()``  the list of B device tensors [k, 6] ``evaluation.detect_batch`` returns; ONE device -> host read
+                  (ops.d2h) of sel[0:4] and the B detection counts.  A forward that flagged its input raises what
+                  ``check_last_status`` raises; a tree that is not made of its proposals' ranges (sel[1]) goes through the
+                  synchronous ``detect_batch`` on the retained batch — a DeviceLoader batch is collated again from its
+                  host items, its ring slot may have been rewritten since."""
+
+    def __init__(self, model, data, slices, out, det, det_count, sel, pred, workspace, event, kw):
+        self.model, self.data, self.slices, self.kw = model, data, slices, kw
+        self._out, self.det, self.det_count, self.sel, self.pred, self.workspace = out, det, det_count, sel, pred, workspace
+        self.event = event
+        self._result = None
+
+    def ready(self):
+        return bool(self.event.query())
+
+    def result(self):
+        if self._result is not None:
+            return self._result
+        B = int(self.det_count.shape[0])
+        n_det = self.det.numel()
+        host = ops.d2h(self._out[n_det:n_det + B + 4]).tolist()     # det_count [B] | sel[0:4]; stream order: behind the NMS
+        cnt, flag, status = host[:B], host[B + 1], host[B + 2]
+        if status != 0:
+            ops.check_status_word(torch.tensor([status], dtype=torch.int32))      # raises for every flag a forward sets
+        if flag != 0:
+            res = self._fallback()
+        else:
+            res = [self.det[i, :k] for i, k in enumerate(cnt)]
+        self._result = res
+        self._release()
+        return res
+
+    def _fallback(self):
+        from .evaluation import detect_batch
+        data, slices = self.data, self.slices
+        st = data.__dict__.get("_lazy") if hasattr(data, "__dict__") else None
+        if st is not None:
+            from .data import collate_to_device
+            data, slices = collate_to_device(st.items, device=self.det.device)
+        return detect_batch(self.model, data, slices, fixup=False, **self.kw)
+
+    def _release(self):
+        self.data = self.slices = self.pred = self.workspace = None
+
 
 class SparseCADGCN(nn.Module):
     def __init__(self, opt, n_edges=3, edge_max_pool=None, expand_ratio=0.25):
@@ -254,6 +308,127 @@ class SparseCADGCN(nn.Module):
                 return out
         return self._predict_two_pass(data, slices)
 
+    def _predict_operands(self, data, logits, bbox):
+        """(edge address, its two strides, bbox_idx address, N, E, P, device) of the batch whose forward just ran — what
+        yolat_predict_select validates the tree against; None when the edge list is not [E, 2]"""
+        d = data.__dict__ if hasattr(data, "__dict__") else {}
+        raw = d.get("_yolat_raw")
+        if raw is not None:
+            _, _, ep, se, sc, _, bp, N, E, P, dev = raw
+            return ep, se, sc, bp, N, E, P, dev
+        st = self._stage_tensors(data)
+        edge, bidx = st["edge"], st["bbox_idx"]
+        if edge.dim() != 2 or edge.shape[1] != 2:
+            return None
+        return (ops._i(edge, torch.int64, "edge"), edge.stride(0), edge.stride(1), ops._i(bidx, torch.int64, "bbox_idx"),
+                st["x"].shape[0], edge.shape[0], bbox.shape[0], logits.device)
+
+    @staticmethod
+    def _predict_tree(data, slices, dev, scales=None):
+        """The flattened tree (data.flatten_tree) on the device, uploaded once per batch object (keyed by the identity of
+        the tree and the image offsets) -> (yolat_predict_tree, the host arrays, address of the scales or None).
+        scales [B, 4] fp32 (detect_submit) travel in the same upload and are cached with it."""
+        import numpy as np
+        from ._lib import PredictTree
+        from .data import flatten_tree
+        d = data.__dict__ if hasattr(data, "__dict__") else {}
+        key = (id(data.roots), len(data.roots), tuple(int(v) for v in slices["roots"]), tuple(int(v) for v in slices["pos"]),
+               tuple(int(v) for v in slices["edge"]), tuple(int(v) for v in slices["bbox"]))
+        ent = d.get("_yolat_tree")
+        skey = None if scales is None else scales.tobytes()
+        if ent is None or ent[0] != key or (skey is not None and ent[4] != skey):
+            ft = flatten_tree(data, slices)
+            order = ("root_row", "root_range", "child_ptr", "child_row", "child_range", "image_root_ptr")
+            parts = [ft[k].reshape(-1) for k in order]
+            if scales is not None:
+                parts.append(np.ascontiguousarray(scales, dtype=np.float32).reshape(-1).view(np.int32))
+            host = torch.from_numpy(np.concatenate(parts))
+            if scales is not None:
+                host = host.pin_memory()                 # a copy from pageable memory waits for the stream: predict reads
+                #                                          the device next anyway, detect_submit must not wait
+            buf = host.to(dev, non_blocking=True)
+            buf._yolat_host = host                       # alive until the copy has run: as long as its target
+            offs, o = {}, 0
+            for k in order:
+                offs[k] = o
+                o += ft[k].size
+            offs["scale"] = o
+            ent = (key, ft, buf, offs, skey)
+            try:
+                data.__dict__["_yolat_tree"] = ent
+            except AttributeError:
+                pass
+        _, ft, buf, offs, have = ent
+        t = PredictTree()
+        t.R, t.Ctot, t.B = ft["R"], ft["Ctot"], ft["B"]
+        base = buf.data_ptr()
+        for k in ("root_row", "root_range", "child_ptr", "child_row", "child_range", "image_root_ptr"):
+            setattr(t, k, base + 4 * offs[k])
+        t._keep = buf
+        return t, ft, (base + 4 * offs["scale"]) if have is not None else None
+
+    def detect_submit(self, data, slices, conf_thres=0.25, iou_thres=0.45, agnostic=False, classifier=None):
+        """The detection of one batch — ``predict``, the scores and the class-aware NMS of ``evaluation.detect_batch`` —
+        ENQUEUED on the current stream: the forward under the model's eval precision, then one ``yolat_detect`` call
+        (csrc/detect.hip) that sizes everything by R + Ctot, the bound the host knows from the tree, and reads the actual
+        row count on the device.  No host read, no synchronisation: the returned ``DetectHandle`` says when the batch is
+        done (``ready``) and hands out the detections (``result``, the one read).  Eval mode, a batch with its raw edge
+        list (``collate`` / ``collate_to_device(csr=False)`` / ``DeviceLoader(csr=False)``); boxes in pixels of
+        ``data.width`` / ``data.height`` when the batch has them.  ``classifier``: as ``detect_batch``'s, default the
+        model's own."""
+        import ctypes
+        import numpy as np
+        from ._lib import lib, check
+        if self.training:
+            raise RuntimeError("detect_submit runs the eval forward: call model.eval() first")
+        d = data.__dict__ if hasattr(data, "__dict__") else {}
+        if d.get("_yolat_graph") is not None and not all(k in data.keys for k in ("edge", "e_attr", "bbox_idx")):
+            raise ValueError(_PREPARED_BATCH)
+        with torch.no_grad():
+            logits, bbox = self.forward(data, slices)
+        opnd = self._predict_operands(data, logits, bbox)
+        if opnd is None:
+            raise ValueError("detect_submit expects the edge list as [E, 2]")
+        ep, se, sc, bp, N, E, P, dev = opnd
+        B = len(slices["roots"]) - 1
+        scales = np.ones((B, 4), dtype=np.float32)
+        if hasattr(data, "width") and hasattr(data, "height"):
+            for i in range(B):
+                scales[i] = (float(data.width[i]), float(data.height[i])) * 2
+        t, ft, scale_ptr = self._predict_tree(data, slices, dev, scales)
+        R_cap, K = ft["R"] + ft["Ctot"], int(logits.shape[1])
+        need = int(lib.yolat_detect_workspace_bytes(N, P, ft["R"], ft["Ctot"], K, B))
+        if need == 0:
+            raise ValueError("detect_submit: a batch of %d images, %d tree nodes and %d classes is outside what the batched "
+                             "NMS supports (nc <= 4096, B <= 65536, rows * nc <= 2^27)" % (B, R_cap, K))
+        if logits.dtype != torch.float32 or logits.stride(1) != 1:
+            logits = logits.float().contiguous()
+        bb = bbox if (bbox.dtype == torch.float32 and bbox.is_contiguous()) else bbox.float().contiguous()
+        # one allocation for what result() looks at and what it returns: det [B, 300, 6] | det_count [B] | sel
+        n_det = B * ops.MAX_DET * 6
+        out = torch.empty(n_det + B + 4 + B + 1 + R_cap, dtype=torch.int32, device=dev)
+        det, det_count, sel = out[:n_det].view(torch.float32).view(B, ops.MAX_DET, 6), out[n_det:n_det + B], out[n_det + B:]
+        pred = torch.empty((R_cap, 4 + K), dtype=torch.float32, device=dev)
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        softmax = (self.classifier if classifier is None else classifier) == "softmax"
+        stream = ops._stream()
+        check(lib.yolat_detect(logits.data_ptr(), logits.stride(0), P, K, bb.data_ptr(), ep if E > 0 else None, se, sc, bp, N,
+                               E, ctypes.byref(t), scale_ptr, int(softmax), float(conf_thres), float(iou_thres),
+                               int(bool(agnostic)), sel.data_ptr(), pred.data_ptr(), det.data_ptr(), det_count.data_ptr(),
+                               ws.data_ptr(), ws.numel(), stream), "yolat_detect")
+        plan = self.__dict__.get("_yolat_plan")
+        status = getattr(plan, "_status", None)
+        if status is not None:
+            # the forward's input-validity word rides along in sel[2]; cleared behind the copy (stream order), so that the
+            # next handle carries the flags of ITS forward only
+            sel[2:3].copy_(status)
+            status.zero_()
+        done = torch.cuda.Event()
+        done.record(ops.current_stream_object())
+        return DetectHandle(self, data, slices, out, det, det_count, sel, pred, ws, done,
+                            dict(conf_thres=conf_thres, iou_thres=iou_thres, agnostic=agnostic,
+                                 classifier=self.classifier if classifier is None else classifier))
+
     def _predict_one_submission(self, data, slices):
         """One forward over the whole batch, then yolat_predict_select / yolat_predict_gather (csrc/subgraph.hip): in eval
         mode the logits of a proposal depend only on its own nodes and edges, so the root pass and the child pass of the
@@ -263,49 +438,18 @@ class SparseCADGCN(nn.Module):
         cases of the reference) — the caller then runs the two-pass extraction."""
         import ctypes
         import numpy as np
-        from ._lib import lib, check, PredictTree
-        from .data import flatten_tree
+        from ._lib import lib, check
         d = data.__dict__ if hasattr(data, "__dict__") else {}
         if d.get("_yolat_graph") is not None:
             return None                                  # prepared-CSR batch: no raw edge list to validate the tree against
         with torch.no_grad():
             logits, bbox = self.forward(data, slices)
-        raw = d.get("_yolat_raw")
-        if raw is not None:
-            _, _, ep, se, sc, _, bp, N, E, P, dev = raw
-        else:
-            st = self._stage_tensors(data)
-            edge, bidx = st["edge"], st["bbox_idx"]
-            if edge.dim() != 2 or edge.shape[1] != 2:
-                return None
-            ep, bp = ops._i(edge, torch.int64, "edge"), ops._i(bidx, torch.int64, "bbox_idx")
-            se, sc = edge.stride(0), edge.stride(1)
-            N, E, P, dev = st["x"].shape[0], edge.shape[0], bbox.shape[0], logits.device
-        # the flattened tree, on the device once per batch object (keyed by the identity of the tree and the image offsets)
-        key = (id(data.roots), len(data.roots), tuple(int(v) for v in slices["roots"]), tuple(int(v) for v in slices["pos"]),
-               tuple(int(v) for v in slices["edge"]), tuple(int(v) for v in slices["bbox"]))
-        ent = d.get("_yolat_tree")
-        if ent is None or ent[0] != key:
-            ft = flatten_tree(data, slices)
-            order = ("root_row", "root_range", "child_ptr", "child_row", "child_range", "image_root_ptr")
-            flat = np.concatenate([ft[k].reshape(-1) for k in order])
-            buf = torch.from_numpy(flat).to(dev, non_blocking=True)
-            offs, o = {}, 0
-            for k in order:
-                offs[k] = o
-                o += ft[k].size
-            ent = (key, ft, buf, offs)
-            try:
-                data.__dict__["_yolat_tree"] = ent
-            except AttributeError:
-                pass
-        _, ft, buf, offs = ent
+        opnd = self._predict_operands(data, logits, bbox)
+        if opnd is None:
+            return None
+        ep, se, sc, bp, N, E, P, dev = opnd
+        t, ft, _ = self._predict_tree(data, slices, dev)
         R, Ctot, B = ft["R"], ft["Ctot"], ft["B"]
-        t = PredictTree()
-        t.R, t.Ctot, t.B = R, Ctot, B
-        base = buf.data_ptr()
-        for k in ("root_row", "root_range", "child_ptr", "child_row", "child_range", "image_root_ptr"):
-            setattr(t, k, base + 4 * offs[k])
         K = logits.shape[1]
         out = torch.empty(4 + B + 1 + R + Ctot, dtype=torch.int32, device=dev)
         ws = torch.empty(int(lib.yolat_predict_select_workspace_bytes(N, P, R)) + 16, dtype=torch.uint8, device=dev)
@@ -342,8 +486,7 @@ class SparseCADGCN(nn.Module):
         gathers are device kernels (`ops.extract_subgraph`); both forwards run through the HIP path."""
         from .data import select_tree_ranges, interleave_root_child
         if getattr(data, "_yolat_graph", None) is not None and not all(k in data.keys for k in ("edge", "e_attr", "bbox_idx")):
-            raise ValueError("predict() cuts sub-graphs out of the raw edge list: batches from collate_to_device(csr=True) "
-                             "carry the prepared CSR only and support forward() — collate with csr=False for predict()")
+            raise ValueError(_PREPARED_BATCH)
         # the whole batch goes to the device once; both sub-batches are cut out of it by integer kernels
         # (csrc/subgraph.hip) — the host only walks the proposal tree (O(#tree nodes))
         dev = {k: getattr(data, k).cuda(non_blocking=True) for k in ("x", "pos", "edge", "e_attr", "bbox_idx", "bbox",

@@ -5,6 +5,7 @@
 //        (box * scale[image], 1 - p[K-1], p[0 .. K-2]),  p = softmax(logits) or the logits themselves;
 //   2. yolat_nms_batched    the class-aware non_max_suppression of train.py:34-121 (classes=None, labels=()) per image;
 //   3. yolat_detect_match   the true-positive walk of utils/det_util.py:154-202 for every (image, IoU threshold) pair.
+// and yolat_detect (2b, 2c): predict's selection, 1. and 2. of one batch enqueued in one call, no size read by the host.
 //
 // Batched NMS.  A (row, class) pair is a SLOT, slot = row * nc + class: row-major order = the candidate order of the
 // reference.  k_det_keys gives every slot the 64-bit key (image << 32 | ~orderable(score)); a slot that is no candidate
@@ -183,6 +184,53 @@ static __global__ void __launch_bounds__(DET_CHUNK) k_det_nms(const float* __res
   if (tid == 0) det_count[img] = nk;
 }
 
+// ------------------------------------------------------------------------------------------------
+// 2b. the pred rows of yolat_detect: k_predict_gather (subgraph.hip) + k_det_scores in one launch with every size read on
+// the device.  One thread per row r < R_cap = R + Ctot, the bound the host knows from the tree it uploaded; the record of
+// yolat_predict_select says how many of them exist: sel[0] = total, sel + 4 = the per-image offsets [B + 1], behind them
+// the proposal row of every output row.  Row r < total: the proposal's box enlarged by 5 % about its centre with the fp32
+// steps of k_predict_gather (w / 2 is exact, nothing else is a multiply feeding an add), times the image's scale, and the
+// scores of k_det_scores — bit for bit the row the two calls produce.  A SPARE row r >= total belongs to no image
+// (det_image_of gives B behind image_off[B] = total): rows[r] is uninitialised and is not read, the row is written as
+// zeros so that k_det_keys reads defined memory, and it can never be a candidate.
+// (A variant in which this kernel also wrote the sort keys — one launch fewer — was measured and is no faster: DESIGN.md.)
+// ------------------------------------------------------------------------------------------------
+static __global__ void __launch_bounds__(256) k_detect_rows(const float* __restrict__ logits, long ld, int K, int P,
+                                                             const float* __restrict__ bbox, const int* __restrict__ sel,
+                                                             int B, int R_cap, const float* __restrict__ scale, int softmax,
+                                                             float* __restrict__ pred) {
+  const int r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= R_cap) return;
+  const int total = det_clamp(sel[0], R_cap);
+  const int* image_off = sel + 4;
+  const int* rows = sel + 4 + B + 1;
+  float* o = pred + (long)r * (4 + K);
+  if (r < total) {
+    const int row = det_clamp(rows[r], P - 1);
+    const float x1 = bbox[4l * row], y1 = bbox[4l * row + 1], x2 = bbox[4l * row + 2], y2 = bbox[4l * row + 3];
+    const float w = (x2 - x1) * 1.05f, h = (y2 - y1) * 1.05f, cx = (x2 + x1) / 2.f, cy = (y2 + y1) / 2.f;
+    const float e[4] = {cx - w / 2.f, cy - h / 2.f, cx + w / 2.f, cy + h / 2.f};
+    const int img = det_image_of(image_off, B, R_cap, r);
+    const float* sc = scale + 4 * (img < B ? img : 0);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) o[j] = img < B ? e[j] * sc[j] : 0.f;
+    const float* x = logits + (long)row * ld;
+    if (softmax) {
+      float m = -INFINITY;
+      for (int k = 0; k < K; ++k) m = fmaxf(m, x[k]);
+      float s = 0.f;
+      for (int k = 0; k < K; ++k) s += expf(x[k] - m);
+      for (int k = 0; k < K - 1; ++k) o[5 + k] = expf(x[k] - m) / s;
+      o[4] = 1.f - expf(x[K - 1] - m) / s;
+    } else {
+      for (int k = 0; k < K - 1; ++k) o[5 + k] = x[k];
+      o[4] = 1.f - x[K - 1];
+    }
+  } else {
+    for (int j = 0; j < 4 + K; ++j) o[j] = 0.f;
+  }
+}
+
 namespace {
 struct DetPlan { size_t off_keys, off_slots, off_skeys, off_sslots, off_tmp, tmp_bytes, total; int end_bit; };
 bool det_shape_ok(int64_t R, int64_t nc, int64_t B) {
@@ -257,6 +305,79 @@ extern "C" int yolat_nms_batched(const float* pred, int64_t R, int64_t nc, const
                      iou_thres, agnostic, det_out, det_count);
   YL_LAUNCH_CHECK();
   return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// 2c. yolat_detect: logits -> det [B, 300, 6] of one batch, enqueued in one go (SparseCADGCN.detect_submit).  The
+// launches of yolat_predict_select, k_detect_rows over R_cap = R + Ctot rows, then keys / radix sort / k_det_nms over the
+// same R_cap rows with image_ptr = sel + 4: a spare row is a non-candidate of image B, the stable sort puts those slots
+// behind every image's own range, and k_det_nms reads an image's range only.  Nothing is read back.
+// ------------------------------------------------------------------------------------------------
+namespace {
+struct DetectPlan { size_t sel_bytes, off_nms, nms_bytes, total; };
+bool detect_shape_ok(int64_t N, int64_t P, int64_t R, int64_t Ctot, int64_t K, int64_t B) {
+  if (N <= 0 || P <= 0 || R < 0 || Ctot < 0 || K < 2) return false;
+  if (N >= (1LL << 30) || P >= (1LL << 30) || R + Ctot >= (1LL << 30)) return false;      // yolat_predict_select's limits
+  return det_shape_ok(R + Ctot, K - 1, B);
+}
+DetectPlan detect_plan(int64_t N, int64_t P, int64_t R, int64_t Ctot, int64_t K, int64_t B) {
+  DetectPlan p;
+  p.sel_bytes = yolat_predict_select_workspace_bytes(N, P, R);
+  p.off_nms = (p.sel_bytes + 255) & ~(size_t)255;
+  p.nms_bytes = det_plan(R + Ctot, K - 1, B).total;
+  p.total = p.off_nms + p.nms_bytes;
+  return p;
+}
+}  // namespace
+
+extern "C" int yolat_detect_rows(const float* logits, int64_t ld_logits, int64_t P, int64_t K, const float* bbox,
+                                 const int32_t* sel, int64_t B, int64_t R_cap, const float* scale, int softmax,
+                                 float* pred_out, yolat_stream_t stream) {
+  if (R_cap < 0 || P <= 0 || K < 2 || ld_logits < K || B < 1) return YOLAT_E_INVALID;
+  if (!sel || !scale) return YOLAT_E_INVALID;
+  if (R_cap == 0) return 0;
+  if (!logits || !bbox || !pred_out) return YOLAT_E_INVALID;
+  if (P >= (1LL << 30) || !det_shape_ok(R_cap, K - 1, B)) return YOLAT_E_UNSUPPORTED;
+  hipLaunchKernelGGL(k_detect_rows, dim3(yl_cdiv(R_cap, 256)), dim3(256), 0, (hipStream_t)stream, logits, (long)ld_logits,
+                     (int)K, (int)P, bbox, sel, (int)B, (int)R_cap, scale, softmax, pred_out);
+  YL_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" size_t yolat_detect_workspace_bytes(int64_t N, int64_t P, int64_t R, int64_t Ctot, int64_t K, int64_t B) {
+  if (!detect_shape_ok(N, P, R, Ctot, K, B)) return 0;
+  return detect_plan(N, P, R, Ctot, K, B).total;
+}
+
+extern "C" int yolat_detect(const float* logits, int64_t ld_logits, int64_t P, int64_t K, const float* bbox,
+                            const int64_t* edge, int64_t stride_e, int64_t stride_c, const int64_t* bbox_idx, int64_t N,
+                            int64_t E, const yolat_predict_tree* tree, const float* scale, int softmax, float conf_thres,
+                            float iou_thres, int agnostic, int32_t* sel, float* pred, float* det_out, int32_t* det_count,
+                            void* workspace, size_t workspace_bytes, yolat_stream_t stream) {
+  // everything either half can refuse is decided here, in front of the first launch
+  if (!logits || !bbox || !bbox_idx || !tree || !scale || !sel || !det_out || !det_count || !workspace || P <= 0 || K < 2 ||
+      N <= 0 || E < 0 || (E > 0 && !edge) || ld_logits < K)
+    return YOLAT_E_INVALID;
+  const yolat_predict_tree& t = *tree;
+  if (t.R < 0 || t.Ctot < 0 || t.B < 1 || !t.image_root_ptr || !t.child_ptr ||
+      (t.R > 0 && (!t.root_row || !t.root_range)) || (t.Ctot > 0 && (!t.child_row || !t.child_range)))
+    return YOLAT_E_INVALID;
+  const int64_t R_cap = t.R + t.Ctot;
+  if (R_cap > 0 && !pred) return YOLAT_E_INVALID;
+  if (E >= (1LL << 30) || !detect_shape_ok(N, P, t.R, t.Ctot, K, t.B) || (((uintptr_t)workspace) & 255) != 0)
+    return YOLAT_E_UNSUPPORTED;
+  const DetectPlan p = detect_plan(N, P, t.R, t.Ctot, K, t.B);
+  if (workspace_bytes < p.total) return YOLAT_E_INVALID;
+  char* base = reinterpret_cast<char*>(workspace);
+  YL_TRY(yolat_predict_select(logits, ld_logits, P, K, edge, stride_e, stride_c, bbox_idx, N, E, tree, sel, base,
+                              p.sel_bytes, stream));
+  if (R_cap > 0) {
+    hipLaunchKernelGGL(k_detect_rows, dim3(yl_cdiv(R_cap, 256)), dim3(256), 0, (hipStream_t)stream, logits, (long)ld_logits,
+                       (int)K, (int)P, bbox, sel, (int)t.B, (int)R_cap, scale, softmax, pred);
+    YL_LAUNCH_CHECK();
+  }
+  return yolat_nms_batched(pred, R_cap, K - 1, sel + 4, t.B, conf_thres, iou_thres, agnostic, det_out, det_count,
+                           base + p.off_nms, p.nms_bytes, stream);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -100,6 +100,52 @@ def detect_batch(model, data, slices, conf_thres=0.25, iou_thres=0.45, classifie
     return non_max_suppression_batched(pred, ptr, conf_thres=conf_thres, iou_thres=iou_thres, agnostic=agnostic)
 
 
+def detect_batch_async(model, data, slices, conf_thres=0.25, iou_thres=0.45, classifier="softmax", agnostic=False,
+                       fixup=True):
+    """``detect_batch`` as a submission: the same ``fixup`` / ``edge_control`` handling, then
+    ``model.detect_submit`` — forward, selection, scores and NMS enqueued on the current stream, nothing read back.
+    Returns the ``DetectHandle``; ``handle.result()`` is the list ``detect_batch`` returns, bit for bit."""
+    if fixup:
+        fixup_offsets(data, slices)
+    if not hasattr(data, "edge_control"):
+        data.edge_control = None
+    return model.detect_submit(data, slices, conf_thres=conf_thres, iou_thres=iou_thres, agnostic=agnostic,
+                               classifier=classifier)
+
+
+def detect_stream(model, batches, depth=4, **kw):
+    """Generator over the detections of ``batches`` — a ``DeviceLoader(..., csr=False)`` or any iterable of
+    ``(data, slices)`` device batches (``collate_to_device(items)``) — with up to ``depth`` batches in flight on the
+    current stream: batch i + depth is submitted before the host looks at batch i, so the device never waits for a host
+    read.  Yields, in order, what ``detect_batch`` returns for each batch.  ``kw``: the keywords of
+    ``detect_batch_async``; ``fixup`` defaults to False here (device batches carry their offsets already).
+    A DeviceLoader hands out ring slots.  A submission enqueues everything that reads its batch before the next draw
+    (the ring rule of the loader's docstring), and a handle's fall-back collates the batch again from its host items, so
+    no handle reads a slot that has been rewritten; the batches the handles in flight hold are valid for ``slots - 1``
+    further draws, one of which is the draw in progress: ``depth <= slots - 2`` is required (ValueError otherwise, also
+    when the loader does not say how many slots it has)."""
+    from collections import deque
+    from .data import DeviceLoader
+    depth = int(depth)
+    if depth < 1:
+        raise ValueError("detect_stream needs depth >= 1")
+    if isinstance(batches, DeviceLoader):
+        slots = getattr(batches, "_slots", None)
+        if not isinstance(slots, int):
+            raise ValueError("detect_stream cannot tell how many slots the loader has")
+        if depth > slots - 2:
+            raise ValueError("detect_stream(depth=%d) over a DeviceLoader needs slots >= depth + 2, the loader has %d"
+                             % (depth, slots))
+    kw.setdefault("fixup", False)
+    flying = deque()
+    for data, slices in batches:
+        flying.append(detect_batch_async(model, data, slices, **kw))
+        if len(flying) >= depth:
+            yield flying.popleft().result()
+    while flying:
+        yield flying.popleft().result()
+
+
 def test(model, test_loader, criterion, opt):
     """train.py:324-508.  Returns the mean AP at the last IoU threshold (None when nothing was detected), like the
     reference; the per-threshold mAPs, MAP@ALL, top-1 accuracy and mean losses are left in ``opt.test_report``."""

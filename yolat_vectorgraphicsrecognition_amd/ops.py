@@ -1349,6 +1349,44 @@ def nms_batched(pred, image_ptr, conf_thres=0.25, iou_thres=0.45, agnostic=False
     return det, det_count
 
 
+def detect_workspace_bytes(N, P, R, Ctot, K, B):
+    """Workspace of yolat_detect in bytes (0: shape not supported)."""
+    return int(lib.yolat_detect_workspace_bytes(int(N), int(P), int(R), int(Ctot), int(K), int(B)))
+
+
+def detect_rows(logits, bbox, sel, B, R_cap, scale, softmax=True, out=None):
+    """yolat_detect_rows (csrc/detect.hip): the pred rows of the asynchronous detection from the record yolat_predict_select
+    wrote.  logits [P, K], bbox [P, 4], sel [4 + B + 1 + R_cap] int32 (sel[0] = total rows, sel[4:] the per-image offsets,
+    then the proposal row of every output row), scale [B, 4] -> pred [R_cap, 4 + K]: row r < total equals the row
+    ``detect_scores`` gives on ``predict``'s logits and enlarged boxes, bit for bit; the spare rows behind are zero.  The
+    row count is read on the device; nothing is read back."""
+    lp = _f(logits, "logits")
+    if logits.dim() != 2 or logits.shape[1] < 2:
+        raise ValueError("detect_rows expects logits [P, K] with K >= 2")
+    P, K = int(logits.shape[0]), int(logits.shape[1])
+    B, R_cap = int(B), int(R_cap)
+    bp, sp = _dense2(bbox, "bbox", 4), _dense2(scale, "scale", 4)
+    ip = _i(sel, torch.int32, "sel")
+    if bbox.shape[0] != P or B < 1 or scale.shape[0] != B or sel.dim() != 1 or sel.numel() < 4 + B + 1 + R_cap:
+        raise ValueError("detect_rows expects bbox [P, 4], scale [B, 4] and sel [4 + B + 1 + R_cap]")
+    if out is None:
+        out = torch.empty((R_cap, 4 + K), dtype=torch.float32, device=logits.device)
+    check(lib.yolat_detect_rows(lp, _ld(logits), P, K, bp, ip, B, R_cap, sp, int(bool(softmax)), _dense2(out, "out", 4 + K),
+                                _stream()), "yolat_detect_rows")
+    return out
+
+
+D2H_READS = 0
+
+
+def d2h(t):
+    """The device -> host read of the asynchronous detection path (DetectHandle.result): one synchronising copy, counted
+    in ``D2H_READS`` so that a test can tell how often the path looks at the device."""
+    global D2H_READS
+    D2H_READS += 1
+    return t.cpu()
+
+
 def detect_match(det, det_count, gt_boxes, gt_labels, gt_ptr, thresholds, out=None):
     """yolat_detect_match (csrc/detect.hip): true-positive flags of get_batch_statistics for every (image, threshold)
     pair.  det [B, 300, 6] / det_count [B] as returned by nms_batched, gt_boxes [G, 4], gt_labels [G] fp32, gt_ptr [B + 1]
