@@ -682,6 +682,17 @@ typedef struct {
    * (sc1 (rows) * Wc1), tc1_gx = sc1*bc1 + tc1.  Used when P >= YOLAT_CLS1_X6_MIN_ROWS.                          */
   const uint16_t *Wc1_gx;
   const float *tc1_gx;
+  /* nullable (all six or none; read only beside Wf_hi.. / Wfs_hi.., norm == 0): both fusion blocks prepared for the
+   * f16x3-emulated kernel (yolat_fusion_pair_eval_f16x3) — Wf_f16 = (hi, lo) and Wf_exp of yolat_split_f16x2 of
+   * sf (rows) * Wf, the shift is tf_fold.  A forward takes that launch unless YOLAT_STRICT_FP32=1 or YOLAT_FUSION_F16X3=0
+   * (then: the bf16x6 launch, exactly the forward of a descriptor without these fields).
+   * Placed HERE, behind the last field a ReLU / BatchNorm descriptor sets: every field above keeps its offset; the
+   * activation and row-norm fields below stay the struct's tail (tests/test_norm_host.py holds their names there) and lie 48
+   * bytes further on than before — build descriptors with this header, by field name.                                      */
+  const uint16_t *Wf_f16[2];
+  const int32_t *Wf_exp;
+  const uint16_t *Wfs_f16[2];
+  const int32_t *Wfs_exp;
   /* act != 0: the slope of each of the four sites (device pointers to one float, read by every launch) in the order
    * fusion_block, fusion_block_super, prediction_cls.0, prediction_cls.1.  Not read when act == 0.                  */
   const float *act_slope[4];
@@ -1261,6 +1272,29 @@ int yolat_fusion_pair_eval_x6(const float* A, int64_t lda, int64_t N, int64_t D,
                               int64_t ldpool, const float* S, int64_t lds, int64_t P, const uint16_t* Wsh,
                               const uint16_t* Wsm, const uint16_t* Wsl, const float* tsfold, float* Ys, int64_t ldys,
                               yolat_stream_t stream);
+/* The same pair launch with the GEMM emulated by THREE half-precision products (fusion_x6.hip k_fusion_rows_f16x3,
+ * csrc/f16x3.hpp): every row of either operand is scaled by a power of two so that its largest magnitude lies in
+ * [2^14, 2^15), split into two fp16 terms by round to nearest (residual <= 2^-23 relative for elements within 2^16 of
+ * their row's maximum; further down the error is relative to the ROW's maximum), three v_mfma_f32_32x32x16_f16 products
+ * per 16 k, fp32 accumulation, exact un-scaling — half the matrix work of the bf16x6 form, ~1e-7 of the output's scale.
+ *   yolat_split_f16x2             hi, lo [rows, cols] fp16 and exps [rows] int32 with
+ *                                 hi + lo ~= fl(row_scale[r] * W[r, c]) * 2^exps[r]  (row_scale nullable); exps[r] =
+ *                                 14 - floor(log2(max_c |.|)), at most 127, 0 for an all-zero row
+ *   yolat_fusion_pair_eval_f16x3  yolat_fusion_pair_eval_x6's contract and argument order with (hi, lo, exps) in place of
+ *                                 (hi, mid, lo);  _act: yolat_fusion_pair_eval_x6_act's                              */
+int yolat_split_f16x2(const float* W, int64_t ldw, int64_t rows, int64_t cols, const float* row_scale, uint16_t* hi,
+                      uint16_t* lo, int32_t* exps, yolat_stream_t stream);
+int yolat_fusion_pair_eval_f16x3(const float* A, int64_t lda, int64_t N, int64_t D, const uint16_t* Wh, const uint16_t* Wl,
+                                 const int32_t* Wexp, const float* tfold, int64_t F, const int32_t* node_seg, float* pool,
+                                 int64_t ldpool, const float* S, int64_t lds, int64_t P, const uint16_t* Wsh,
+                                 const uint16_t* Wsl, const int32_t* Wsexp, const float* tsfold, float* Ys, int64_t ldys,
+                                 yolat_stream_t stream);
+int yolat_fusion_pair_eval_f16x3_act(const float* A, int64_t lda, int64_t N, int64_t D, const uint16_t* Wh,
+                                     const uint16_t* Wl, const int32_t* Wexp, const float* tfold, int64_t F,
+                                     const float* slope_f, const int32_t* node_seg, const int32_t* seg_ptr, float* pool,
+                                     int64_t ldpool, const float* S, int64_t lds, int64_t P, const uint16_t* Wsh,
+                                     const uint16_t* Wsl, const int32_t* Wsexp, const float* tsfold, const float* slope_s,
+                                     float* Ys, int64_t ldys, yolat_stream_t stream);
 
 /* nn.Dropout2d(p) of MLP in training mode (gcn_lib/sparse/torch_nn.py:67-68; only prediction_cls.1 can carry it,
  * architecture3cc_rpn_gp_iter2.py:92) on a [M,C] activation, with the producer's lazy BatchNorm + ReLU applied on the

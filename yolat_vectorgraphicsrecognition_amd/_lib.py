@@ -36,7 +36,8 @@ class ModelEval(ctypes.Structure):
                 [(n, c_p) for n in ("Wf", "bf", "sf", "tf", "Wf_hi", "Wf_mid", "Wf_lo", "tf_fold", "Wfs_hi", "Wfs_mid",
                                     "Wfs_lo", "tfs_fold", "Wfs", "bfs", "sfs", "tfs", "Wc1", "bc1", "sc1", "tc1", "Wc2",
                                     "bc2", "sc2", "tc2", "Wc3", "bc3")] +
-                [("Wc_x6", c_p * 3), ("tc_fold", c_p * 3), ("Wc1_gx", c_p), ("tc1_gx", c_p), ("act_slope", c_p * 4),
+                [("Wc_x6", c_p * 3), ("tc_fold", c_p * 3), ("Wc1_gx", c_p), ("tc1_gx", c_p),
+                 ("Wf_f16", c_p * 2), ("Wf_exp", c_p), ("Wfs_f16", c_p * 2), ("Wfs_exp", c_p), ("act_slope", c_p * 4),
                  ("norm", ctypes.c_int32), ("rn_eps", ctypes.c_float), ("rn_gamma", c_p * 4), ("rn_beta", c_p * 4),
                  ("rn_route", ctypes.c_int32)])
 
@@ -298,6 +299,11 @@ SIGNATURES = {
                                       c_p, c_i64, c_p, c_i64, c_p]),
     "yolat_fusion_pair_eval_x6": (c_int, [c_p, c_i64, c_i64, c_i64, c_p, c_p, c_p, c_p, c_i64, c_p, c_p, c_i64, c_p,
                                           c_i64, c_i64, c_p, c_p, c_p, c_p, c_p, c_i64, c_p]),
+    "yolat_split_f16x2": (c_int, [c_p, c_i64, c_i64, c_i64, c_p, c_p, c_p, c_p, c_p]),
+    "yolat_fusion_pair_eval_f16x3": (c_int, [c_p, c_i64, c_i64, c_i64, c_p, c_p, c_p, c_p, c_i64, c_p, c_p, c_i64, c_p,
+                                             c_i64, c_i64, c_p, c_p, c_p, c_p, c_p, c_i64, c_p]),
+    "yolat_fusion_pair_eval_f16x3_act": (c_int, [c_p, c_i64, c_i64, c_i64, c_p, c_p, c_p, c_p, c_i64, c_p, c_p, c_p, c_p,
+                                                 c_i64, c_p, c_i64, c_i64, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_p]),
     "yolat_inv_degree": (c_int, [c_p, c_i64, c_p, c_p]),
     "yolat_bn_csr_work_elems": (c_sz, [c_i64, c_i64]),
     "yolat_bn_csr_bwd_stats": (c_int, [ctypes.POINTER(BnCsrGrad), c_i64, c_i64, c_p, c_p, c_int, c_p, c_p, c_p]),

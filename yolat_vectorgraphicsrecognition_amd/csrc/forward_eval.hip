@@ -375,6 +375,13 @@ static int forward_eval_impl(const yolat_model_eval* m, const float* x, int64_t 
   static const bool riders_on = []() { const char* v = getenv("YOLAT_POOL_RIDERS"); return !(v && v[0] == '0'); }();
   const bool fusion_x6 = m->Wf_hi && m->Wf_mid && m->Wf_lo && m->tf_fold && m->Wfs_hi && m->Wfs_mid && m->Wfs_lo &&
                          m->tfs_fold && (D == 64 || D == 128) && F % 64 == 0 && (long)P * ZW < (1LL << 32);
+  // the BatchNorm fusion launch (ReLU or leaky) on three half-precision products instead of six bfloat16 ones (fusion_x6.hip
+  // k_fusion_rows_f16x3): same grid, same rider, same epilogues, half the MFMAs.  YOLAT_FUSION_F16X3=0: the bf16x6 launch —
+  // the forward of a descriptor without the f16 fields, launch for launch.  Read per forward (a getenv, no HIP call), so one
+  // process can run both forms; both launch regimes take the same kernel.
+  const char* f16_env = getenv("YOLAT_FUSION_F16X3");
+  const bool fusion_f16 = fusion_x6 && !rn && m->Wf_f16[0] && m->Wf_f16[1] && m->Wf_exp && m->Wfs_f16[0] && m->Wfs_f16[1] &&
+                          m->Wfs_exp && !yl_strict_fp32() && !(f16_env && f16_env[0] == '0');
   const bool small_pool = riders_on && (long)P * (F + 2 * D) <= (1L << 20);
   PoolRider ride_a{}, ride_b{};
   ride_a.feats = ride_b.feats = p.feats; ride_a.fsup = ride_b.fsup = p.fsup; ride_a.ld = ride_b.ld = D;
@@ -541,9 +548,14 @@ static int forward_eval_impl(const yolat_model_eval* m, const float* x, int64_t 
     // -inf / 0 per proposal — one launch more than the ReLU pair
     YL_STAGE("pool_init_signed[P x F]", 0, 4.0 * P * F, yolat_pool_init_signed(p.seg_ptr, P, F, p.Z, ZW, stream));
     YL_STAGE(nm, 2.0 * (N + P) * D * F, 4.0 * (N * D + 2.0 * D * F + 2.0 * P * F + N + P * D),
-             yl_fusion_pair_eval_x6_impl(p.feats, D, N, D, m->Wf_hi, m->Wf_mid, m->Wf_lo, m->tf_fold, F, p.node_seg, p.Z, ZW,
-                                         sup, ZW, P, m->Wfs_hi, m->Wfs_mid, m->Wfs_lo, m->tfs_fold, p.Z + F + D, ZW,
-                                         ride_max ? &ride_b : nullptr, stream, m->act_slope[0], m->act_slope[1]));
+             fusion_f16
+                 ? yl_fusion_pair_eval_f16x3_impl(p.feats, D, N, D, m->Wf_f16[0], m->Wf_f16[1], m->Wf_exp, m->tf_fold, F,
+                                                  p.node_seg, p.Z, ZW, sup, ZW, P, m->Wfs_f16[0], m->Wfs_f16[1], m->Wfs_exp,
+                                                  m->tfs_fold, p.Z + F + D, ZW, ride_max ? &ride_b : nullptr, stream,
+                                                  m->act_slope[0], m->act_slope[1])
+                 : yl_fusion_pair_eval_x6_impl(p.feats, D, N, D, m->Wf_hi, m->Wf_mid, m->Wf_lo, m->tf_fold, F, p.node_seg, p.Z,
+                                               ZW, sup, ZW, P, m->Wfs_hi, m->Wfs_mid, m->Wfs_lo, m->tfs_fold, p.Z + F + D, ZW,
+                                               ride_max ? &ride_b : nullptr, stream, m->act_slope[0], m->act_slope[1]));
   } else if (leaky) {
     // other widths: the BatchNorm output of the fusion block materialised per column range, activated and pooled by
     // yolat_segment_act_max (the activation is applied per element BEFORE the maximum either way)
@@ -553,6 +565,10 @@ static int forward_eval_impl(const yolat_model_eval* m, const float* x, int64_t 
                                         p.act_work, stream));
   } else
   YL_STAGE(nm, 2.0 * (N + P) * D * F, 4.0 * (N * D + 2.0 * D * F + 2.0 * P * F + N + P * D),
+           fusion_f16 ? yl_fusion_pair_eval_f16x3_impl(p.feats, D, N, D, m->Wf_f16[0], m->Wf_f16[1], m->Wf_exp, m->tf_fold, F,
+                                                       p.node_seg, p.Z, ZW, sup, ZW, P, m->Wfs_f16[0], m->Wfs_f16[1],
+                                                       m->Wfs_exp, m->tfs_fold, p.Z + F + D, ZW,
+                                                       ride_max ? &ride_b : nullptr, stream, nullptr, nullptr) :
            fusion_x6 ? yl_fusion_pair_eval_x6_impl(p.feats, D, N, D, m->Wf_hi, m->Wf_mid, m->Wf_lo, m->tf_fold, F,
                                                    p.node_seg, p.Z, ZW, sup, ZW, P, m->Wfs_hi, m->Wfs_mid, m->Wfs_lo,
                                                    m->tfs_fold, p.Z + F + D, ZW, ride_max ? &ride_b : nullptr, stream)

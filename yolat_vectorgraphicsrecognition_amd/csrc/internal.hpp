@@ -114,6 +114,14 @@ int yl_fusion_pair_eval_x6_impl(const float* A, int64_t lda, int64_t N, int64_t 
                                 const uint16_t* Wsm, const uint16_t* Wsl, const float* tsfold, float* Ys, int64_t ldys,
                                 const PoolRider* rider, yolat_stream_t stream, const float* slope_f = nullptr,
                                 const float* slope_s = nullptr);
+// the same launch with the GEMM emulated by three half-precision products (fusion_x6.hip k_fusion_rows_f16x3): the weights
+// as yolat_split_f16x2 gives them
+int yl_fusion_pair_eval_f16x3_impl(const float* A, int64_t lda, int64_t N, int64_t D, const uint16_t* Wh, const uint16_t* Wl,
+                                   const int32_t* Wexp, const float* tfold, int64_t F, const int32_t* node_seg, float* pool,
+                                   int64_t ldpool, const float* S, int64_t lds, int64_t P, const uint16_t* Wsh,
+                                   const uint16_t* Wsl, const int32_t* Wsexp, const float* tsfold, float* Ys, int64_t ldys,
+                                   const PoolRider* rider, yolat_stream_t stream, const float* slope_f = nullptr,
+                                   const float* slope_s = nullptr);
 // the fusion pair behind a row norm (rownorm.hip): does a batch of N nodes run the fused kernel (true) or the materialising
 // route?  The descriptor's rn_route, or N >= YOLAT_RN_FUSED_MIN_ROWS when that is YOLAT_RN_ROUTE_AUTO: a function of the
 // descriptor and N alone, so the workspace sizing and the forward always agree.

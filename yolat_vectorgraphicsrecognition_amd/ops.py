@@ -761,6 +761,17 @@ def split_bf16x3(w, row_scale=None):
     return parts
 
 
+def split_f16x2(w, row_scale=None):
+    """Scaled two-term half-precision split (hi [rows, cols], lo [rows, cols], scale exponent per row [rows] int32) of a
+    contiguous fp32 matrix, rows scaled first when row_scale is given (yolat_split_f16x2, csrc/f16x3.hpp)."""
+    rows, cols = w.shape
+    hi, lo = (torch.empty(rows, cols, dtype=torch.float16, device=w.device) for _ in range(2))
+    exps = torch.empty(rows, dtype=torch.int32, device=w.device)
+    check(lib.yolat_split_f16x2(_f(w), cols, rows, cols, _f(row_scale, "row_scale", True), hi.data_ptr(), lo.data_ptr(),
+                                exps.data_ptr(), _stream()), "yolat_split_f16x2")
+    return hi, lo, exps
+
+
 def fusion_pair_eval_x6_rn(A, lin_f, gb_f, node_seg, pool, S, lin_s, gb_s, Ys, eps):
     """yolat_fusion_pair_eval_x6_rn: pool[P,F] (zero-filled by the caller) = per-proposal max of relu(rownorm(lin_f(A)) g + b),
     Ys = the same of lin_s(S) stored; gb_* = (gamma, beta) or (None, None)."""

@@ -216,6 +216,14 @@ class EvalPlan(object):
             d.tf_fold = _shift(fb[0], ff, keep).data_ptr()
             d.Wfs_hi, d.Wfs_mid, d.Wfs_lo = _split3(fs[0].weight, ffs[0], False, keep)
             d.tfs_fold = _shift(fs[0], ffs, keep).data_ptr()
+            # ... and for its f16x3 form (csrc/f16x3.hpp): the same scaled rows as two half-precision planes and one scale
+            # exponent per row; the forward picks the launch (YOLAT_FUSION_F16X3)
+            for lin, fold, planes, exp_name in ((fb[0], ff, d.Wf_f16, "Wf_exp"), (fs[0], ffs, d.Wfs_f16, "Wfs_exp")):
+                _ptr(lin.weight)
+                hi, lo, exps = ops.split_f16x2(lin.weight, fold[0])
+                keep += [hi, lo, exps]
+                planes[0], planes[1] = hi.data_ptr(), lo.data_ptr()
+                setattr(d, exp_name, exps.data_ptr())
         m1, m2, m3 = m.prediction_cls[0], m.prediction_cls[1], m.prediction_cls[2]
         d.H1, d.H2 = m1[0].out_features, m2[0].out_features
         (d.Wc1, d.bc1, d.sc1, d.tc1), fc1 = _lin_bn(m1[0], m1[1], dev, keep)
