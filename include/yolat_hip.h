@@ -1134,6 +1134,44 @@ int yolat_detect(const float* logits, int64_t ld_logits, int64_t P, int64_t K, c
 int yolat_detect_rows(const float* logits, int64_t ld_logits, int64_t P, int64_t K, const float* bbox, const int32_t* sel,
                       int64_t B, int64_t R_cap, const float* scale, int softmax, float* pred_out, yolat_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * The evaluation of one batch in ONE call (csrc/evaluate.hip; SparseCADGCN.evaluate_submit): logits -> loss, top-1 and
+ * confusion counts, detections and true-positive flags; nothing read back, nothing sized by a number the device computes.
+ * On `stream`, in this order:
+ *   a. the launches of yolat_detect with the same arguments (agnostic = 0) and the same sel record, pred [R_cap, 4 + K],
+ *      det_out [B, 300, 6] and det_count [B]; R_cap = tree->R + tree->Ctot;
+ *   b. the rows stage: stats zeroed, one rows launch over R_cap rows, one final launch;
+ *   c. the launch of yolat_detect_match on det_out / det_count with the batch's targets -> tp_out [T, B, 300].
+ * The rows stage reads total = sel[0] and the row list behind sel + 4 + B + 1 on the device.  For r < total, with
+ * row = rows[r] clamped to [0, P) and label = labels[row] (labels: DEVICE int64 [P]):
+ *   loss     the mean over the `total` rows of the cross entropy of logits[row] (softmax != 0), or the mean over
+ *            total * K elements of the BCE of the probabilities logits[row] against the one-hot label (softmax == 0) —
+ *            bit for bit what yolat_softmax_ce / yolat_bce (with scratch, K <= 32) give on the rows yolat_predict_gather
+ *            gathers: the same row code, the same two fixed-order trees, row r at tree position r.  A label outside
+ *            [0, K) makes the loss NaN; nothing is read or written through it.  total == 0: NaN.
+ *   y_pred   [R_cap] int32: the first index of the row maximum, a NaN counting as the maximum (torch's max(1)[1]);
+ *   y_true   [R_cap] int32: the label (saturated to int32).  Entries r >= total of both are not written.
+ *   stats    [2 + K * K] int32 = n_true (rows with y_pred == label), n_total (= total), confusion[label, y_pred] counts
+ *            of the in-range labels, row-major.  Integer atomics: two runs are bit-identical.
+ * A spare row r >= total reads neither rows[r] nor a label and contributes +0.0f / no count.
+ * K in [2, 32] (the register-resident row of the loss kernels), G <= 262144, T in [1, 65535], and everything
+ * yolat_detect accepts; outside that yolat_evaluate_workspace_bytes returns 0 and the call YOLAT_E_UNSUPPORTED, decided
+ * in front of the first launch.  workspace: that many bytes, 256-byte aligned.
+ * yolat_eval_rows: the rows stage alone, on a record yolat_predict_select has written.  work: (R_cap + 255) / 256 + 1 floats.
+ * ------------------------------------------------------------------------------------------ */
+size_t yolat_evaluate_workspace_bytes(int64_t N, int64_t P, int64_t R, int64_t Ctot, int64_t K, int64_t B, int64_t G,
+                                      int64_t T);
+int yolat_evaluate(const float* logits, int64_t ld_logits, int64_t P, int64_t K, const float* bbox, const int64_t* edge,
+                   int64_t stride_e, int64_t stride_c, const int64_t* bbox_idx, int64_t N, int64_t E,
+                   const yolat_predict_tree* tree, const float* scale, int softmax, float conf_thres, float iou_thres,
+                   const int64_t* labels, const float* gt_boxes, const float* gt_labels, int64_t G, const int32_t* gt_ptr,
+                   const float* thresholds, int64_t T, int32_t* sel, float* pred, float* det_out, int32_t* det_count,
+                   int32_t* stats, float* loss, int32_t* y_pred, int32_t* y_true, uint8_t* tp_out, void* workspace,
+                   size_t workspace_bytes, yolat_stream_t stream);
+int yolat_eval_rows(const float* logits, int64_t ld_logits, int64_t P, int64_t K, const int64_t* labels, const int32_t* sel,
+                    int64_t B, int64_t R_cap, int softmax, int32_t* stats, float* loss, int32_t* y_pred, int32_t* y_true,
+                    float* work, yolat_stream_t stream);
+
 /* Stage profiler of yolat_forward_eval: when enabled, a hipEvent pair is recorded on `stream` around
  * every stage (each stage = the launch(es) of one kernel family); totals accumulate across calls until
  * reset.  yolat_profile_get must be called after the stream has been synchronised.  `flops` / `bytes`

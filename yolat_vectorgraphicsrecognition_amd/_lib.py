@@ -280,6 +280,11 @@ SIGNATURES = {
     "yolat_detect": (c_int, [c_p, c_i64, c_i64, c_i64, c_p, c_p, c_i64, c_i64, c_p, c_i64, c_i64,
                              ctypes.POINTER(PredictTree), c_p, c_int, c_f, c_f, c_int, c_p, c_p, c_p, c_p, c_p, c_sz, c_p]),
     "yolat_detect_rows": (c_int, [c_p, c_i64, c_i64, c_i64, c_p, c_p, c_i64, c_i64, c_p, c_int, c_p, c_p]),
+    "yolat_evaluate_workspace_bytes": (c_sz, [c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64]),
+    "yolat_evaluate": (c_int, [c_p, c_i64, c_i64, c_i64, c_p, c_p, c_i64, c_i64, c_p, c_i64, c_i64,
+                               ctypes.POINTER(PredictTree), c_p, c_int, c_f, c_f, c_p, c_p, c_p, c_i64, c_p, c_p, c_i64,
+                               c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_sz, c_p]),
+    "yolat_eval_rows": (c_int, [c_p, c_i64, c_i64, c_i64, c_p, c_p, c_i64, c_i64, c_int, c_p, c_p, c_p, c_p, c_p, c_p]),
     "yolat_f32_to_bf16": (c_int, [c_p, c_i64, c_p, c_p]),
     "yolat_edge_uv_lin1_fwd_h": (c_int, [c_p, c_i64, c_p, c_p, c_p, c_i64, c_p, c_p, c_i64, c_p, c_i64, c_p, c_p]),
     "yolat_linear_fwd_h": (c_int, [c_p, c_i64, c_i64, c_i64, c_p, c_p, c_int, c_p, c_i64, c_p, c_i64, c_p, c_i64, c_p,

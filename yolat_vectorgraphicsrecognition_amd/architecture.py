@@ -173,6 +173,84 @@ class DetectHandle(object):
         self.data = self.slices = self.pred = self.workspace = None
 
 
+class EvalHandle(object):
+    """One batch of ``SparseCADGCN.evaluate_submit`` in flight.  It owns the device record of its batch — ONE allocation
+    ``det_count | stats | loss | y_pred | y_true | det | tp | sel`` plus ``pred`` and the workspace, allocated on the
+    submitting stream and released with the handle — and keeps the batch for the fall-back.  The record is per handle, not
+    a global accumulator: a batch that takes the fall-back discards its device record.
+
+    ``ready()``   the event behind the batch's last launch has completed (a query, no wait)
+    ``result()``  the dict ``evaluation.evaluate_batch`` returns (``sample_metrics``, ``labels``, ``loss``, ``n_true``,
+                  ``n_total``, ``y_pred``, ``y_true``) plus ``confusion``, np.int64 [K, K] (rows: true class, columns:
+                  predicted); ONE device -> host read (ops.d2h, on the submitting stream) of the record up to sel[0:4].
+                  A forward that flagged its input raises what ``check_last_status`` raises; a tree that is not made of
+                  its proposals' ranges (sel[1]) goes through ``evaluate_batch(device_post=True, fixup=False)`` on a
+                  shallow copy of the retained batch — a DeviceLoader batch is collated again from its host items — and
+                  ``confusion`` is then counted on the host."""
+
+    def __init__(self, model, data, slices, out, lay, sel, pred, workspace, event, stream, labels, kw):
+        self.model, self.data, self.slices, self.kw = model, data, slices, kw
+        self._out, self._lay, self.sel, self.pred, self.workspace = out, lay, sel, pred, workspace
+        self.event, self._stream, self._labels = event, stream, labels
+        self._result = None
+
+    def ready(self):
+        return bool(self.event.query())
+
+    def result(self):
+        if self._result is not None:
+            return self._result
+        import numpy as np
+        from .postprocess import _unpack_statistics
+        lay = self._lay
+        B, K, T, R_cap = lay["B"], lay["K"], lay["T"], lay["R_cap"]
+        with torch.cuda.stream(self._stream):
+            host = ops.d2h(self._out[:lay["copy"]]).numpy()     # stream order: behind the true-positive walk
+            total, flag, status = int(host[lay["sel"]]), int(host[lay["sel"] + 1]), int(host[lay["sel"] + 2])
+            if status != 0:
+                ops.check_status_word(torch.tensor([status], dtype=torch.int32))      # raises for every flag a forward sets
+            if flag != 0:
+                res = self._fallback()
+            else:
+                stats = host[lay["stats"]:lay["stats"] + 2 + K * K]
+                loss = float(host[lay["loss"]:lay["loss"] + 1].view(np.float32)[0])
+                det = host[lay["det"]:lay["det"] + B * ops.MAX_DET * 6].view(np.float32).reshape(B, ops.MAX_DET, 6)
+                tp = host[lay["tp"]:lay["sel"]].view(np.uint8)[:T * B * ops.MAX_DET].reshape(T, B, ops.MAX_DET)
+                total = min(max(total, 0), R_cap)
+                res = {"loss": {"loss": loss, "loss_cls": loss}, "n_true": int(stats[0]), "n_total": int(stats[1]),
+                       "y_pred": host[lay["y_pred"]:lay["y_pred"] + total].astype(np.int64),
+                       "y_true": host[lay["y_true"]:lay["y_true"] + total].astype(np.int64),
+                       "sample_metrics": _unpack_statistics(host[:B], det, tp), "labels": list(self._labels),
+                       "confusion": stats[2:].reshape(K, K).astype(np.int64)}
+        self._result = res
+        self._release()
+        return res
+
+    def _fallback(self):
+        from .evaluation import evaluate_batch, confusion_counts
+        data, slices = self.data, self.slices
+        st = data.__dict__.get("_lazy") if hasattr(data, "__dict__") else None
+        if st is not None:
+            from .data import collate_to_device
+            data, slices = collate_to_device(st.items, device=self._out.device)
+        else:
+            # evaluate_batch overwrites data.labels and slices["bbox"], as the reference does: not on the caller's objects
+            bag = data.__class__()
+            bag.__dict__.update(data.__dict__)
+            data, slices = bag, dict(slices)
+        kw = self.kw
+        crit = DetectionLoss(Opt(classifier=kw["classifier"]))
+        with torch.no_grad():
+            res = evaluate_batch(self.model, crit, data, slices, classifier=kw["classifier"],
+                                 iou_thresholds=kw["iou_thresholds"], conf_thres=kw["conf_thres"],
+                                 iou_thres=kw["iou_thres"], fixup=False, device_post=True)
+        res["confusion"] = confusion_counts(res["y_true"], res["y_pred"], self._lay["K"])
+        return res
+
+    def _release(self):
+        self.data = self.slices = self.pred = self.workspace = None
+
+
 class SparseCADGCN(nn.Module):
     def __init__(self, opt, n_edges=3, edge_max_pool=None, expand_ratio=0.25):
         super(SparseCADGCN, self).__init__()
@@ -324,10 +402,13 @@ class SparseCADGCN(nn.Module):
                 st["x"].shape[0], edge.shape[0], bbox.shape[0], logits.device)
 
     @staticmethod
-    def _predict_tree(data, slices, dev, scales=None):
+    def _predict_tree(data, slices, dev, scales=None, extra=None):
         """The flattened tree (data.flatten_tree) on the device, uploaded once per batch object (keyed by the identity of
         the tree and the image offsets) -> (yolat_predict_tree, the host arrays, address of the scales or None).
-        scales [B, 4] fp32 (detect_submit) travel in the same upload and are cached with it."""
+        scales [B, 4] fp32 (detect_submit) travel in the same upload and are cached with it; so do the arrays of
+        ``extra`` (evaluate_submit: a list of (name, contiguous numpy array of 4- or 8-byte elements), each placed at an
+        8-byte aligned offset) — their device addresses are left in ``tree._addr[name]``.  An upload made under another
+        stream is waited for on the current one before it is handed out."""
         import numpy as np
         from ._lib import PredictTree
         from .data import flatten_tree
@@ -336,35 +417,55 @@ class SparseCADGCN(nn.Module):
                tuple(int(v) for v in slices["edge"]), tuple(int(v) for v in slices["bbox"]))
         ent = d.get("_yolat_tree")
         skey = None if scales is None else scales.tobytes()
+        if extra:
+            skey = (skey,) + tuple((name, a.dtype.str, a.tobytes()) for name, a in extra)
         if ent is None or ent[0] != key or (skey is not None and ent[4] != skey):
             ft = flatten_tree(data, slices)
             order = ("root_row", "root_range", "child_ptr", "child_row", "child_range", "image_root_ptr")
             parts = [ft[k].reshape(-1) for k in order]
-            if scales is not None:
-                parts.append(np.ascontiguousarray(scales, dtype=np.float32).reshape(-1).view(np.int32))
-            host = torch.from_numpy(np.concatenate(parts))
-            if scales is not None:
-                host = host.pin_memory()                 # a copy from pageable memory waits for the stream: predict reads
-                #                                          the device next anyway, detect_submit must not wait
-            buf = host.to(dev, non_blocking=True)
-            buf._yolat_host = host                       # alive until the copy has run: as long as its target
             offs, o = {}, 0
             for k in order:
                 offs[k] = o
                 o += ft[k].size
             offs["scale"] = o
+            if scales is not None:
+                parts.append(np.ascontiguousarray(scales, dtype=np.float32).reshape(-1).view(np.int32))
+                o += parts[-1].size
+            for name, a in (extra or ()):
+                if o % 2:
+                    parts.append(np.zeros(1, dtype=np.int32))
+                    o += 1
+                offs[name] = o
+                parts.append(np.ascontiguousarray(a).reshape(-1).view(np.int32))
+                o += parts[-1].size
+            host = torch.from_numpy(np.concatenate(parts))
+            if skey is not None:
+                host = host.pin_memory()                 # a copy from pageable memory waits for the stream: predict reads
+                #                                          the device next anyway, detect_submit must not wait
+            buf = host.to(dev, non_blocking=True)
+            buf._yolat_host = host                       # alive until the copy has run: as long as its target
+            if extra:
+                up = torch.cuda.Event()
+                up.record(ops.current_stream_object())
+                buf._yolat_upload = (ops._stream(), up)
             ent = (key, ft, buf, offs, skey)
             try:
                 data.__dict__["_yolat_tree"] = ent
             except AttributeError:
                 pass
         _, ft, buf, offs, have = ent
+        upload = getattr(buf, "_yolat_upload", None)
+        if upload is not None and upload[0] != ops._stream():
+            cur = ops.current_stream_object()
+            cur.wait_event(upload[1])
+            buf.record_stream(cur)
         t = PredictTree()
         t.R, t.Ctot, t.B = ft["R"], ft["Ctot"], ft["B"]
         base = buf.data_ptr()
         for k in ("root_row", "root_range", "child_ptr", "child_row", "child_range", "image_root_ptr"):
             setattr(t, k, base + 4 * offs[k])
         t._keep = buf
+        t._addr = {name: base + 4 * offs[name] for name, _ in (extra or ())}
         return t, ft, (base + 4 * offs["scale"]) if have is not None else None
 
     def detect_submit(self, data, slices, conf_thres=0.25, iou_thres=0.45, agnostic=False, classifier=None):
@@ -428,6 +529,108 @@ class SparseCADGCN(nn.Module):
         return DetectHandle(self, data, slices, out, det, det_count, sel, pred, ws, done,
                             dict(conf_thres=conf_thres, iou_thres=iou_thres, agnostic=agnostic,
                                  classifier=self.classifier if classifier is None else classifier))
+
+    def evaluate_submit(self, data, slices, iou_thresholds=None, conf_thres=0.0, iou_thres=0.5, classifier=None):
+        """One iteration of the evaluation loop (``evaluation.evaluate_batch(device_post=True)``: predict, loss, top-1,
+        detections, true-positive flags) ENQUEUED on the current stream: the forward under the model's eval precision, ONE
+        pinned upload (the flattened tree, the scales, gt_ptr, the targets — labels as fp32, boxes times (w, h, w, h) in
+        fp32, formed as evaluate_batch forms them — the thresholds, and the labels when they are on the host; cached on
+        the batch object with the tree), then one ``yolat_evaluate`` call (csrc/evaluate.hip).  No host read, no
+        synchronisation: the returned ``EvalHandle`` says when the batch is done (``ready``) and hands out the dict
+        (``result``, the one read).  Eval mode, a batch with its raw edge list whose index offsets are fixed up already.
+        Host labels are range-checked before anything is enqueued — ALL labels of the batch, where DetectionLoss sees the
+        selected rows only — and raise IndexError; device labels are guarded in the kernel (NaN loss).  ``data`` and
+        ``slices`` are not modified.  ``classifier``: as ``evaluate_batch``'s, default the model's own."""
+        import ctypes
+        import numpy as np
+        from ._lib import lib, check
+        if self.training:
+            raise RuntimeError("evaluate_submit runs the eval forward: call model.eval() first")
+        d = data.__dict__ if hasattr(data, "__dict__") else {}
+        if d.get("_yolat_graph") is not None and not all(k in data.keys for k in ("edge", "e_attr", "bbox_idx")):
+            raise ValueError(_PREPARED_BATCH)
+        if iou_thresholds is None:
+            iou_thresholds = np.linspace(0.5, 0.95, 10)
+        ths = np.ascontiguousarray(np.asarray(iou_thresholds, dtype=np.float32).reshape(-1))
+        labels = data.labels
+        if not labels.is_cuda and labels.numel():
+            lo, hi = int(labels.min()), int(labels.max())
+            if lo < 0 or hi >= self.n_classes:
+                raise IndexError("Target %d is out of bounds." % (lo if lo < 0 else hi))
+        with torch.no_grad():
+            logits, bbox = self.forward(data, slices)
+        opnd = self._predict_operands(data, logits, bbox)
+        if opnd is None:
+            raise ValueError("evaluate_submit expects the edge list as [E, 2]")
+        ep, se, sc, bp, N, E, P, dev = opnd
+        B = len(slices["roots"]) - 1
+        K, T = int(logits.shape[1]), int(ths.shape[0])
+        scales = np.ones((B, 4), dtype=np.float32)
+        if hasattr(data, "width") and hasattr(data, "height"):
+            for i in range(B):
+                scales[i] = (float(data.width[i]), float(data.height[i])) * 2
+        # the targets of evaluate_batch: rows label_ptr[i]:label_ptr[i + 1] of image i, boxes scaled in fp32
+        lptr = np.asarray([int(v) for v in slices["gt_labels"]], dtype=np.int64)
+        if lptr.shape[0] != B + 1:
+            raise ValueError("slices['gt_labels'] must hold B + 1 offsets")
+        g0, g1 = int(lptr[0]), int(lptr[-1])
+        per_image = np.repeat(np.arange(B), np.diff(lptr))
+        gt_labels = data.gt_labels[g0:g1].cpu()
+        gt_box = (data.gt_bbox[g0:g1].cpu().float() * torch.from_numpy(scales)[torch.from_numpy(per_image)]).numpy()
+        G = int(gt_box.shape[0])
+        extra = [("gt_ptr", (lptr - g0).astype(np.int32)), ("gt_box", np.ascontiguousarray(gt_box, dtype=np.float32)),
+                 ("gt_label", gt_labels.float().numpy()), ("thresholds", ths)]
+        if not labels.is_cuda:
+            extra.append(("labels", np.ascontiguousarray(labels.numpy(), dtype=np.int64)))
+        elif labels.dtype != torch.int64 or not labels.is_contiguous():
+            labels = labels.long().contiguous()
+        if int(labels.shape[0]) != P:
+            raise ValueError("labels must hold one class id per proposal")
+        t, ft, scale_ptr = self._predict_tree(data, slices, dev, scales, extra)
+        R_cap = ft["R"] + ft["Ctot"]
+        need = int(lib.yolat_evaluate_workspace_bytes(N, P, ft["R"], ft["Ctot"], K, B, G, T))
+        if need == 0:
+            raise ValueError("evaluate_submit: a batch of %d images, %d tree nodes, %d classes, %d targets and %d thresholds "
+                             "is outside what yolat_evaluate supports (K in [2, 32], B <= 65536, rows * (K - 1) <= 2^27, "
+                             "targets <= 262144, thresholds <= 65535)" % (B, R_cap, K, G, T))
+        if logits.dtype != torch.float32 or logits.stride(1) != 1:
+            logits = logits.float().contiguous()
+        bb = bbox if (bbox.dtype == torch.float32 and bbox.is_contiguous()) else bbox.float().contiguous()
+        # one allocation for what result() looks at, in int32 units; sel comes last so that the copy ends behind sel[0:4]
+        lay, o = {"B": B, "K": K, "T": T, "R_cap": R_cap}, B
+        for name, n in (("stats", 2 + K * K), ("loss", 1), ("y_pred", R_cap), ("y_true", R_cap),
+                        ("det", B * ops.MAX_DET * 6), ("tp", (T * B * ops.MAX_DET + 3) // 4), ("sel", 4 + B + 1 + R_cap)):
+            lay[name] = o
+            o += n
+        lay["copy"] = lay["sel"] + 4
+        out = torch.empty(o, dtype=torch.int32, device=dev)
+        sel = out[lay["sel"]:]
+        pred = torch.empty((R_cap, 4 + K), dtype=torch.float32, device=dev)
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        cls = self.classifier if classifier is None else classifier
+        base, addr = out.data_ptr(), t._addr
+        stream = ops._stream()
+        check(lib.yolat_evaluate(logits.data_ptr(), logits.stride(0), P, K, bb.data_ptr(), ep if E > 0 else None, se, sc, bp,
+                                 N, E, ctypes.byref(t), scale_ptr, int(cls == "softmax"), float(conf_thres),
+                                 float(iou_thres), addr["labels"] if "labels" in addr else labels.data_ptr(),
+                                 addr["gt_box"], addr["gt_label"], G, addr["gt_ptr"], addr["thresholds"], T,
+                                 sel.data_ptr(), pred.data_ptr(), base + 4 * lay["det"], base, base + 4 * lay["stats"],
+                                 base + 4 * lay["loss"], base + 4 * lay["y_pred"], base + 4 * lay["y_true"],
+                                 base + 4 * lay["tp"], ws.data_ptr(), ws.numel(), stream), "yolat_evaluate")
+        plan = self.__dict__.get("_yolat_plan")
+        status = getattr(plan, "_status", None)
+        if status is not None:
+            # the forward's input-validity word rides along in sel[2]; cleared behind the copy (stream order), so that the
+            # next handle carries the flags of ITS forward only
+            sel[2:3].copy_(status)
+            status.zero_()
+        cur = ops.current_stream_object()
+        done = torch.cuda.Event()
+        done.record(cur)
+        hold = (logits, bb, labels, t)                   # what the launches read: alive as long as the handle's record
+        out._yolat_keep = hold
+        return EvalHandle(self, data, slices, out, lay, sel, pred, ws, done, cur, gt_labels.tolist(),
+                          dict(conf_thres=conf_thres, iou_thres=iou_thres, classifier=cls, iou_thresholds=iou_thresholds))
 
     def _predict_one_submission(self, data, slices):
         """One forward over the whole batch, then yolat_predict_select / yolat_predict_gather (csrc/subgraph.hip): in eval

@@ -1,7 +1,9 @@
 // loss_optim.hip — nn.CrossEntropyLoss of DetectionLoss (architecture3cc_rpn_gp_iter2.py:363,376), the sigmoid /
 // nn.BCELoss head of classifier != 'softmax' (:132-133,362-376), and the torch.optim.Adam step of
-// cad_recognition/train.py:212,284 over one flat buffer.
+// cad_recognition/train.py:212,284 over one flat buffer.  The per-row functions of both losses and the two fixed-order
+// trees live in loss_rows.hpp, which evaluate.hip includes too.
 #include "base.hpp"
+#include "loss_rows.hpp"
 
 // One 1024-thread workgroup; thread t owns rows t, t+1024, ...; fixed-order tree reduction.
 __global__ void __launch_bounds__(1024) k_softmax_ce(const float* logits, long ld,
@@ -42,64 +44,23 @@ __global__ void __launch_bounds__(1024) k_softmax_ce(const float* logits, long l
 }
 
 // Multi-workgroup variant: one row per thread, 256 rows per workgroup; the row is held in registers
-// (K <= 32: all loads independent, one expf per element), the workgroup's loss sum goes to work[wg] via a
-// fixed-order tree, and k_ce_final adds the per-workgroup sums in a fixed order -> run-to-run deterministic.
+// (YL_CE_ROW_LOSS, K <= 32), the workgroup's loss sum goes to work[wg] via a fixed-order tree, and k_ce_final adds the
+// per-workgroup sums in a fixed order -> run-to-run deterministic.
 template <int KMAX>
 __global__ void __launch_bounds__(256) k_softmax_ce_rows(const float* logits, long ld, const int64_t* labels,
                                                          int P, int K, float* work, float* dl, long lddl) {
-  __shared__ float red[256];
   const int tid = threadIdx.x;
   const int p = blockIdx.x * 256 + tid;
   float row_loss = 0.f;
   if (p < P) {
     const float* z = logits + (long)p * ld;
-    float v[KMAX];
-#pragma unroll
-    for (int k = 0; k < KMAX; ++k) v[k] = z[k < K ? k : K - 1];
-    float m = v[0];
-#pragma unroll
-    for (int k = 1; k < KMAX; ++k) m = fmaxf(m, v[k]);
-    float s = 0.f;
-#pragma unroll
-    for (int k = 0; k < KMAX; ++k) {
-      v[k] = expf(v[k] - m);
-      s += (k < K) ? v[k] : 0.f;
-    }
-    // a label outside [0, K) (torch raises "Target out of bounds"; ignore_index is not used by the reference,
-    // architecture3cc_rpn_gp_iter2.py:363) must not become an out-of-bounds read: the loss is poisoned with NaN
-    const int64_t yl = labels[p];
-    const bool bad = yl < 0 || yl >= K;
-    const int y = bad ? 0 : (int)yl;
-    row_loss = bad ? __builtin_nanf("") : m + logf(s) - z[y];
-    if (dl != nullptr) {
-      const float invs = 1.f / s, invP = 1.f / (float)P;
-      float* d = dl + (long)p * lddl;
-#pragma unroll
-      for (int k = 0; k < KMAX; ++k)
-        if (k < K) d[k] = (v[k] * invs - (k == y ? 1.f : 0.f)) * invP;
-    }
+    YL_CE_ROW_LOSS(KMAX, z, K, labels, p, P, dl, lddl, row_loss)
   }
-  red[tid] = row_loss;
-  __syncthreads();
-  for (int st = 128; st > 0; st >>= 1) {
-    if (tid < st) red[tid] += red[tid + st];
-    __syncthreads();
-  }
-  if (tid == 0) work[blockIdx.x] = red[0];
+  yl_rows_tree256(tid, row_loss, work + blockIdx.x);
 }
 
 __global__ void __launch_bounds__(1024) k_ce_final(const float* work, int n, int P, float* loss) {
-  __shared__ float red[1024];
-  const int tid = threadIdx.x;
-  float a = 0.f;
-  for (int i = tid; i < n; i += 1024) a += work[i];
-  red[tid] = a;
-  __syncthreads();
-  for (int st = 512; st > 0; st >>= 1) {
-    if (tid < st) red[tid] += red[tid + st];
-    __syncthreads();
-  }
-  if (tid == 0) loss[0] = red[0] / (float)P;
+  yl_partials_tree1024(work, n, threadIdx.x, [=](float sum) { loss[0] = sum / (float)P; });
 }
 
 extern "C" size_t yolat_softmax_ce_work_elems(int64_t P) { return (size_t)((P + 255) / 256 + 1); }
@@ -126,90 +87,27 @@ extern "C" int yolat_softmax_ce(const float* logits, int64_t ld, const int64_t* 
 }
 
 // ------------------------------------------------------------------------------------------------
-// classifier != 'softmax' (architecture3cc_rpn_gp_iter2.py:132-133,362-376): torch.sigmoid on the logits, nn.BCELoss
-// (mean over all P*K elements) against the one-hot labels.  Every step is rounded to fp32 on its own, in torch's order:
-//   p = 1 / (1 + exp(-z));  term = -max(log(p), -100) (target 1) or -max(log(1 - p), -100) (target 0)
-//   q = p (1 - p);  dp = ((p - t) / max(q, 1e-12)) / n;  dz = dp q
-// which is BCELoss' backward followed by sigmoid's — NOT the closed form (p - t) / n: where p rounds to exactly 1.0f or
-// 0.0f the reference's gradient is 0 and a wrong element's loss term is 100, and that is kept.
-// The fused entry point and the three separate ones run these same four functions, so they agree bit for bit.
+// classifier != 'softmax' (architecture3cc_rpn_gp_iter2.py:132-133,362-376): the sigmoid / nn.BCELoss head.  The
+// element functions (yl_sigmoid, yl_bce_term, yl_bce_dp, yl_sigmoid_dz, yl_bce_elem) and the row body (YL_BCE_ROW_LOSS) are in
+// loss_rows.hpp.  One row per thread, 256 rows per workgroup, like k_softmax_ce_rows: the workgroup's rows are added in
+// a fixed-order tree -> work[wg]; k_bce_final adds those in order.
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float yl_sigmoid(float z) { return 1.f / (1.f + expf(-z)); }
-__device__ __forceinline__ float yl_bce_term(float p, bool t) {
-  return -(t ? fmaxf(logf(p), -100.f) : fmaxf(logf(1.f - p), -100.f));
-}
-__device__ __forceinline__ float yl_bce_dp(float p, bool t, float inv_n) {
-  const float q = p * (1.f - p);
-  return ((p - (t ? 1.f : 0.f)) / fmaxf(q, 1e-12f)) * inv_n;
-}
-__device__ __forceinline__ float yl_sigmoid_dz(float dp, float p) { return dp * (p * (1.f - p)); }
-
-// One element of a row: in = logit (LOGITS) or probability; adds the loss term, writes prob (LOGITS only, nullable)
-// and the gradient w.r.t. `in` (nullable).
-template <bool LOGITS>
-__device__ __forceinline__ float yl_bce_elem(float in, bool t, float inv_n, float* prob, float* dout) {
-  const float p = LOGITS ? yl_sigmoid(in) : in;
-  if (LOGITS && prob != nullptr) *prob = p;
-  if (dout != nullptr) {
-    const float dp = yl_bce_dp(p, t, inv_n);
-    *dout = LOGITS ? yl_sigmoid_dz(dp, p) : dp;
-  }
-  return yl_bce_term(p, t);
-}
-
-// One row per thread, 256 rows per workgroup, like k_softmax_ce_rows.  KMAX > 0: K <= KMAX, the row is loaded into
-// registers first (all loads independent); KMAX == 0: a plain loop over K.  The row's terms are added in ascending
-// column order either way, the workgroup's rows in a fixed-order tree -> work[wg]; k_bce_final adds those in order.
 template <int KMAX, bool LOGITS>
 __global__ void __launch_bounds__(256) k_bce_rows(const float* in, long ld, const int64_t* labels, int P, int K,
                                                   float inv_n, float* work, float* dout, long ldd, float* prob,
                                                   long ldp) {
-  __shared__ float red[256];
   const int tid = threadIdx.x;
   const int p = blockIdx.x * 256 + tid;
   float row_loss = 0.f;
   if (p < P) {
     const float* z = in + (long)p * ld;
-    // a label outside [0, K) matches no column (nothing is read through it); the loss is poisoned with NaN
-    const int64_t yl = labels[p];
-    const bool bad = yl < 0 || yl >= K;
-    const int y = bad ? -1 : (int)yl;
-    float* d = dout != nullptr ? dout + (long)p * ldd : nullptr;
-    float* pr = (LOGITS && prob != nullptr) ? prob + (long)p * ldp : nullptr;
-    if (KMAX > 0) {
-      float v[KMAX > 0 ? KMAX : 1];
-#pragma unroll
-      for (int k = 0; k < KMAX; ++k) v[k] = z[k < K ? k : K - 1];
-#pragma unroll
-      for (int k = 0; k < KMAX; ++k)
-        if (k < K) row_loss += yl_bce_elem<LOGITS>(v[k], k == y, inv_n, pr ? pr + k : nullptr, d ? d + k : nullptr);
-    } else {
-      for (int k = 0; k < K; ++k)
-        row_loss += yl_bce_elem<LOGITS>(z[k], k == y, inv_n, pr ? pr + k : nullptr, d ? d + k : nullptr);
-    }
-    if (bad) row_loss = __builtin_nanf("");
+    YL_BCE_ROW_LOSS(KMAX, LOGITS, z, K, labels, p, inv_n, dout, ldd, prob, ldp, row_loss)
   }
-  red[tid] = row_loss;
-  __syncthreads();
-  for (int st = 128; st > 0; st >>= 1) {
-    if (tid < st) red[tid] += red[tid + st];
-    __syncthreads();
-  }
-  if (tid == 0) work[blockIdx.x] = red[0];
+  yl_rows_tree256(tid, row_loss, work + blockIdx.x);
 }
 
 __global__ void __launch_bounds__(1024) k_bce_final(const float* work, int n, float inv_n, float* loss) {
-  __shared__ float red[1024];
-  const int tid = threadIdx.x;
-  float a = 0.f;
-  for (int i = tid; i < n; i += 1024) a += work[i];
-  red[tid] = a;
-  __syncthreads();
-  for (int st = 512; st > 0; st >>= 1) {
-    if (tid < st) red[tid] += red[tid + st];
-    __syncthreads();
-  }
-  if (tid == 0) loss[0] = inv_n * red[0];
+  yl_partials_tree1024(work, n, threadIdx.x, [=](float sum) { loss[0] = inv_n * sum; });
 }
 
 __global__ void k_sigmoid(const float* z, long ldz, long n, int K, float* out, long ldo) {

@@ -146,26 +146,159 @@ def detect_stream(model, batches, depth=4, **kw):
         yield flying.popleft().result()
 
 
+def confusion_counts(y_true, y_pred, K):
+    """Confusion matrix np.int64 [K, K] of two equally long integer sequences: entry [t, p] counts the rows of true class t
+    predicted as p (the table train.py:489-505 prints).  Rows whose true or predicted class is outside [0, K) are ignored."""
+    t = np.asarray(y_true, dtype=np.int64).reshape(-1)
+    p = np.asarray(y_pred, dtype=np.int64).reshape(-1)
+    if t.shape != p.shape:
+        raise ValueError("confusion_counts expects y_true and y_pred of one length")
+    ok = (t >= 0) & (t < K) & (p >= 0) & (p < K)
+    out = np.zeros((int(K), int(K)), dtype=np.int64)
+    np.add.at(out, (t[ok], p[ok]), 1)
+    return out
+
+
+def evaluate_batch_async(model, data, slices, fixup=True, **kw):
+    """``evaluate_batch(device_post=True)`` as a submission: the same ``fixup`` / ``edge_control`` handling, then
+    ``model.evaluate_submit`` — forward, selection, loss, top-1 and confusion counts, scores, NMS and the true-positive
+    walk enqueued on the current stream, nothing read back.  Returns the ``EvalHandle``; ``handle.result()`` is the dict
+    ``evaluate_batch`` returns (the loss bit for bit) plus ``confusion``.  ``kw``: ``iou_thresholds``, ``conf_thres``,
+    ``iou_thres``, ``classifier`` (default: the model's own).  ``data.labels`` and ``slices["bbox"]`` are left as they
+    are; the criterion is DetectionLoss' by construction."""
+    if fixup:
+        fixup_offsets(data, slices)
+    if not hasattr(data, "edge_control"):
+        data.edge_control = None
+    return model.evaluate_submit(data, slices, **kw)
+
+
+MAX_EVAL_STREAMS = 4
+
+
+def evaluate_stream(model, batches, depth=4, streams=None, **kw):
+    """Generator over the evaluation dicts of ``batches`` — a ``DeviceLoader(..., csr=False)`` or any iterable of
+    ``(data, slices)`` batches — with up to ``depth`` batches in flight: batch i + depth is submitted before the host looks
+    at batch i.  Yields, in order, what ``evaluate_batch_async(...).result()`` returns for each batch.  ``kw``: the
+    keywords of ``evaluate_batch_async``; ``fixup`` defaults to False here (device batches carry their offsets already).
+    ``streams``: None — the current stream — or a list of 1 to 4 ``torch.cuda.Stream``: batch i is submitted under
+    ``streams[i % len(streams)]``, so that the serial chains of consecutive batches overlap on the GPU.  Every listed
+    stream first waits for an event recorded on the caller's current stream at entry, and each submission for one
+    recorded there after its batch was drawn (a batch collated while the generator runs is complete before another stream
+    reads it).  A handle's tensors are allocated under its stream and only host arrays leave the generator.
+    Over a DeviceLoader: ``depth <= slots - 2`` as for ``detect_stream``, and one stream at the most — the loader's ring
+    belongs to the stream its batches are drawn on (ValueError otherwise)."""
+    from collections import deque
+    from .data import DeviceLoader
+    depth = int(depth)
+    if depth < 1:
+        raise ValueError("evaluate_stream needs depth >= 1")
+    if streams is not None:
+        streams = list(streams)
+        if not 1 <= len(streams) <= MAX_EVAL_STREAMS:
+            raise ValueError("evaluate_stream takes 1 to %d streams, got %d" % (MAX_EVAL_STREAMS, len(streams)))
+    if isinstance(batches, DeviceLoader):
+        if streams is not None and len(streams) > 1:
+            raise ValueError("evaluate_stream over a DeviceLoader takes one stream: the loader's ring belongs to the stream "
+                             "its batches are drawn on")
+        slots = getattr(batches, "_slots", None)
+        if not isinstance(slots, int):
+            raise ValueError("evaluate_stream cannot tell how many slots the loader has")
+        if depth > slots - 2:
+            raise ValueError("evaluate_stream(depth=%d) over a DeviceLoader needs slots >= depth + 2, the loader has %d"
+                             % (depth, slots))
+    kw.setdefault("fixup", False)
+    flying = deque()
+    if streams is None:
+        for data, slices in batches:
+            flying.append(evaluate_batch_async(model, data, slices, **kw))
+            if len(flying) >= depth:
+                yield flying.popleft().result()
+    elif isinstance(batches, DeviceLoader):
+        # the draws themselves happen under the stream: the loader hands a slot back behind an event on the drawing stream
+        entry = torch.cuda.Event()
+        entry.record(ops.current_stream_object())
+        streams[0].wait_event(entry)
+        it = iter(batches)
+        while True:
+            with torch.cuda.stream(streams[0]):
+                nxt = next(it, None)
+                if nxt is None:
+                    break
+                flying.append(evaluate_batch_async(model, nxt[0], nxt[1], **kw))
+            if len(flying) >= depth:
+                yield flying.popleft().result()
+    else:
+        home = ops.current_stream_object()
+        entry = torch.cuda.Event()
+        entry.record(home)
+        for s in streams:
+            s.wait_event(entry)
+        for i, (data, slices) in enumerate(batches):
+            s = streams[i % len(streams)]
+            drawn = torch.cuda.Event()
+            drawn.record(home)
+            s.wait_event(drawn)
+            with torch.cuda.stream(s):
+                flying.append(evaluate_batch_async(model, data, slices, **kw))
+            if len(flying) >= depth:
+                yield flying.popleft().result()
+    while flying:
+        yield flying.popleft().result()
+
+
+def _async_eval_applies(model, criterion, opt):
+    """test() takes evaluate_stream when opt.async_eval is set, the criterion is DetectionLoss itself (what the rows stage
+    computes) and the class count is one the rows kernel holds in registers; anything else takes the synchronous loop"""
+    from .architecture import DetectionLoss
+    return bool(getattr(opt, "async_eval", False)) and type(criterion) is DetectionLoss and \
+        2 <= int(getattr(model, "n_classes", 0)) <= 32
+
+
+def _eval_streams(opt):
+    n = getattr(opt, "eval_streams", None)
+    if n is None:
+        return None
+    if isinstance(n, int):
+        return [torch.cuda.Stream() for _ in range(n)]
+    return list(n)
+
+
 def test(model, test_loader, criterion, opt):
     """train.py:324-508.  Returns the mean AP at the last IoU threshold (None when nothing was detected), like the
-    reference; the per-threshold mAPs, MAP@ALL, top-1 accuracy and mean losses are left in ``opt.test_report``."""
+    reference; the per-threshold mAPs, MAP@ALL, top-1 accuracy and mean losses are left in ``opt.test_report``.
+    ``opt.async_eval`` (absent: the loop below as it always was): the batches go through ``evaluate_stream`` with
+    ``opt.eval_depth`` (default 4) in flight on ``opt.eval_streams`` streams (a count or a list; default the current
+    stream) when the criterion is DetectionLoss — same value, same report, plus ``report["confusion"]``, the [K, K]
+    counts summed over the batches."""
     model.eval()
     steps = int(getattr(opt, "map_step", 10))
     ths = np.linspace(0.5, 0.95, steps)
     metrics, labels, losses = [[] for _ in range(steps)], [], {}
     n_true = n_total = 0
+    confusion = None
+    classifier = getattr(opt, "classifier", "softmax")
     with torch.no_grad():
-        for data, slices in test_loader:
-            rep = evaluate_batch(model, criterion, data, slices, classifier=getattr(opt, "classifier", "softmax"),
-                                 iou_thresholds=ths, device_post=bool(getattr(opt, "device_postprocess", False)))
+        if _async_eval_applies(model, criterion, opt):
+            reps = evaluate_stream(model, test_loader, depth=int(getattr(opt, "eval_depth", 4)), streams=_eval_streams(opt),
+                                   fixup=True, classifier=classifier, iou_thresholds=ths)
+        else:
+            reps = (evaluate_batch(model, criterion, data, slices, classifier=classifier, iou_thresholds=ths,
+                                   device_post=bool(getattr(opt, "device_postprocess", False)))
+                    for data, slices in test_loader)
+        for rep in reps:
             for t in range(steps):
                 metrics[t] += rep["sample_metrics"][t]
             labels += rep["labels"]
             n_true, n_total = n_true + rep["n_true"], n_total + rep["n_total"]
             for k, v in rep["loss"].items():
                 losses.setdefault(k, []).append(v)
+            if "confusion" in rep:
+                confusion = rep["confusion"].copy() if confusion is None else confusion + rep["confusion"]
     report = {"iou_thresholds": ths, "map": [], "top1": n_true / max(n_total, 1),
               "loss": {k: float(np.mean(v)) for k, v in losses.items()}}
+    if confusion is not None:
+        report["confusion"] = confusion
     ap = None
     for t in range(steps):
         if len(metrics[t]) == 0:

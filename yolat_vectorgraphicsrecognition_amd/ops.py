@@ -1387,6 +1387,36 @@ def detect_rows(logits, bbox, sel, B, R_cap, scale, softmax=True, out=None):
     return out
 
 
+def evaluate_workspace_bytes(N, P, R, Ctot, K, B, G, T):
+    """Workspace of yolat_evaluate in bytes (0: shape not supported)."""
+    return int(lib.yolat_evaluate_workspace_bytes(int(N), int(P), int(R), int(Ctot), int(K), int(B), int(G), int(T)))
+
+
+def eval_rows(logits, labels, sel, B, R_cap, softmax=True):
+    """yolat_eval_rows (csrc/evaluate.hip): the rows stage of the asynchronous evaluation from the record
+    yolat_predict_select wrote.  logits [P, K] (the probabilities of a sigmoid model with softmax=False), labels [P] int64,
+    sel [4 + B + 1 + R_cap] int32 -> (loss [1] fp32, stats [2 + K * K] int32 = n_true, n_total, confusion[label, y_pred],
+    y_pred [R_cap] int32, y_true [R_cap] int32), all on the device.  The loss is bit for bit DetectionLoss' on the rows
+    ``predict`` gathers; entries of y_pred / y_true behind sel[0] are not written.  Nothing is read back."""
+    lp = _f(logits, "logits")
+    if logits.dim() != 2 or not 2 <= logits.shape[1] <= 32:
+        raise ValueError("eval_rows expects logits [P, K] with K in [2, 32]")
+    P, K = int(logits.shape[0]), int(logits.shape[1])
+    B, R_cap = int(B), int(R_cap)
+    yp, ip = _i(labels, torch.int64, "labels"), _i(sel, torch.int32, "sel")
+    if labels.dim() != 1 or labels.shape[0] != P or B < 1 or sel.dim() != 1 or sel.numel() < 4 + B + 1 + R_cap:
+        raise ValueError("eval_rows expects labels [P] and sel [4 + B + 1 + R_cap]")
+    dev = logits.device
+    loss = torch.empty(1, dtype=torch.float32, device=dev)
+    stats = torch.empty(2 + K * K, dtype=torch.int32, device=dev)
+    y_pred = torch.empty(R_cap, dtype=torch.int32, device=dev)
+    y_true = torch.empty(R_cap, dtype=torch.int32, device=dev)
+    work = torch.empty((R_cap + 255) // 256 + 1, dtype=torch.float32, device=dev)
+    check(lib.yolat_eval_rows(lp, _ld(logits), P, K, yp, ip, B, R_cap, int(bool(softmax)), stats.data_ptr(), loss.data_ptr(),
+                              y_pred.data_ptr(), y_true.data_ptr(), work.data_ptr(), _stream()), "yolat_eval_rows")
+    return loss, stats, y_pred, y_true
+
+
 D2H_READS = 0
 
 
