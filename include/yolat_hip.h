@@ -1478,6 +1478,72 @@ int yolat_augment_batch(float* pos, float* x, int64_t ldx, int64_t col_x, int64_
                         const int64_t* prop_ptr, float* bbox, const double* params, int64_t N, int64_t P, int64_t B,
                         yolat_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * The metrics of an evaluation EPOCH on the device (metrics.hip): the mAP of cad_recognition/train.py:462-508 —
+ * utils/det_util.py:71-145, ap_per_class + compute_ap, at up to 32 IoU thresholds — the mean loss and the summed
+ * top-1 / confusion counts, from what yolat_evaluate leaves on the device per batch.  Nothing is read back by any call.
+ *
+ * THE EPOCH RECORD is ONE caller-owned device buffer of yolat_metrics_record_bytes(capacity_images, K, batch_cap)
+ * bytes, 256-byte aligned, made of eight sections in this order, each starting at a multiple of 256 bytes (the offsets
+ * are written to `offsets` [8] when it is not NULL); S = 300 * capacity_images:
+ *   0 conf         fp32   [S]            } slot s: image s / 300 of the epoch, detection rank s % 300.  Image i of the
+ *   1 cls          int32  [S]            } epoch owns the slots [300 i, 300 i + 300).  cls = -1: the slot is unfilled.
+ *   2 tp           uint32 [S]            } bit t of tp: the detection is a true positive at threshold t (T <= 32)
+ *   3 gt_hist      int64  [K]              targets per class id
+ *   4 stats        int64  [2 + K*K]        n_true, n_total, confusion[label, predicted] summed over the batches
+ *   5 loss         fp32   [batch_cap]      the loss of batch b
+ *   6 batch_flags  int32  [batch_cap][2]   sel[1] (tree not made of its proposals' ranges) and sel[2] (status) of batch b
+ *   7 status       int32  [1]              YOLAT_METRICS_* bits
+ * Capacity: capacity_images * 300 <= 2^27 slots (447 392 images), batch_cap <= 2^24, K in [2, 32]; outside that the
+ * size query returns 0.  The HOST assigns the slots — it knows B of every batch, image_base and batch_index are plain
+ * arguments, there is no cursor on the device — so calls enqueued on several streams write disjoint slots and the record,
+ * and every number derived from it, does not depend on the number of streams.  A larger record is made by the caller:
+ * allocate, yolat_metrics_reset, copy the sections, swap.
+ *
+ * yolat_metrics_reset   every section zero, every slot unfilled.
+ * yolat_metrics_append  ONE launch.  Arguments as yolat_evaluate wrote them for a batch of B images: det [B,300,6],
+ *   det_count [B], tp [T,B,300], stats [2 + K*K] int32, loss [1], sel; gt_labels [G] the batch's target classes as fp32.
+ *   sel[1] and sel[2] are read ON THE DEVICE and stored in batch_flags[batch_index]; only if both are zero, the first
+ *   det_count[b] rows of image b go to the slots of image image_base + b (conf = column 4, cls = column 5, tp packed
+ *   over t; a class that is not an integer in [0, K) is a class no target has: its slot stays unfilled), gt_labels are
+ *   counted into gt_hist, stats is added and loss stored at loss[batch_index].  Integer atomics only; floats are
+ *   stored, never added: two epochs are bit-identical.  A gt_label that is not an integer in [0, K) sets
+ *   YOLAT_METRICS_BAD_GT_LABEL in the status word and is counted nowhere; nothing is indexed through it.
+ * yolat_metrics_append_host  the same launch on arrays the HOST computed for one batch and uploaded (the synchronous
+ *   fall-back of a batch whose flags were set): no sel, batch_flags[batch_index] keeps what the device stored.
+ *   YOLAT_E_INVALID for image_base + B > capacity_images or batch_index >= batch_cap.
+ * yolat_metrics_finalize  over the first n_images * 300 slots and the first n_batches batches:
+ *   1. a STABLE sort of the filled slots into class runs, descending conf inside a run (-0 = +0); equal scores keep slot
+ *      order, i.e. epoch image order, then detection rank.  (rocPRIM radix sort of class << 32 | ordered conf bits:
+ *      the stable descending sort by conf followed by a stable regrouping by class gives exactly this order.  A NaN
+ *      conf — NMS drops them — lands at the end of its run, in slot order, where numpy's argsort puts it.)
+ *   2. per (t, c) with gt_hist[c] > 0 and a non-empty run, in float64 as numpy does: tpc / fpc the cumulative counts,
+ *      recall = tpc / (n_gt + 1e-16), precision = tpc / (tpc + fpc), the precision envelope (reverse running maximum,
+ *      sentinels (0, 0) and (1, 0)), AP = the area summed at the recall change points; p / r = the last point.  A class
+ *      without targets or without detections: 0 (the caller leaves classes with n_gt == 0 out of the mean).
+ *   3. `out`, yolat_metrics_out_bytes(T, K, n_batches) bytes, 8-byte aligned, ONE block:  ap [T,K] f64 | p [T,K] f64 |
+ *      r [T,K] f64 | n_gt [K] i64 | n_p [K] i64 (filled slots per class) | loss_mean f64 (loss[0:n_batches] added in
+ *      index order / n_batches) | stats [2 + K*K] i64 | status i64 | batch_flags [n_batches][2] i32.
+ *   work: yolat_metrics_finalize_work_bytes(n_images, T, K) bytes, 256-byte aligned.  K outside [2, 32], T outside
+ *   [1, 32] or n_images * 300 > 2^27: the query returns 0 and the call YOLAT_E_UNSUPPORTED, before the first launch.  */
+#define YOLAT_METRICS_SLOTS 300
+#define YOLAT_METRICS_BAD_GT_LABEL 1
+size_t yolat_metrics_record_bytes(int64_t capacity_images, int64_t K, int64_t batch_cap, int64_t* offsets);
+int yolat_metrics_reset(void* record, int64_t capacity_images, int64_t K, int64_t batch_cap, yolat_stream_t stream);
+int yolat_metrics_append(void* record, int64_t capacity_images, int64_t K, int64_t batch_cap, const float* det,
+                         const int32_t* det_count, const uint8_t* tp, const int32_t* stats, const float* loss,
+                         const float* gt_labels, int64_t G, const int32_t* sel, int64_t B, int64_t T, int64_t image_base,
+                         int64_t batch_index, yolat_stream_t stream);
+int yolat_metrics_append_host(void* record, int64_t capacity_images, int64_t K, int64_t batch_cap, const float* det,
+                              const int32_t* det_count, const uint8_t* tp, const int32_t* stats, const float* loss,
+                              const float* gt_labels, int64_t G, int64_t B, int64_t T, int64_t image_base,
+                              int64_t batch_index, yolat_stream_t stream);
+size_t yolat_metrics_finalize_work_bytes(int64_t n_images, int64_t T, int64_t K);
+size_t yolat_metrics_out_bytes(int64_t T, int64_t K, int64_t n_batches);
+int yolat_metrics_finalize(const void* record, int64_t capacity_images, int64_t K, int64_t batch_cap, int64_t n_images,
+                           int64_t n_batches, int64_t T, void* out, size_t out_bytes, void* work, size_t work_bytes,
+                           yolat_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

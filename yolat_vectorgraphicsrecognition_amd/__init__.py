@@ -23,7 +23,7 @@ from .data import (Data, DeviceLoader, collate, collate_to_device, item_csr, fix
 from .postprocess import (non_max_suppression, get_batch_statistics, ap_per_class, compute_ap, bbox_iou,  # noqa: F401
                           non_max_suppression_batched, get_batch_statistics_batched)
 from .evaluation import evaluate_batch, detect_batch, detect_batch_async, detect_stream, test as evaluate  # noqa: F401
-from .evaluation import evaluate_batch_async, evaluate_stream, confusion_counts  # noqa: F401
+from .evaluation import evaluate_batch_async, evaluate_stream, confusion_counts, EpochMetrics  # noqa: F401
 from .architecture import DetectHandle, EvalHandle  # noqa: F401
 from .trainer import (FlatParams, FlatAdam, Trainer, shard_graph_ids, allreduce_mean_, broadcast_parameters,  # noqa: F401
                       load_reference_checkpoint)

@@ -390,6 +390,16 @@ SIGNATURES = {
                                             ctypes.POINTER(GraphCsr), c_i64, c_i64, c_i64, c_p, c_i64, c_p, c_sz, c_p,
                                             ctypes.POINTER(Locality), c_int, c_p]),
     "yolat_augment_batch": (c_int, [c_p, c_p, c_i64, c_i64, c_i64, c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_p]),
+    # epoch metrics (metrics.hip)
+    "yolat_metrics_record_bytes": (c_sz, [c_i64, c_i64, c_i64, c_p]),
+    "yolat_metrics_reset": (c_int, [c_p, c_i64, c_i64, c_i64, c_p]),
+    "yolat_metrics_append": (c_int, [c_p, c_i64, c_i64, c_i64, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_p, c_i64, c_i64, c_i64,
+                                     c_i64, c_p]),
+    "yolat_metrics_append_host": (c_int, [c_p, c_i64, c_i64, c_i64, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_i64,
+                                          c_i64, c_p]),
+    "yolat_metrics_finalize_work_bytes": (c_sz, [c_i64, c_i64, c_i64]),
+    "yolat_metrics_out_bytes": (c_sz, [c_i64, c_i64, c_i64]),
+    "yolat_metrics_finalize": (c_int, [c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_p, c_sz, c_p, c_sz, c_p]),
 }
 
 

@@ -226,6 +226,16 @@ class EvalHandle(object):
         self._release()
         return res
 
+    def device_record(self):
+        """Views of the device record, nothing read: (det [B, 300, 6], det_count [B], tp [T, B, 300] uint8,
+        stats [2 + K * K] int32, loss [1]) — what yolat_metrics_append takes (evaluation.EpochMetrics)"""
+        lay, out = self._lay, self._out
+        B, K, T = lay["B"], lay["K"], lay["T"]
+        det = out[lay["det"]:lay["det"] + B * ops.MAX_DET * 6].view(torch.float32).view(B, ops.MAX_DET, 6)
+        tp = out[lay["tp"]:lay["sel"]].view(torch.uint8)[:T * B * ops.MAX_DET].view(T, B, ops.MAX_DET)
+        return (det, out[:B], tp, out[lay["stats"]:lay["stats"] + 2 + K * K],
+                out[lay["loss"]:lay["loss"] + 1].view(torch.float32))
+
     def _fallback(self):
         from .evaluation import evaluate_batch, confusion_counts
         data, slices = self.data, self.slices
@@ -629,8 +639,12 @@ class SparseCADGCN(nn.Module):
         done.record(cur)
         hold = (logits, bb, labels, t)                   # what the launches read: alive as long as the handle's record
         out._yolat_keep = hold
-        return EvalHandle(self, data, slices, out, lay, sel, pred, ws, done, cur, gt_labels.tolist(),
-                          dict(conf_thres=conf_thres, iou_thres=iou_thres, classifier=cls, iou_thresholds=iou_thresholds))
+        h = EvalHandle(self, data, slices, out, lay, sel, pred, ws, done, cur, gt_labels.tolist(),
+                       dict(conf_thres=conf_thres, iou_thres=iou_thres, classifier=cls, iou_thresholds=iou_thresholds))
+        # the uploaded target classes [G] fp32, for the epoch record (evaluation.EpochMetrics)
+        g_at = (addr["gt_label"] - t._keep.data_ptr()) // 4
+        h.gt_label = t._keep[g_at:g_at + G].view(torch.float32)
+        return h
 
     def _predict_one_submission(self, data, slices):
         """One forward over the whole batch, then yolat_predict_select / yolat_predict_gather (csrc/subgraph.hip): in eval

@@ -173,7 +173,215 @@ def evaluate_batch_async(model, data, slices, fixup=True, **kw):
     return model.evaluate_submit(data, slices, **kw)
 
 
+class EpochMetrics(object):
+    """The metrics of an evaluation epoch accumulated ON THE DEVICE (csrc/metrics.hip): every ``EvalHandle`` is appended to
+    one epoch record without being read, and ``result()`` brings the epoch home in one copy.
+
+    ``EpochMetrics(model, iou_thresholds, capacity_images=1024)``: 1 to 32 thresholds (one bit of a slot's mask each), a
+    model of 2 to 32 classes.  The record starts at ``capacity_images`` images and grows — allocate, device copy, swap, no
+    read — when the epoch holds more.
+
+    ``add(handle)``  takes the handle WITHOUT calling its ``result()``: one ``yolat_metrics_append`` launch on the handle's
+        stream behind its last launch, slots and batch number assigned here on the host (so the record is the same for one
+        stream and for four), an event, and a non-blocking copy of the batch's two flags into pinned memory.  No blocking
+        call.  Later calls poll the events (a query, never a wait) and let go of every handle whose flags arrived as
+        zero; a handle with a flag set is kept for ``result()``.  Returns the batch's number.
+    ``result()``  the current stream waits for every stream's last append; ONE flags read if a handle is still pending; a
+        batch whose forward flagged its input raises what ``ops.check_status_word`` raises; a batch with the tree flag goes
+        through ``EvalHandle._fallback`` and its outcome is uploaded into the batch's reserved slots
+        (``ops.metrics_append_host``); then ``yolat_metrics_finalize`` and ONE device -> host copy.  Returns the report
+        of ``test()`` — ``iou_thresholds``, ``map`` (per threshold the mean AP over the classes with targets, 0.0 without
+        any), ``map_all`` (their sum / 10, as the reference divides), ``top1``, ``loss``, ``confusion`` — plus ``ap``
+        [T, K], ``p``, ``r``, ``classes`` (the ids with targets), ``n_gt`` and ``n_p`` [K]; None when no batch was added.
+        A target class that is not an integer in [0, K) raises ValueError.
+    Score ties keep epoch order (image, then detection rank): ``np.argsort(-conf, kind="stable")``."""
+
+    MIN_BATCH_CAP = 256
+
+    def __init__(self, model, iou_thresholds, capacity_images=1024):
+        ths = np.asarray(iou_thresholds, dtype=np.float64).reshape(-1)
+        T, K = int(ths.shape[0]), int(getattr(model, "n_classes", 0))
+        if not 1 <= T <= ops.METRICS_MAX_THRESHOLDS:
+            raise ValueError("EpochMetrics takes 1 to %d IoU thresholds, got %d" % (ops.METRICS_MAX_THRESHOLDS, T))
+        if not 2 <= K <= ops.METRICS_MAX_CLASSES:
+            raise ValueError("EpochMetrics takes a model of 2 to %d classes, got %d" % (ops.METRICS_MAX_CLASSES, K))
+        if int(capacity_images) < 1:
+            raise ValueError("EpochMetrics needs capacity_images >= 1")
+        self.model, self.iou_thresholds, self.T, self.K = model, ths, T, K
+        self.capacity_images = int(capacity_images)
+        from collections import deque
+        self._rec, self._retired, self._pinned = None, [], None
+        self._n_images = self._n_batches = 0
+        self._pending, self._flagged = deque(), []
+        self._last = {}              # raw stream -> (stream object, event behind its last append)
+        self._ready, self._ready_id, self._seen = None, 0, {}     # the record's last reset / growth and who waited for it
+        self._result = None
+        self.grown = 0
+
+    # -- the record ------------------------------------------------------------------------------
+    def _reserve(self, n_images, n_batches, device, stream):
+        """a record that holds n_images / n_batches, made or grown on `stream`; the other streams wait for it in add()"""
+        rec = self._rec
+        if rec is not None and n_images <= rec.capacity_images and n_batches <= rec.batch_cap:
+            return rec
+        if rec is None:
+            cap, bcap = max(self.capacity_images, n_images), max(self.MIN_BATCH_CAP, n_batches)
+            new = ops.metrics_record(cap, self.K, bcap, device)
+        else:
+            cap, bcap = rec.capacity_images, rec.batch_cap
+            while cap < n_images:
+                cap *= 2
+            while bcap < n_batches:
+                bcap *= 2
+            for s, ev in self._last.values():          # every append into the old record is in front of the copy
+                stream.wait_event(ev)
+            new = ops.metrics_grow(rec, cap, bcap)
+            self._retired.append(rec)                  # alive until result(): other streams may still be writing it
+            self.grown += 1
+        if self._pinned is None or self._pinned.shape[0] < new.batch_cap:
+            self._pinned = torch.zeros((new.batch_cap, 2), dtype=torch.int32).pin_memory()
+        self._ready = torch.cuda.Event()
+        self._ready.record(stream)
+        self._ready_id += 1
+        self._seen = {}
+        self._rec = new
+        return new
+
+    def _poll(self):
+        while self._pending and self._pending[0][3].query():
+            h, b, base, _, flags = self._pending.popleft()
+            if flags[b, 0] != 0 or flags[b, 1] != 0:
+                self._flagged.append((h, b, base, int(flags[b, 1])))
+
+    def add(self, handle):
+        from .architecture import EvalHandle
+        if not isinstance(handle, EvalHandle):
+            raise TypeError("EpochMetrics.add takes the EvalHandle of evaluate_submit / evaluate_batch_async")
+        if self._result is not None:
+            raise RuntimeError("EpochMetrics.result() has closed this epoch: make a new EpochMetrics for the next one")
+        lay = handle._lay
+        if lay["T"] != self.T or lay["K"] != self.K:
+            raise ValueError("the handle was submitted with %d thresholds and %d classes, the epoch holds %d and %d"
+                             % (lay["T"], lay["K"], self.T, self.K))
+        self._poll()
+        B, stream = lay["B"], handle._stream
+        key = stream.cuda_stream
+        base, b = self._n_images, self._n_batches
+        with torch.cuda.stream(stream):
+            rec = self._reserve(base + B, b + 1, handle._out.device, stream)
+            if self._seen.get(key) != self._ready_id:
+                stream.wait_event(self._ready)
+                rec.buf.record_stream(stream)
+                self._seen[key] = self._ready_id
+            det, det_count, tp, stats, loss = handle.device_record()
+            ops.metrics_append(rec, det, det_count, tp, stats, loss, handle.gt_label, handle.sel, base, b)
+            pinned = self._pinned
+            pinned[b].copy_(rec.batch_flags()[b], non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record(stream)
+        self._n_images, self._n_batches = base + B, b + 1
+        self._last[key] = (stream, ev)
+        self._pending.append((handle, b, base, ev, pinned.numpy()))
+        return b
+
+    def _upload_fallback(self, handle, b, base):
+        """the synchronous evaluation of a batch whose tree was flagged -> its reserved slots"""
+        res = handle._fallback()
+        lay = handle._lay
+        B, K, T = lay["B"], lay["K"], lay["T"]
+        det = np.zeros((B, ops.MAX_DET, 6), dtype=np.float32)
+        cnt = np.zeros(B, dtype=np.int32)
+        tp = np.zeros((T, B, ops.MAX_DET), dtype=np.uint8)
+        for t in range(T):
+            for i, (flags, scores, labels) in enumerate(res["sample_metrics"][t]):
+                k = len(flags)
+                cnt[i] = k
+                det[i, :k, 4], det[i, :k, 5] = np.asarray(scores, dtype=np.float32), np.asarray(labels, dtype=np.float32)
+                tp[t, i, :k] = np.asarray(flags) != 0
+        stats = np.concatenate([[res["n_true"], res["n_total"]], np.asarray(res["confusion"]).reshape(-1)]).astype(np.int32)
+        dev = handle._out.device
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+        ops.metrics_append_host(self._rec, up(det), up(cnt), up(tp), up(stats),
+                                up(np.asarray([res["loss"]["loss"]], dtype=np.float32)),
+                                up(np.asarray(res["labels"], dtype=np.float32).reshape(-1)), base, b)
+
+    def result(self):
+        if self._result is not None:
+            return self._result
+        if self._n_batches == 0:
+            return None
+        cur = ops.current_stream_object()
+        for s, ev in self._last.values():
+            cur.wait_event(ev)
+        cur.wait_event(self._ready)
+        rec, nb = self._rec, self._n_batches
+        rec.buf.record_stream(cur)
+        self._poll()
+        flagged = list(self._flagged)
+        if self._pending:
+            flags = ops.d2h(rec.batch_flags()[:nb]).numpy()           # the one flags read
+            flagged += [(h, b, base, int(flags[b, 1])) for h, b, base, _, _ in self._pending if flags[b].any()]
+        self._pending.clear()
+        for h, b, base, status in sorted(flagged, key=lambda e: e[1]):
+            if status != 0:
+                ops.check_status_word(torch.tensor([status], dtype=torch.int32))   # raises for every flag a forward sets
+            self._upload_fallback(h, b, base)        # the device left the batch's slots unfilled
+        self._flagged = []
+        out = ops.metrics_finalize(rec, self._n_images, nb, self.T)
+        m = ops.metrics_unpack(ops.d2h(out).numpy(), self.T, self.K, nb)     # the one copy that brings the epoch home
+        self._retired = []
+        if m["status"] & ops.METRICS_BAD_GT_LABEL:
+            raise ValueError("gt_labels hold a class id that is not an integer in [0, %d) (YOLAT_METRICS_BAD_GT_LABEL)"
+                             % self.K)
+        K = self.K
+        classes = np.flatnonzero(m["n_gt"] > 0)
+        maps = [float(np.mean(m["ap"][t, classes])) if len(classes) else 0.0 for t in range(self.T)]
+        stats = m["stats"]
+        rep = {"iou_thresholds": self.iou_thresholds, "map": maps, "top1": int(stats[0]) / max(int(stats[1]), 1),
+               "loss": {"loss": m["loss_mean"], "loss_cls": m["loss_mean"]},
+               "confusion": stats[2:].reshape(K, K).astype(np.int64), "map_all": float(np.sum(maps) / 10),
+               "ap": m["ap"], "p": m["p"], "r": m["r"], "classes": classes.astype("int32"), "n_gt": m["n_gt"],
+               "n_p": m["n_p"], "batch_flags": m["batch_flags"]}
+        self._result = rep
+        return rep
+
+
 MAX_EVAL_STREAMS = 4
+
+
+def _submissions(model, batches, streams, kw):
+    """The handles of ``evaluate_stream``'s three ways to submit — current stream, a DeviceLoader under one stream, batch i
+    under streams[i % n] — in batch order; nothing is read (the ``metrics=`` form of evaluate_stream)."""
+    from .data import DeviceLoader
+    if streams is None:
+        for data, slices in batches:
+            yield evaluate_batch_async(model, data, slices, **kw)
+    elif isinstance(batches, DeviceLoader):
+        entry = torch.cuda.Event()
+        entry.record(ops.current_stream_object())
+        streams[0].wait_event(entry)
+        it = iter(batches)
+        while True:
+            with torch.cuda.stream(streams[0]):
+                nxt = next(it, None)
+                if nxt is None:
+                    break
+                h = evaluate_batch_async(model, nxt[0], nxt[1], **kw)
+            yield h
+    else:
+        home = ops.current_stream_object()
+        entry = torch.cuda.Event()
+        entry.record(home)
+        for s in streams:
+            s.wait_event(entry)
+        for i, (data, slices) in enumerate(batches):
+            s = streams[i % len(streams)]
+            drawn = torch.cuda.Event()
+            drawn.record(home)
+            s.wait_event(drawn)
+            with torch.cuda.stream(s):
+                h = evaluate_batch_async(model, data, slices, **kw)
+            yield h
 
 
 def evaluate_stream(model, batches, depth=4, streams=None, **kw):
@@ -187,10 +395,14 @@ def evaluate_stream(model, batches, depth=4, streams=None, **kw):
     recorded there after its batch was drawn (a batch collated while the generator runs is complete before another stream
     reads it).  A handle's tensors are allocated under its stream and only host arrays leave the generator.
     Over a DeviceLoader: ``depth <= slots - 2`` as for ``detect_stream``, and one stream at the most — the loader's ring
-    belongs to the stream its batches are drawn on (ValueError otherwise)."""
+    belongs to the stream its batches are drawn on (ValueError otherwise).
+    ``metrics`` (a keyword of its own among ``kw``, default None): an ``EpochMetrics`` — every submitted handle goes to ``metrics.add`` instead of being read, and the
+    generator yields the batch's number in the epoch; ``metrics.result()`` then is the epoch's report.  The same loader and
+    stream rules; nothing limits the batches in flight but the polling of ``add``."""
     from collections import deque
     from .data import DeviceLoader
     depth = int(depth)
+    metrics = kw.pop("metrics", None)
     if depth < 1:
         raise ValueError("evaluate_stream needs depth >= 1")
     if streams is not None:
@@ -208,6 +420,12 @@ def evaluate_stream(model, batches, depth=4, streams=None, **kw):
             raise ValueError("evaluate_stream(depth=%d) over a DeviceLoader needs slots >= depth + 2, the loader has %d"
                              % (depth, slots))
     kw.setdefault("fixup", False)
+    if metrics is not None:
+        if not isinstance(metrics, EpochMetrics):
+            raise TypeError("evaluate_stream(metrics=) takes an EpochMetrics")
+        for h in _submissions(model, batches, streams, kw):
+            yield metrics.add(h)
+        return
     flying = deque()
     if streams is None:
         for data, slices in batches:
@@ -255,6 +473,12 @@ def _async_eval_applies(model, criterion, opt):
         2 <= int(getattr(model, "n_classes", 0)) <= 32
 
 
+def _device_metrics_apply(model, criterion, opt, steps):
+    """opt.device_metrics takes effect where the asynchronous evaluation does and a slot's mask holds the thresholds"""
+    return bool(getattr(opt, "device_metrics", False)) and _async_eval_applies(model, criterion, opt) and \
+        1 <= steps <= ops.METRICS_MAX_THRESHOLDS
+
+
 def _eval_streams(opt):
     n = getattr(opt, "eval_streams", None)
     if n is None:
@@ -270,7 +494,11 @@ def test(model, test_loader, criterion, opt):
     ``opt.async_eval`` (absent: the loop below as it always was): the batches go through ``evaluate_stream`` with
     ``opt.eval_depth`` (default 4) in flight on ``opt.eval_streams`` streams (a count or a list; default the current
     stream) when the criterion is DetectionLoss — same value, same report, plus ``report["confusion"]``, the [K, K]
-    counts summed over the batches."""
+    counts summed over the batches.
+    ``opt.device_metrics`` (off by default; only where ``opt.async_eval`` applies and ``map_step <= 32``): no handle is
+    read, the epoch is accumulated on the device (``EpochMetrics``, ``opt.metrics_capacity`` images to start with) and AP
+    per class and threshold is computed there — one device -> host copy per epoch; the same keys in the report.  Equal
+    scores keep epoch order there, where numpy's argsort leaves their order open."""
     model.eval()
     steps = int(getattr(opt, "map_step", 10))
     ths = np.linspace(0.5, 0.95, steps)
@@ -279,6 +507,17 @@ def test(model, test_loader, criterion, opt):
     confusion = None
     classifier = getattr(opt, "classifier", "softmax")
     with torch.no_grad():
+        if _device_metrics_apply(model, criterion, opt, steps):
+            acc = EpochMetrics(model, ths, capacity_images=int(getattr(opt, "metrics_capacity", 1024)))
+            for _ in evaluate_stream(model, test_loader, depth=int(getattr(opt, "eval_depth", 4)), streams=_eval_streams(opt),
+                                     metrics=acc, fixup=True, classifier=classifier, iou_thresholds=ths):
+                pass
+            rep = acc.result()
+            if rep is None:
+                return None
+            opt.test_report = {k: rep[k] for k in ("iou_thresholds", "map", "top1", "loss", "confusion", "map_all")}
+            opt.test_value = rep["map"][-1]
+            return opt.test_value
         if _async_eval_applies(model, criterion, opt):
             reps = evaluate_stream(model, test_loader, depth=int(getattr(opt, "eval_depth", 4)), streams=_eval_streams(opt),
                                    fixup=True, classifier=classifier, iou_thresholds=ths)

@@ -1448,3 +1448,152 @@ def detect_match(det, det_count, gt_boxes, gt_labels, gt_ptr, thresholds, out=No
     check(lib.yolat_detect_match(dp, _i(det_count, torch.int32, "det_count"), B, gp, lp, G, _i(gt_ptr, torch.int32, "gt_ptr"),
                                  tp_, T, out.data_ptr(), _stream()), "yolat_detect_match")
     return out
+
+
+# ---------------------------------------------------------------------------------------------
+# epoch metrics (csrc/metrics.hip)
+# ---------------------------------------------------------------------------------------------
+METRICS_BAD_GT_LABEL = 1
+METRICS_MAX_THRESHOLDS = 32
+METRICS_MAX_CLASSES = 32
+
+
+class MetricsRecord(object):
+    """The epoch record of csrc/metrics.hip: ONE uint8 device buffer ``buf`` of yolat_metrics_record_bytes(capacity_images,
+    K, batch_cap) bytes and the byte offsets of its eight sections (include/yolat_hip.h: conf | cls | tp | gt_hist | stats |
+    loss | batch_flags | status)."""
+
+    __slots__ = ("buf", "capacity_images", "K", "batch_cap", "offsets", "nbytes")
+
+    def __init__(self, buf, capacity_images, K, batch_cap):
+        offs = (ctypes.c_int64 * 8)()
+        n = int(lib.yolat_metrics_record_bytes(int(capacity_images), int(K), int(batch_cap), offs))
+        if n == 0:
+            raise ValueError("a metrics record of %d images, %d classes and %d batches is outside what csrc/metrics.hip "
+                             "supports (images * 300 <= 2^27, K in [2, 32], batches <= 2^24)" % (capacity_images, K, batch_cap))
+        if buf.dtype != torch.uint8 or buf.dim() != 1 or buf.numel() < n or not buf.is_contiguous():
+            raise ValueError("the record buffer must be a contiguous uint8 tensor of at least %d bytes" % n)
+        self.buf, self.capacity_images, self.K, self.batch_cap = buf, int(capacity_images), int(K), int(batch_cap)
+        self.offsets, self.nbytes = [int(v) for v in offs], n
+
+    def section_bytes(self):
+        S, K, bc = 300 * self.capacity_images, self.K, self.batch_cap
+        return [4 * S, 4 * S, 4 * S, 8 * K, 8 * (2 + K * K), 4 * bc, 8 * bc, 4]
+
+    def section(self, i, nbytes=None):
+        n = self.section_bytes()[i] if nbytes is None else int(nbytes)
+        return self.buf[self.offsets[i]:self.offsets[i] + n]
+
+    def batch_flags(self):
+        """int32 view [batch_cap, 2] of the flags section: (sel[1], sel[2]) of every batch"""
+        return self.section(6).view(torch.int32).view(self.batch_cap, 2)
+
+    def _ptr(self):
+        if not self.buf.is_cuda:
+            raise RuntimeError("the metrics record must be a CUDA (ROCm) tensor — the yolat HIP path has no CPU fallback")
+        return self.buf.data_ptr()
+
+
+def metrics_record(capacity_images, K, batch_cap, device):
+    """A fresh (reset) epoch record on ``device``; the reset is enqueued on the current stream."""
+    if torch.device(device).type != "cuda":
+        raise RuntimeError("the metrics record lives on a CUDA (ROCm) device — the yolat HIP path has no CPU fallback")
+    n = int(lib.yolat_metrics_record_bytes(int(capacity_images), int(K), int(batch_cap), None))
+    rec = MetricsRecord(torch.empty(max(n, 1), dtype=torch.uint8, device=device), capacity_images, K, batch_cap)
+    check(lib.yolat_metrics_reset(rec._ptr(), rec.capacity_images, rec.K, rec.batch_cap, _stream()), "yolat_metrics_reset")
+    return rec
+
+
+def metrics_grow(rec, capacity_images, batch_cap):
+    """A larger record with ``rec``'s content: allocate, reset, device copies of the sections — all on the current stream,
+    nothing read back.  The caller orders the streams that still write ``rec`` in front of this one and swaps."""
+    if capacity_images < rec.capacity_images or batch_cap < rec.batch_cap:
+        raise ValueError("metrics_grow only grows")
+    rec._ptr()
+    new = metrics_record(capacity_images, rec.K, batch_cap, rec.buf.device)
+    for i, n in enumerate(rec.section_bytes()):
+        new.section(i, n).copy_(rec.section(i, n))
+    return new
+
+
+def _metrics_batch(det, det_count, tp, stats, loss, gt_labels, K):
+    dp = _f(det, "det")
+    if det.dim() != 3 or tuple(det.shape[1:]) != (MAX_DET, 6) or not det.is_contiguous() or det.shape[0] < 1:
+        raise ValueError("metrics_append expects det [B, 300, 6]")
+    B = int(det.shape[0])
+    cp, sp, lp = _i(det_count, torch.int32, "det_count"), _i(stats, torch.int32, "stats"), _f(loss, "loss")
+    if not tp.is_cuda:
+        raise RuntimeError("tp must be a CUDA (ROCm) tensor — the yolat HIP path has no CPU fallback")
+    if tp.dtype != torch.uint8 or tp.dim() != 3 or tuple(tp.shape[1:]) != (B, MAX_DET) or not tp.is_contiguous():
+        raise ValueError("metrics_append expects tp [T, B, 300] uint8")
+    T = int(tp.shape[0])
+    if not 1 <= T <= METRICS_MAX_THRESHOLDS:
+        raise ValueError("metrics_append takes 1 to 32 thresholds, one bit of a slot's mask each")
+    if tuple(det_count.shape) != (B,) or tuple(stats.shape) != (2 + K * K,) or loss.numel() < 1:
+        raise ValueError("metrics_append expects det_count [B], stats [2 + K * K] and loss [1]")
+    gp = _f(gt_labels, "gt_labels")
+    if gt_labels.dim() != 1:
+        raise ValueError("metrics_append expects gt_labels [G]")
+    G = int(gt_labels.shape[0])
+    return dp, cp, tp.data_ptr(), sp, lp, (gp if G > 0 else None), G, B, T
+
+
+def metrics_append(rec, det, det_count, tp, stats, loss, gt_labels, sel, image_base, batch_index):
+    """yolat_metrics_append (csrc/metrics.hip): ONE launch on the current stream that appends what yolat_evaluate wrote for
+    a batch — det [B, 300, 6], det_count [B], tp [T, B, 300] uint8, stats [2 + K * K] int32, loss [1], sel — and the batch's
+    target classes gt_labels [G] fp32 to the record: the images take the slots of image_base .. image_base + B - 1, the
+    batch is number batch_index.  sel[1] / sel[2] are read on the device; nothing is read back."""
+    rp = rec._ptr()
+    a = _metrics_batch(det, det_count, tp, stats, loss, gt_labels, rec.K)
+    if sel is None or sel.dim() != 1 or sel.numel() < 4:
+        raise ValueError("metrics_append expects the sel record of yolat_predict_select (at least its four head words)")
+    check(lib.yolat_metrics_append(rp, rec.capacity_images, rec.K, rec.batch_cap, a[0], a[1], a[2], a[3], a[4], a[5], a[6],
+                                   _i(sel, torch.int32, "sel"), a[7], a[8], int(image_base), int(batch_index), _stream()),
+          "yolat_metrics_append")
+
+
+def metrics_append_host(rec, det, det_count, tp, stats, loss, gt_labels, image_base, batch_index):
+    """yolat_metrics_append_host: ``metrics_append`` for a batch the HOST evaluated (the synchronous fall-back) and
+    uploaded — no sel, the batch's flags stay as the device stored them."""
+    rp = rec._ptr()
+    a = _metrics_batch(det, det_count, tp, stats, loss, gt_labels, rec.K)
+    check(lib.yolat_metrics_append_host(rp, rec.capacity_images, rec.K, rec.batch_cap, a[0], a[1], a[2], a[3], a[4], a[5],
+                                        a[6], a[7], a[8], int(image_base), int(batch_index), _stream()),
+          "yolat_metrics_append_host")
+
+
+def metrics_finalize(rec, n_images, n_batches, T):
+    """yolat_metrics_finalize over the first n_images images and n_batches batches of the record -> the out block as ONE
+    int64 device tensor (``metrics_unpack`` names its parts on the host).  Nothing is read back."""
+    rp = rec._ptr()
+    n_images, n_batches, T = int(n_images), int(n_batches), int(T)
+    need = int(lib.yolat_metrics_finalize_work_bytes(n_images, T, rec.K))
+    nout = int(lib.yolat_metrics_out_bytes(T, rec.K, n_batches))
+    if need == 0 or nout == 0:
+        raise ValueError("metrics_finalize supports 1 to 32 thresholds, K in [2, 32] and 1 to 447392 images")
+    dev = rec.buf.device
+    work = torch.empty(need, dtype=torch.uint8, device=dev)
+    out = torch.empty(nout // 8, dtype=torch.int64, device=dev)
+    check(lib.yolat_metrics_finalize(rp, rec.capacity_images, rec.K, rec.batch_cap, n_images, n_batches, T, out.data_ptr(),
+                                     nout, work.data_ptr(), need, _stream()), "yolat_metrics_finalize")
+    return out
+
+
+def metrics_unpack(words, T, K, n_batches):
+    """The host copy (numpy int64) of ``metrics_finalize``'s block -> dict: ap / p / r [T, K] float64, n_gt / n_p [K],
+    loss_mean, stats [2 + K * K], status, batch_flags [n_batches, 2] int32."""
+    import numpy as np
+    w = np.ascontiguousarray(words, dtype=np.int64)
+    TK, o = T * K, 0
+    out = {}
+    for name in ("ap", "p", "r"):
+        out[name] = w[o:o + TK].view(np.float64).reshape(T, K).copy()
+        o += TK
+    out["n_gt"], out["n_p"] = w[o:o + K].copy(), w[o + K:o + 2 * K].copy()
+    o += 2 * K
+    out["loss_mean"] = float(w[o:o + 1].view(np.float64)[0])
+    out["stats"] = w[o + 1:o + 3 + K * K].copy()
+    o += 3 + K * K
+    out["status"] = int(w[o])
+    out["batch_flags"] = w[o + 1:o + 1 + n_batches].view(np.int32).reshape(n_batches, 2).copy()
+    return out
