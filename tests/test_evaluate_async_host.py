@@ -165,3 +165,43 @@ def test_async_eval_is_taken_only_for_detection_loss_and_supported_class_counts(
     assert not evaluation._async_eval_applies(M(), Other(opt), opt)    # any other criterion: the synchronous loop
     M.n_classes = 33
     assert not evaluation._async_eval_applies(M(), crit, opt)
+
+
+def test_evaluation_record_layout_is_the_one_the_kernels_were_given():
+    """int32 offsets of the EvalHandle's record at B=2, K=3, T=2, R_cap=5, written out by hand from
+    det_count [B] | stats [2 + K K] | loss | y_pred [R_cap] | y_true [R_cap] | det [B 300 6] | tp [T B 300 bytes] | sel"""
+    from yolat_vectorgraphicsrecognition_amd import submit
+    assert yv.ops.sel_words(2, 5) == 12 and yv.ops.sel_words(1, 0) == 6
+    rec = submit.EvalRecord(2, 3, 2, 5)
+    assert rec.off == {"det_count": 0, "stats": 2, "loss": 13, "y_pred": 14, "y_true": 19, "det": 24, "tp": 3624, "sel": 3924}
+    assert rec.copy == 3928 and rec.words == 3936
+    host = np.arange(rec.copy, dtype=np.int32)
+    det, det_count, tp, stats, loss = rec.views(host)
+    assert det.shape == (2, 300, 6) and det.dtype == np.float32 and det.view(np.int32)[0, 0, 0] == 24
+    assert tp.shape == (2, 2, 300) and tp.dtype == np.uint8 and tp[0, 0, :4].tolist() == [0x28, 0x0E, 0, 0]      # word 3624
+    assert det_count.tolist() == [0, 1] and stats.tolist() == list(range(2, 13)) and loss.view(np.int32).tolist() == [13]
+    total, flag, status, image_off, rows = yv.ops.sel_split(np.arange(12), 2)
+    assert (total, flag, status) == (0, 1, 2) and image_off.tolist() == [4, 5, 6] and rows.tolist() == [7, 8, 9, 10, 11]
+
+
+@pytest.mark.parametrize("depth,want", [
+    (2, "s0 s1 r0 s2 r1 s3 r2 s4 r3 r4"), (1, "s0 r0 s1 r1 s2 r2 s3 r3 s4 r4"), (7, "s0 s1 s2 s3 s4 r0 r1 r2 r3 r4")])
+def test_in_flight_reads_the_oldest_handle_once_depth_are_flying(depth, want):
+    from yolat_vectorgraphicsrecognition_amd import evaluation
+    log = []
+
+    class Handle(object):
+        def __init__(self, i):
+            self.i = i
+
+        def result(self):
+            log.append("r%d" % self.i)
+            return self.i
+
+    def submitted():
+        for i in range(5):
+            log.append("s%d" % i)
+            yield Handle(i)
+
+    assert list(evaluation._in_flight(submitted(), depth)) == [0, 1, 2, 3, 4]
+    assert " ".join(log) == want

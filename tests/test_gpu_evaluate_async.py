@@ -112,6 +112,27 @@ def test_result_equals_evaluate_batch_with_device_post(form):
     _same_rep(model.evaluate_submit(data, slices).result(), want, K)
 
 
+def test_detect_submit_and_evaluate_submit_leave_the_same_selection_and_detections():
+    """the two submissions share their front half and yolat_detect: on one batch, with evaluate_submit's thresholds, the
+    record of the selection up to its last row, the detection counts and the detections are the same bytes"""
+    yv = _yv()
+    K = 17
+    model = _model(yv, dict(n_classes=K, n_blocks=2, n_blocks_out=2), 4)
+    data, slices = yv.collate_to_device(_eval_items(yv, 81, 2, n_classes=K, num_proposals=40, nodes_hi=12))
+    _shift_last_class(model, data, slices, "half")
+    hd = model.detect_submit(data, slices, conf_thres=0.0, iou_thres=0.5)
+    he = model.evaluate_submit(data, slices)
+    torch.cuda.synchronize()
+    total = int(hd.sel[0])
+    words = yv.ops.sel_words(2, total)
+    assert 0 < len(data.roots) <= total <= hd.sel.numel() - yv.ops.sel_words(2, 0)      # every root, children of some
+    assert _bits(hd.sel[:words].cpu()) == _bits(he.sel[:words].cpu())
+    det, det_count = he.device_record()[:2]
+    assert int(det_count.sum()) > 0
+    assert _bits(hd.det_count.cpu()) == _bits(det_count.cpu()) and _bits(hd.det.cpu()) == _bits(det.cpu())
+    hd.result(), he.result()
+
+
 # ---------------------------------------------------------------------------------------------
 # 4. the rows kernel at workgroup edges, per element against DetectionLoss / torch on the gathered rows
 # ---------------------------------------------------------------------------------------------
@@ -119,8 +140,8 @@ def _select(yv, model, data, slices, logits, bbox):
     """yolat_predict_select on `logits` -> the sel record (device int32) and R_cap"""
     import ctypes
     from yolat_vectorgraphicsrecognition_amd._lib import lib, check
-    ep, se, sc, bp, N, E, P, dev = model._predict_operands(data, logits, bbox)
-    t, ft, _ = model._predict_tree(data, slices, dev)
+    ep, se, sc, bp, N, E, P, dev = yv.submit.predict_operands(model, data, logits, bbox)
+    t, ft, _ = yv.submit.predict_tree(data, slices, dev)
     R, Ctot, B = ft["R"], ft["Ctot"], ft["B"]
     sel = torch.empty(4 + B + 1 + R + Ctot, dtype=torch.int32, device=dev)
     ws = torch.empty(int(lib.yolat_predict_select_workspace_bytes(N, P, R)) + 16, dtype=torch.uint8, device=dev)

@@ -8,6 +8,7 @@ Layout
     engine.py        hand-scheduled forward / backward of the model blocks
     nn_modules.py    gcn_lib.sparse mirror: MultiSeq, MLP, GraphConv, ResBlock
     architecture.py  cad_recognition/architecture3cc_rpn_gp_iter2 mirror: SparseCADGCN, ...
+    submit.py        predict in one submission, detect_submit / evaluate_submit and their handles (behind SparseCADGCN's methods)
     trainer.py       flat-buffer Adam + data-parallel step (RCCL all-reduce of one gradient bucket)
     data.py          Data bag, collate / offset fix-up, synthetic Bezier-graph generators
     augment.py       training augmentation (graph_dict3.random_transfer + update_bbox) on host items / device batches
@@ -24,7 +25,7 @@ from .postprocess import (non_max_suppression, get_batch_statistics, ap_per_clas
                           non_max_suppression_batched, get_batch_statistics_batched)
 from .evaluation import evaluate_batch, detect_batch, detect_batch_async, detect_stream, test as evaluate  # noqa: F401
 from .evaluation import evaluate_batch_async, evaluate_stream, confusion_counts, EpochMetrics  # noqa: F401
-from .architecture import DetectHandle, EvalHandle  # noqa: F401
+from .submit import DetectHandle, EvalHandle  # noqa: F401
 from .trainer import (FlatParams, FlatAdam, Trainer, shard_graph_ids, allreduce_mean_, broadcast_parameters,  # noqa: F401
                       load_reference_checkpoint)
 

@@ -12,11 +12,14 @@ arch:107-115), derives the CSR / segment structure on the device (ops.build_grap
 hand-scheduled HIP sequence of engine.model_fwd; in training mode the result carries a custom
 autograd node whose backward is engine.model_bwd.  Module attribute names reproduce the reference
 state_dict keys so reference checkpoints load.
+
+What the reference's file does not have — ``predict`` in one submission, ``detect_submit`` / ``evaluate_submit`` and their
+handles — lives in submit.py; the methods here carry the signatures and the documentation and delegate.
 """
 import torch
 from torch import nn
 
-from . import engine, ops
+from . import engine, ops, submit
 from .engine import GradSink
 from .nn_modules import MultiSeq, MLP, GraphConv, ResBlock, scatter, graph_for
 from .data import Data
@@ -117,148 +120,6 @@ class _SigmoidFn(torch.autograd.Function):
 # predict(): one forward over the whole batch + integer selection on the device (csrc/subgraph.hip, yolat_predict_select);
 # False: always the two-pass sub-graph extraction (module flag; the tests run both)
 PREDICT_ONE_SUBMISSION = True
-
-_PREPARED_BATCH = ("predict() cuts sub-graphs out of the raw edge list: batches from collate_to_device(csr=True) "
-                   "carry the prepared CSR only and support forward() — collate with csr=False for predict()")
-
-
-class DetectHandle(object):
-    """One batch of ``SparseCADGCN.detect_submit`` in flight.  It owns the device tensors of its batch — ``sel`` (the
-    record of yolat_predict_select), ``pred`` [R + Ctot, 4 + K], ``det`` [B, 300, 6], ``det_count`` [B] and the workspace —
-    allocated on the submitting stream and released with the handle, and keeps the batch for the fall-back.
-
-    ``ready()``   the event behind the batch's last launch has completed (a query, no wait)
-    ``result()``  the list of B device tensors [k, 6] ``evaluation.detect_batch`` returns; ONE device -> host read
-                  (ops.d2h) of sel[0:4] and the B detection counts.  A forward that flagged its input raises what
-                  ``check_last_status`` raises; a tree that is not made of its proposals' ranges (sel[1]) goes through the
-                  synchronous ``detect_batch`` on the retained batch — a DeviceLoader batch is collated again from its
-                  host items, its ring slot may have been rewritten since."""
-
-    def __init__(self, model, data, slices, out, det, det_count, sel, pred, workspace, event, kw):
-        self.model, self.data, self.slices, self.kw = model, data, slices, kw
-        self._out, self.det, self.det_count, self.sel, self.pred, self.workspace = out, det, det_count, sel, pred, workspace
-        self.event = event
-        self._result = None
-
-    def ready(self):
-        return bool(self.event.query())
-
-    def result(self):
-        if self._result is not None:
-            return self._result
-        B = int(self.det_count.shape[0])
-        n_det = self.det.numel()
-        host = ops.d2h(self._out[n_det:n_det + B + 4]).tolist()     # det_count [B] | sel[0:4]; stream order: behind the NMS
-        cnt, flag, status = host[:B], host[B + 1], host[B + 2]
-        if status != 0:
-            ops.check_status_word(torch.tensor([status], dtype=torch.int32))      # raises for every flag a forward sets
-        if flag != 0:
-            res = self._fallback()
-        else:
-            res = [self.det[i, :k] for i, k in enumerate(cnt)]
-        self._result = res
-        self._release()
-        return res
-
-    def _fallback(self):
-        from .evaluation import detect_batch
-        data, slices = self.data, self.slices
-        st = data.__dict__.get("_lazy") if hasattr(data, "__dict__") else None
-        if st is not None:
-            from .data import collate_to_device
-            data, slices = collate_to_device(st.items, device=self.det.device)
-        return detect_batch(self.model, data, slices, fixup=False, **self.kw)
-
-    def _release(self):
-        self.data = self.slices = self.pred = self.workspace = None
-
-
-class EvalHandle(object):
-    """One batch of ``SparseCADGCN.evaluate_submit`` in flight.  It owns the device record of its batch — ONE allocation
-    ``det_count | stats | loss | y_pred | y_true | det | tp | sel`` plus ``pred`` and the workspace, allocated on the
-    submitting stream and released with the handle — and keeps the batch for the fall-back.  The record is per handle, not
-    a global accumulator: a batch that takes the fall-back discards its device record.
-
-    ``ready()``   the event behind the batch's last launch has completed (a query, no wait)
-    ``result()``  the dict ``evaluation.evaluate_batch`` returns (``sample_metrics``, ``labels``, ``loss``, ``n_true``,
-                  ``n_total``, ``y_pred``, ``y_true``) plus ``confusion``, np.int64 [K, K] (rows: true class, columns:
-                  predicted); ONE device -> host read (ops.d2h, on the submitting stream) of the record up to sel[0:4].
-                  A forward that flagged its input raises what ``check_last_status`` raises; a tree that is not made of
-                  its proposals' ranges (sel[1]) goes through ``evaluate_batch(device_post=True, fixup=False)`` on a
-                  shallow copy of the retained batch — a DeviceLoader batch is collated again from its host items — and
-                  ``confusion`` is then counted on the host."""
-
-    def __init__(self, model, data, slices, out, lay, sel, pred, workspace, event, stream, labels, kw):
-        self.model, self.data, self.slices, self.kw = model, data, slices, kw
-        self._out, self._lay, self.sel, self.pred, self.workspace = out, lay, sel, pred, workspace
-        self.event, self._stream, self._labels = event, stream, labels
-        self._result = None
-
-    def ready(self):
-        return bool(self.event.query())
-
-    def result(self):
-        if self._result is not None:
-            return self._result
-        import numpy as np
-        from .postprocess import _unpack_statistics
-        lay = self._lay
-        B, K, T, R_cap = lay["B"], lay["K"], lay["T"], lay["R_cap"]
-        with torch.cuda.stream(self._stream):
-            host = ops.d2h(self._out[:lay["copy"]]).numpy()     # stream order: behind the true-positive walk
-            total, flag, status = int(host[lay["sel"]]), int(host[lay["sel"] + 1]), int(host[lay["sel"] + 2])
-            if status != 0:
-                ops.check_status_word(torch.tensor([status], dtype=torch.int32))      # raises for every flag a forward sets
-            if flag != 0:
-                res = self._fallback()
-            else:
-                stats = host[lay["stats"]:lay["stats"] + 2 + K * K]
-                loss = float(host[lay["loss"]:lay["loss"] + 1].view(np.float32)[0])
-                det = host[lay["det"]:lay["det"] + B * ops.MAX_DET * 6].view(np.float32).reshape(B, ops.MAX_DET, 6)
-                tp = host[lay["tp"]:lay["sel"]].view(np.uint8)[:T * B * ops.MAX_DET].reshape(T, B, ops.MAX_DET)
-                total = min(max(total, 0), R_cap)
-                res = {"loss": {"loss": loss, "loss_cls": loss}, "n_true": int(stats[0]), "n_total": int(stats[1]),
-                       "y_pred": host[lay["y_pred"]:lay["y_pred"] + total].astype(np.int64),
-                       "y_true": host[lay["y_true"]:lay["y_true"] + total].astype(np.int64),
-                       "sample_metrics": _unpack_statistics(host[:B], det, tp), "labels": list(self._labels),
-                       "confusion": stats[2:].reshape(K, K).astype(np.int64)}
-        self._result = res
-        self._release()
-        return res
-
-    def device_record(self):
-        """Views of the device record, nothing read: (det [B, 300, 6], det_count [B], tp [T, B, 300] uint8,
-        stats [2 + K * K] int32, loss [1]) — what yolat_metrics_append takes (evaluation.EpochMetrics)"""
-        lay, out = self._lay, self._out
-        B, K, T = lay["B"], lay["K"], lay["T"]
-        det = out[lay["det"]:lay["det"] + B * ops.MAX_DET * 6].view(torch.float32).view(B, ops.MAX_DET, 6)
-        tp = out[lay["tp"]:lay["sel"]].view(torch.uint8)[:T * B * ops.MAX_DET].view(T, B, ops.MAX_DET)
-        return (det, out[:B], tp, out[lay["stats"]:lay["stats"] + 2 + K * K],
-                out[lay["loss"]:lay["loss"] + 1].view(torch.float32))
-
-    def _fallback(self):
-        from .evaluation import evaluate_batch, confusion_counts
-        data, slices = self.data, self.slices
-        st = data.__dict__.get("_lazy") if hasattr(data, "__dict__") else None
-        if st is not None:
-            from .data import collate_to_device
-            data, slices = collate_to_device(st.items, device=self._out.device)
-        else:
-            # evaluate_batch overwrites data.labels and slices["bbox"], as the reference does: not on the caller's objects
-            bag = data.__class__()
-            bag.__dict__.update(data.__dict__)
-            data, slices = bag, dict(slices)
-        kw = self.kw
-        crit = DetectionLoss(Opt(classifier=kw["classifier"]))
-        with torch.no_grad():
-            res = evaluate_batch(self.model, crit, data, slices, classifier=kw["classifier"],
-                                 iou_thresholds=kw["iou_thresholds"], conf_thres=kw["conf_thres"],
-                                 iou_thres=kw["iou_thres"], fixup=False, device_post=True)
-        res["confusion"] = confusion_counts(res["y_true"], res["y_pred"], self._lay["K"])
-        return res
-
-    def _release(self):
-        self.data = self.slices = self.pred = self.workspace = None
 
 
 class SparseCADGCN(nn.Module):
@@ -387,96 +248,14 @@ class SparseCADGCN(nn.Module):
 
     def predict(self, data, slices):
         """arch:139-356.  Eval mode, a batch with its raw edge list: ONE forward over the whole batch
-        + integer selection on the device (`_predict_one_submission`: no host round trip between the two passes of the
+        + integer selection on the device (`submit.predict_one_submission`: no host round trip between the two passes of the
         reference, one read at the end); when the tree of the batch is not made of the ranges of its own proposals — or in
         any other mode — the two-pass extraction (`_predict_two_pass`).  Same 6-tuple either way."""
         if PREDICT_ONE_SUBMISSION and not self.training:
-            out = self._predict_one_submission(data, slices)
+            out = submit.predict_one_submission(self, data, slices)
             if out is not None:
                 return out
         return self._predict_two_pass(data, slices)
-
-    def _predict_operands(self, data, logits, bbox):
-        """(edge address, its two strides, bbox_idx address, N, E, P, device) of the batch whose forward just ran — what
-        yolat_predict_select validates the tree against; None when the edge list is not [E, 2]"""
-        d = data.__dict__ if hasattr(data, "__dict__") else {}
-        raw = d.get("_yolat_raw")
-        if raw is not None:
-            _, _, ep, se, sc, _, bp, N, E, P, dev = raw
-            return ep, se, sc, bp, N, E, P, dev
-        st = self._stage_tensors(data)
-        edge, bidx = st["edge"], st["bbox_idx"]
-        if edge.dim() != 2 or edge.shape[1] != 2:
-            return None
-        return (ops._i(edge, torch.int64, "edge"), edge.stride(0), edge.stride(1), ops._i(bidx, torch.int64, "bbox_idx"),
-                st["x"].shape[0], edge.shape[0], bbox.shape[0], logits.device)
-
-    @staticmethod
-    def _predict_tree(data, slices, dev, scales=None, extra=None):
-        """The flattened tree (data.flatten_tree) on the device, uploaded once per batch object (keyed by the identity of
-        the tree and the image offsets) -> (yolat_predict_tree, the host arrays, address of the scales or None).
-        scales [B, 4] fp32 (detect_submit) travel in the same upload and are cached with it; so do the arrays of
-        ``extra`` (evaluate_submit: a list of (name, contiguous numpy array of 4- or 8-byte elements), each placed at an
-        8-byte aligned offset) — their device addresses are left in ``tree._addr[name]``.  An upload made under another
-        stream is waited for on the current one before it is handed out."""
-        import numpy as np
-        from ._lib import PredictTree
-        from .data import flatten_tree
-        d = data.__dict__ if hasattr(data, "__dict__") else {}
-        key = (id(data.roots), len(data.roots), tuple(int(v) for v in slices["roots"]), tuple(int(v) for v in slices["pos"]),
-               tuple(int(v) for v in slices["edge"]), tuple(int(v) for v in slices["bbox"]))
-        ent = d.get("_yolat_tree")
-        skey = None if scales is None else scales.tobytes()
-        if extra:
-            skey = (skey,) + tuple((name, a.dtype.str, a.tobytes()) for name, a in extra)
-        if ent is None or ent[0] != key or (skey is not None and ent[4] != skey):
-            ft = flatten_tree(data, slices)
-            order = ("root_row", "root_range", "child_ptr", "child_row", "child_range", "image_root_ptr")
-            parts = [ft[k].reshape(-1) for k in order]
-            offs, o = {}, 0
-            for k in order:
-                offs[k] = o
-                o += ft[k].size
-            offs["scale"] = o
-            if scales is not None:
-                parts.append(np.ascontiguousarray(scales, dtype=np.float32).reshape(-1).view(np.int32))
-                o += parts[-1].size
-            for name, a in (extra or ()):
-                if o % 2:
-                    parts.append(np.zeros(1, dtype=np.int32))
-                    o += 1
-                offs[name] = o
-                parts.append(np.ascontiguousarray(a).reshape(-1).view(np.int32))
-                o += parts[-1].size
-            host = torch.from_numpy(np.concatenate(parts))
-            if skey is not None:
-                host = host.pin_memory()                 # a copy from pageable memory waits for the stream: predict reads
-                #                                          the device next anyway, detect_submit must not wait
-            buf = host.to(dev, non_blocking=True)
-            buf._yolat_host = host                       # alive until the copy has run: as long as its target
-            if extra:
-                up = torch.cuda.Event()
-                up.record(ops.current_stream_object())
-                buf._yolat_upload = (ops._stream(), up)
-            ent = (key, ft, buf, offs, skey)
-            try:
-                data.__dict__["_yolat_tree"] = ent
-            except AttributeError:
-                pass
-        _, ft, buf, offs, have = ent
-        upload = getattr(buf, "_yolat_upload", None)
-        if upload is not None and upload[0] != ops._stream():
-            cur = ops.current_stream_object()
-            cur.wait_event(upload[1])
-            buf.record_stream(cur)
-        t = PredictTree()
-        t.R, t.Ctot, t.B = ft["R"], ft["Ctot"], ft["B"]
-        base = buf.data_ptr()
-        for k in ("root_row", "root_range", "child_ptr", "child_row", "child_range", "image_root_ptr"):
-            setattr(t, k, base + 4 * offs[k])
-        t._keep = buf
-        t._addr = {name: base + 4 * offs[name] for name, _ in (extra or ())}
-        return t, ft, (base + 4 * offs["scale"]) if have is not None else None
 
     def detect_submit(self, data, slices, conf_thres=0.25, iou_thres=0.45, agnostic=False, classifier=None):
         """The detection of one batch — ``predict``, the scores and the class-aware NMS of ``evaluation.detect_batch`` —
@@ -487,58 +266,7 @@ class SparseCADGCN(nn.Module):
         list (``collate`` / ``collate_to_device(csr=False)`` / ``DeviceLoader(csr=False)``); boxes in pixels of
         ``data.width`` / ``data.height`` when the batch has them.  ``classifier``: as ``detect_batch``'s, default the
         model's own."""
-        import ctypes
-        import numpy as np
-        from ._lib import lib, check
-        if self.training:
-            raise RuntimeError("detect_submit runs the eval forward: call model.eval() first")
-        d = data.__dict__ if hasattr(data, "__dict__") else {}
-        if d.get("_yolat_graph") is not None and not all(k in data.keys for k in ("edge", "e_attr", "bbox_idx")):
-            raise ValueError(_PREPARED_BATCH)
-        with torch.no_grad():
-            logits, bbox = self.forward(data, slices)
-        opnd = self._predict_operands(data, logits, bbox)
-        if opnd is None:
-            raise ValueError("detect_submit expects the edge list as [E, 2]")
-        ep, se, sc, bp, N, E, P, dev = opnd
-        B = len(slices["roots"]) - 1
-        scales = np.ones((B, 4), dtype=np.float32)
-        if hasattr(data, "width") and hasattr(data, "height"):
-            for i in range(B):
-                scales[i] = (float(data.width[i]), float(data.height[i])) * 2
-        t, ft, scale_ptr = self._predict_tree(data, slices, dev, scales)
-        R_cap, K = ft["R"] + ft["Ctot"], int(logits.shape[1])
-        need = int(lib.yolat_detect_workspace_bytes(N, P, ft["R"], ft["Ctot"], K, B))
-        if need == 0:
-            raise ValueError("detect_submit: a batch of %d images, %d tree nodes and %d classes is outside what the batched "
-                             "NMS supports (nc <= 4096, B <= 65536, rows * nc <= 2^27)" % (B, R_cap, K))
-        if logits.dtype != torch.float32 or logits.stride(1) != 1:
-            logits = logits.float().contiguous()
-        bb = bbox if (bbox.dtype == torch.float32 and bbox.is_contiguous()) else bbox.float().contiguous()
-        # one allocation for what result() looks at and what it returns: det [B, 300, 6] | det_count [B] | sel
-        n_det = B * ops.MAX_DET * 6
-        out = torch.empty(n_det + B + 4 + B + 1 + R_cap, dtype=torch.int32, device=dev)
-        det, det_count, sel = out[:n_det].view(torch.float32).view(B, ops.MAX_DET, 6), out[n_det:n_det + B], out[n_det + B:]
-        pred = torch.empty((R_cap, 4 + K), dtype=torch.float32, device=dev)
-        ws = torch.empty(need, dtype=torch.uint8, device=dev)
-        softmax = (self.classifier if classifier is None else classifier) == "softmax"
-        stream = ops._stream()
-        check(lib.yolat_detect(logits.data_ptr(), logits.stride(0), P, K, bb.data_ptr(), ep if E > 0 else None, se, sc, bp, N,
-                               E, ctypes.byref(t), scale_ptr, int(softmax), float(conf_thres), float(iou_thres),
-                               int(bool(agnostic)), sel.data_ptr(), pred.data_ptr(), det.data_ptr(), det_count.data_ptr(),
-                               ws.data_ptr(), ws.numel(), stream), "yolat_detect")
-        plan = self.__dict__.get("_yolat_plan")
-        status = getattr(plan, "_status", None)
-        if status is not None:
-            # the forward's input-validity word rides along in sel[2]; cleared behind the copy (stream order), so that the
-            # next handle carries the flags of ITS forward only
-            sel[2:3].copy_(status)
-            status.zero_()
-        done = torch.cuda.Event()
-        done.record(ops.current_stream_object())
-        return DetectHandle(self, data, slices, out, det, det_count, sel, pred, ws, done,
-                            dict(conf_thres=conf_thres, iou_thres=iou_thres, agnostic=agnostic,
-                                 classifier=self.classifier if classifier is None else classifier))
+        return submit.detect_submit(self, data, slices, conf_thres, iou_thres, agnostic, classifier)
 
     def evaluate_submit(self, data, slices, iou_thresholds=None, conf_thres=0.0, iou_thres=0.5, classifier=None):
         """One iteration of the evaluation loop (``evaluation.evaluate_batch(device_post=True)``: predict, loss, top-1,
@@ -551,148 +279,7 @@ class SparseCADGCN(nn.Module):
         Host labels are range-checked before anything is enqueued — ALL labels of the batch, where DetectionLoss sees the
         selected rows only — and raise IndexError; device labels are guarded in the kernel (NaN loss).  ``data`` and
         ``slices`` are not modified.  ``classifier``: as ``evaluate_batch``'s, default the model's own."""
-        import ctypes
-        import numpy as np
-        from ._lib import lib, check
-        if self.training:
-            raise RuntimeError("evaluate_submit runs the eval forward: call model.eval() first")
-        d = data.__dict__ if hasattr(data, "__dict__") else {}
-        if d.get("_yolat_graph") is not None and not all(k in data.keys for k in ("edge", "e_attr", "bbox_idx")):
-            raise ValueError(_PREPARED_BATCH)
-        if iou_thresholds is None:
-            iou_thresholds = np.linspace(0.5, 0.95, 10)
-        ths = np.ascontiguousarray(np.asarray(iou_thresholds, dtype=np.float32).reshape(-1))
-        labels = data.labels
-        if not labels.is_cuda and labels.numel():
-            lo, hi = int(labels.min()), int(labels.max())
-            if lo < 0 or hi >= self.n_classes:
-                raise IndexError("Target %d is out of bounds." % (lo if lo < 0 else hi))
-        with torch.no_grad():
-            logits, bbox = self.forward(data, slices)
-        opnd = self._predict_operands(data, logits, bbox)
-        if opnd is None:
-            raise ValueError("evaluate_submit expects the edge list as [E, 2]")
-        ep, se, sc, bp, N, E, P, dev = opnd
-        B = len(slices["roots"]) - 1
-        K, T = int(logits.shape[1]), int(ths.shape[0])
-        scales = np.ones((B, 4), dtype=np.float32)
-        if hasattr(data, "width") and hasattr(data, "height"):
-            for i in range(B):
-                scales[i] = (float(data.width[i]), float(data.height[i])) * 2
-        # the targets of evaluate_batch: rows label_ptr[i]:label_ptr[i + 1] of image i, boxes scaled in fp32
-        lptr = np.asarray([int(v) for v in slices["gt_labels"]], dtype=np.int64)
-        if lptr.shape[0] != B + 1:
-            raise ValueError("slices['gt_labels'] must hold B + 1 offsets")
-        g0, g1 = int(lptr[0]), int(lptr[-1])
-        per_image = np.repeat(np.arange(B), np.diff(lptr))
-        gt_labels = data.gt_labels[g0:g1].cpu()
-        gt_box = (data.gt_bbox[g0:g1].cpu().float() * torch.from_numpy(scales)[torch.from_numpy(per_image)]).numpy()
-        G = int(gt_box.shape[0])
-        extra = [("gt_ptr", (lptr - g0).astype(np.int32)), ("gt_box", np.ascontiguousarray(gt_box, dtype=np.float32)),
-                 ("gt_label", gt_labels.float().numpy()), ("thresholds", ths)]
-        if not labels.is_cuda:
-            extra.append(("labels", np.ascontiguousarray(labels.numpy(), dtype=np.int64)))
-        elif labels.dtype != torch.int64 or not labels.is_contiguous():
-            labels = labels.long().contiguous()
-        if int(labels.shape[0]) != P:
-            raise ValueError("labels must hold one class id per proposal")
-        t, ft, scale_ptr = self._predict_tree(data, slices, dev, scales, extra)
-        R_cap = ft["R"] + ft["Ctot"]
-        need = int(lib.yolat_evaluate_workspace_bytes(N, P, ft["R"], ft["Ctot"], K, B, G, T))
-        if need == 0:
-            raise ValueError("evaluate_submit: a batch of %d images, %d tree nodes, %d classes, %d targets and %d thresholds "
-                             "is outside what yolat_evaluate supports (K in [2, 32], B <= 65536, rows * (K - 1) <= 2^27, "
-                             "targets <= 262144, thresholds <= 65535)" % (B, R_cap, K, G, T))
-        if logits.dtype != torch.float32 or logits.stride(1) != 1:
-            logits = logits.float().contiguous()
-        bb = bbox if (bbox.dtype == torch.float32 and bbox.is_contiguous()) else bbox.float().contiguous()
-        # one allocation for what result() looks at, in int32 units; sel comes last so that the copy ends behind sel[0:4]
-        lay, o = {"B": B, "K": K, "T": T, "R_cap": R_cap}, B
-        for name, n in (("stats", 2 + K * K), ("loss", 1), ("y_pred", R_cap), ("y_true", R_cap),
-                        ("det", B * ops.MAX_DET * 6), ("tp", (T * B * ops.MAX_DET + 3) // 4), ("sel", 4 + B + 1 + R_cap)):
-            lay[name] = o
-            o += n
-        lay["copy"] = lay["sel"] + 4
-        out = torch.empty(o, dtype=torch.int32, device=dev)
-        sel = out[lay["sel"]:]
-        pred = torch.empty((R_cap, 4 + K), dtype=torch.float32, device=dev)
-        ws = torch.empty(need, dtype=torch.uint8, device=dev)
-        cls = self.classifier if classifier is None else classifier
-        base, addr = out.data_ptr(), t._addr
-        stream = ops._stream()
-        check(lib.yolat_evaluate(logits.data_ptr(), logits.stride(0), P, K, bb.data_ptr(), ep if E > 0 else None, se, sc, bp,
-                                 N, E, ctypes.byref(t), scale_ptr, int(cls == "softmax"), float(conf_thres),
-                                 float(iou_thres), addr["labels"] if "labels" in addr else labels.data_ptr(),
-                                 addr["gt_box"], addr["gt_label"], G, addr["gt_ptr"], addr["thresholds"], T,
-                                 sel.data_ptr(), pred.data_ptr(), base + 4 * lay["det"], base, base + 4 * lay["stats"],
-                                 base + 4 * lay["loss"], base + 4 * lay["y_pred"], base + 4 * lay["y_true"],
-                                 base + 4 * lay["tp"], ws.data_ptr(), ws.numel(), stream), "yolat_evaluate")
-        plan = self.__dict__.get("_yolat_plan")
-        status = getattr(plan, "_status", None)
-        if status is not None:
-            # the forward's input-validity word rides along in sel[2]; cleared behind the copy (stream order), so that the
-            # next handle carries the flags of ITS forward only
-            sel[2:3].copy_(status)
-            status.zero_()
-        cur = ops.current_stream_object()
-        done = torch.cuda.Event()
-        done.record(cur)
-        hold = (logits, bb, labels, t)                   # what the launches read: alive as long as the handle's record
-        out._yolat_keep = hold
-        h = EvalHandle(self, data, slices, out, lay, sel, pred, ws, done, cur, gt_labels.tolist(),
-                       dict(conf_thres=conf_thres, iou_thres=iou_thres, classifier=cls, iou_thresholds=iou_thresholds))
-        # the uploaded target classes [G] fp32, for the epoch record (evaluation.EpochMetrics)
-        g_at = (addr["gt_label"] - t._keep.data_ptr()) // 4
-        h.gt_label = t._keep[g_at:g_at + G].view(torch.float32)
-        return h
-
-    def _predict_one_submission(self, data, slices):
-        """One forward over the whole batch, then yolat_predict_select / yolat_predict_gather (csrc/subgraph.hip): in eval
-        mode the logits of a proposal depend only on its own nodes and edges, so the root pass and the child pass of the
-        reference are rows of the same forward; `has_object` (:259-281), the per-image interleaving (:317-328) and the 5 %
-        box enlargement (:341-346) are device kernels.  Returns None when the shortcut does not apply (the device found
-        tree ranges that are not the ranges of the proposals, or an edge between proposals: the duplicate / KeyError
-        cases of the reference) — the caller then runs the two-pass extraction."""
-        import ctypes
-        import numpy as np
-        from ._lib import lib, check
-        d = data.__dict__ if hasattr(data, "__dict__") else {}
-        if d.get("_yolat_graph") is not None:
-            return None                                  # prepared-CSR batch: no raw edge list to validate the tree against
-        with torch.no_grad():
-            logits, bbox = self.forward(data, slices)
-        opnd = self._predict_operands(data, logits, bbox)
-        if opnd is None:
-            return None
-        ep, se, sc, bp, N, E, P, dev = opnd
-        t, ft, _ = self._predict_tree(data, slices, dev)
-        R, Ctot, B = ft["R"], ft["Ctot"], ft["B"]
-        K = logits.shape[1]
-        out = torch.empty(4 + B + 1 + R + Ctot, dtype=torch.int32, device=dev)
-        ws = torch.empty(int(lib.yolat_predict_select_workspace_bytes(N, P, R)) + 16, dtype=torch.uint8, device=dev)
-        stream = ops._stream()
-        check(lib.yolat_predict_select(logits.data_ptr(), logits.stride(0), P, K, ep if E > 0 else None, se, sc, bp, N, E,
-                                       ctypes.byref(t), out.data_ptr(), ws.data_ptr(), ws.numel(), stream),
-              "yolat_predict_select")
-        plan = self.__dict__.get("_yolat_plan")
-        if getattr(plan, "_status", None) is not None:    # the forward's input-validity word rides along in out[2]
-            out[2:3].copy_(plan._status)
-        host = out.cpu().numpy()                          # the ONE host read of the call (synchronises)
-        if int(host[2]) != 0:
-            self.check_last_status()                      # raises IndexError / ValueError like the forward's own check
-        if int(host[1]) != 0:
-            return None
-        total = int(host[0])
-        slice_image_bbox = [int(v) for v in host[4:4 + B + 1]]
-        slice_bbox = torch.from_numpy(host[4 + B + 1:4 + B + 1 + total].astype(np.int64))
-        pred_cls = torch.empty(total, K, dtype=torch.float32, device=dev)
-        pred_bbox = torch.empty(total, 4, dtype=torch.float32, device=dev)
-        bb = bbox if (bbox.dtype == torch.float32 and bbox.is_contiguous()) else bbox.float().contiguous()
-        check(lib.yolat_predict_gather(logits.data_ptr(), logits.stride(0), P, K, bb.data_ptr(),
-                                       out.data_ptr() + 4 * (4 + B + 1), total, pred_cls.data_ptr(), pred_bbox.data_ptr(),
-                                       stream), "yolat_predict_gather")
-        pred_cls._yolat_keep = (out, logits, bb)
-        return pred_cls, pred_bbox, None, slice_bbox, slice_image_bbox, None
+        return submit.evaluate_submit(self, data, slices, iou_thresholds, conf_thres, iou_thres, classifier)
 
     def _predict_two_pass(self, data, slices):
         """Two-pass root/children inference, arch:139-356: forward on the sub-batch of all root
@@ -702,8 +289,7 @@ class SparseCADGCN(nn.Module):
         slice_image_bbox, None)``.  The host walks the proposal tree; node / edge re-indexing and the
         gathers are device kernels (`ops.extract_subgraph`); both forwards run through the HIP path."""
         from .data import select_tree_ranges, interleave_root_child
-        if getattr(data, "_yolat_graph", None) is not None and not all(k in data.keys for k in ("edge", "e_attr", "bbox_idx")):
-            raise ValueError(_PREPARED_BATCH)
+        submit.require_raw_edges(data)
         # the whole batch goes to the device once; both sub-batches are cut out of it by integer kernels
         # (csrc/subgraph.hip) — the host only walks the proposal tree (O(#tree nodes))
         dev = {k: getattr(data, k).cuda(non_blocking=True) for k in ("x", "pos", "edge", "e_attr", "bbox_idx", "bbox",

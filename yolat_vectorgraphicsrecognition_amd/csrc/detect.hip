@@ -18,7 +18,7 @@
 // boxes kept in its own chunk, and the walk stops at the 300th keep: O(n * 300) IoU tests and O(n) memory, where the
 // n x n / 64 suppression mask of nms.hip is 112 MB per image at the 30 000-candidate cap.  The predicate is nms.hip's.
 // Workspace: 24 bytes per slot (keys and slots, in and out) + rocPRIM's own temporary storage.
-#include "base.hpp"
+#include "sel_record.hpp"
 
 #include <rocprim/device/device_radix_sort.hpp>
 
@@ -33,17 +33,14 @@ constexpr int64_t DET_MAX_IMAGES = 65536;
 constexpr int64_t DET_MAX_CLASSES = 4096;
 constexpr int64_t DET_MAX_TARGETS = 262144;   // claimed-set of k_det_match: one bit per target in LDS (32 KB)
 
-// image_ptr / gt_ptr entries are read through this: whatever the array holds, every index derived from it is in range
-__device__ __forceinline__ int det_clamp(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
-
 // the image of row r: the last i in [0, B) with image_ptr[i] <= r, r < image_ptr[i + 1]; B when no image holds the row
 __device__ __forceinline__ int det_image_of(const int* __restrict__ image_ptr, int B, int R, int r) {
   int lo = 0, hi = B;                  // invariant: image_ptr[lo] <= r (or lo == 0), first i with image_ptr[i] > r is in (lo, hi]
   while (hi - lo > 1) {
     const int mid = (lo + hi) >> 1;
-    if (det_clamp(image_ptr[mid], R) <= r) lo = mid; else hi = mid;
+    if (yl_clamp(image_ptr[mid], R) <= r) lo = mid; else hi = mid;
   }
-  return (r >= det_clamp(image_ptr[lo], R) && r < det_clamp(image_ptr[lo + 1], R)) ? lo : B;
+  return (r >= yl_clamp(image_ptr[lo], R) && r < yl_clamp(image_ptr[lo + 1], R)) ? lo : B;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -123,8 +120,8 @@ static __global__ void __launch_bounds__(DET_CHUNK) k_det_nms(const float* __res
   __shared__ int wfirst[2][DET_CHUNK / 64];
   __shared__ int n_s;
   const int img = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int r0 = det_clamp(image_ptr[img], R), r1 = det_clamp(image_ptr[img + 1], R);
-  const int rbase = det_clamp(image_ptr[0], R);
+  const int r0 = yl_clamp(image_ptr[img], R), r1 = yl_clamp(image_ptr[img + 1], R);
+  const int rbase = yl_clamp(image_ptr[0], R);
   // the image's slots in sorted order start where its rows' slots start (rows before image_ptr[0] sort last)
   const long s0 = (long)(r0 - rbase) * nc;
   const long len = r1 > r0 && r0 >= rbase ? (long)(r1 - r0) * nc : 0;
@@ -187,12 +184,11 @@ static __global__ void __launch_bounds__(DET_CHUNK) k_det_nms(const float* __res
 // ------------------------------------------------------------------------------------------------
 // 2b. the pred rows of yolat_detect: k_predict_gather (subgraph.hip) + k_det_scores in one launch with every size read on
 // the device.  One thread per row r < R_cap = R + Ctot, the bound the host knows from the tree it uploaded; the record of
-// yolat_predict_select says how many of them exist: sel[0] = total, sel + 4 = the per-image offsets [B + 1], behind them
-// the proposal row of every output row.  Row r < total: the proposal's box enlarged by 5 % about its centre with the fp32
-// steps of k_predict_gather (w / 2 is exact, nothing else is a multiply feeding an add), times the image's scale, and the
-// scores of k_det_scores — bit for bit the row the two calls produce.  A SPARE row r >= total belongs to no image
-// (det_image_of gives B behind image_off[B] = total): rows[r] is uninitialised and is not read, the row is written as
-// zeros so that k_det_keys reads defined memory, and it can never be a candidate.
+// yolat_predict_select (sel_record.hpp) says how many of them exist and which proposal each is.  Row r < total: the
+// proposal's box enlarged by 5 % about its centre with the fp32 steps of k_predict_gather (w / 2 is exact, nothing else is
+// a multiply feeding an add), times the image's scale, and the scores of k_det_scores — bit for bit the row the two calls
+// produce.  A SPARE row r >= total belongs to no image (det_image_of gives B behind image_off[B] = total): rows[r] is
+// uninitialised and is not read, the row is written as zeros for k_det_keys, and it can never be a candidate.
 // (A variant in which this kernel also wrote the sort keys — one launch fewer — was measured and is no faster: DESIGN.md.)
 // ------------------------------------------------------------------------------------------------
 static __global__ void __launch_bounds__(256) k_detect_rows(const float* __restrict__ logits, long ld, int K, int P,
@@ -201,16 +197,15 @@ static __global__ void __launch_bounds__(256) k_detect_rows(const float* __restr
                                                              float* __restrict__ pred) {
   const int r = blockIdx.x * blockDim.x + threadIdx.x;
   if (r >= R_cap) return;
-  const int total = det_clamp(sel[0], R_cap);
-  const int* image_off = sel + 4;
-  const int* rows = sel + 4 + B + 1;
+  const int total = yl_clamp(sel[YL_SEL_TOTAL], R_cap);
+  const int* rows = yl_sel_rows(sel, B);
   float* o = pred + (long)r * (4 + K);
   if (r < total) {
-    const int row = det_clamp(rows[r], P - 1);
+    const int row = yl_clamp(rows[r], P - 1);
     const float x1 = bbox[4l * row], y1 = bbox[4l * row + 1], x2 = bbox[4l * row + 2], y2 = bbox[4l * row + 3];
     const float w = (x2 - x1) * 1.05f, h = (y2 - y1) * 1.05f, cx = (x2 + x1) / 2.f, cy = (y2 + y1) / 2.f;
     const float e[4] = {cx - w / 2.f, cy - h / 2.f, cx + w / 2.f, cy + h / 2.f};
-    const int img = det_image_of(image_off, B, R_cap, r);
+    const int img = det_image_of(yl_sel_image_off(sel), B, R_cap, r);
     const float* sc = scale + 4 * (img < B ? img : 0);
 #pragma unroll
     for (int j = 0; j < 4; ++j) o[j] = img < B ? e[j] * sc[j] : 0.f;
@@ -310,8 +305,8 @@ extern "C" int yolat_nms_batched(const float* pred, int64_t R, int64_t nc, const
 // ------------------------------------------------------------------------------------------------
 // 2c. yolat_detect: logits -> det [B, 300, 6] of one batch, enqueued in one go (SparseCADGCN.detect_submit).  The
 // launches of yolat_predict_select, k_detect_rows over R_cap = R + Ctot rows, then keys / radix sort / k_det_nms over the
-// same R_cap rows with image_ptr = sel + 4: a spare row is a non-candidate of image B, the stable sort puts those slots
-// behind every image's own range, and k_det_nms reads an image's range only.  Nothing is read back.
+// same R_cap rows with image_ptr = the record's offsets: a spare row is a non-candidate of image B, the stable sort puts
+// those slots behind every image's own range, and k_det_nms reads an image's range only.  Nothing is read back.
 // ------------------------------------------------------------------------------------------------
 namespace {
 struct DetectPlan { size_t sel_bytes, off_nms, nms_bytes, total; };
@@ -359,9 +354,7 @@ extern "C" int yolat_detect(const float* logits, int64_t ld_logits, int64_t P, i
       N <= 0 || E < 0 || (E > 0 && !edge) || ld_logits < K)
     return YOLAT_E_INVALID;
   const yolat_predict_tree& t = *tree;
-  if (t.R < 0 || t.Ctot < 0 || t.B < 1 || !t.image_root_ptr || !t.child_ptr ||
-      (t.R > 0 && (!t.root_row || !t.root_range)) || (t.Ctot > 0 && (!t.child_row || !t.child_range)))
-    return YOLAT_E_INVALID;
+  if (!yl_predict_tree_ok(t, 1)) return YOLAT_E_INVALID;
   const int64_t R_cap = t.R + t.Ctot;
   if (R_cap > 0 && !pred) return YOLAT_E_INVALID;
   if (E >= (1LL << 30) || !detect_shape_ok(N, P, t.R, t.Ctot, K, t.B) || (((uintptr_t)workspace) & 255) != 0)
@@ -376,8 +369,8 @@ extern "C" int yolat_detect(const float* logits, int64_t ld_logits, int64_t P, i
                        (int)K, (int)P, bbox, sel, (int)t.B, (int)R_cap, scale, softmax, pred);
     YL_LAUNCH_CHECK();
   }
-  return yolat_nms_batched(pred, R_cap, K - 1, sel + 4, t.B, conf_thres, iou_thres, agnostic, det_out, det_count,
-                           base + p.off_nms, p.nms_bytes, stream);
+  return yolat_nms_batched(pred, R_cap, K - 1, yl_sel_image_off(sel), t.B, conf_thres, iou_thres, agnostic, det_out,
+                           det_count, base + p.off_nms, p.nms_bytes, stream);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -392,9 +385,9 @@ static __global__ void __launch_bounds__(64) k_det_match(const float* __restrict
                                                         unsigned char* __restrict__ tp_out) {
   extern __shared__ unsigned claimed[];          // one bit per target of the image
   const int img = blockIdx.x, t = blockIdx.y, lane = threadIdx.x;
-  const int g0 = det_clamp(gt_ptr[img], G), g1 = yl_max(det_clamp(gt_ptr[img + 1], G), g0);
+  const int g0 = yl_clamp(gt_ptr[img], G), g1 = yl_max(yl_clamp(gt_ptr[img + 1], G), g0);
   const int m = g1 - g0;
-  const int nd = det_clamp(det_count[img], DET_MAX_DET);
+  const int nd = yl_clamp(det_count[img], DET_MAX_DET);
   const float thr = thresholds[t];
   for (int w = lane; w < (m + 31) / 32; w += 64) claimed[w] = 0u;
   __syncthreads();

@@ -7,7 +7,7 @@
 //   c. yolat_detect_match (detect.hip): the true-positive flags of every (image, IoU threshold) pair -> tp.
 //
 // The rows stage.  One thread per row r < R_cap = R + Ctot, the bound the host knows from the tree it uploaded, 256 rows per
-// workgroup; total = sel[0] and the row list behind sel + 4 + B + 1 are read on the device, as k_detect_rows reads them.
+// workgroup; the total and the row list of sel (sel_record.hpp) are read on the device, as k_detect_rows reads them.
 // Row r < total: the loss term of logits[rows[r]] against labels[rows[r]] with the row bodies of loss_rows.hpp — the text
 // k_softmax_ce_rows<32> / k_bce_rows<32, false> are made of — the workgroup's fixed-order tree into work[wg], and
 // k_eval_final adds the partials in k_ce_final's / k_bce_final's order and divides by total (total * K for BCE) with the
@@ -18,15 +18,12 @@
 // a workgroup counts in LDS (K <= 32: 4 KB) and issues one global integer atomic per non-zero cell — integer adds commute,
 // two runs are bit-identical.  A label outside [0, K) poisons the loss with NaN (yolat_softmax_ce's contract), enters no
 // confusion cell and is never a hit; nothing is read or written through it.
-#include "base.hpp"
+#include "sel_record.hpp"
 #include "loss_rows.hpp"
 
 constexpr int EVAL_KMAX = 32;                 // the register-resident row of the loss kernels
 constexpr int64_t EVAL_MAX_TARGETS = 262144;  // yolat_detect_match's limits
 constexpr int64_t EVAL_MAX_THRESHOLDS = 65535;
-
-// sel entries are read through this: whatever the record holds, every index derived from it is in range
-__device__ __forceinline__ int eval_clamp(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
 
 template <bool SOFTMAX>
 static __global__ void __launch_bounds__(256) k_eval_rows(const float* logits, long ld, int K, int P, const int64_t* labels,
@@ -36,14 +33,13 @@ static __global__ void __launch_bounds__(256) k_eval_rows(const float* logits, l
   __shared__ int hits;
   const int tid = threadIdx.x;
   const int r = blockIdx.x * 256 + tid;
-  const int total = eval_clamp(sel[0], R_cap);
-  const int* rows = sel + 4 + B + 1;
+  const int total = yl_clamp(sel[YL_SEL_TOTAL], R_cap);
   for (int c = tid; c < K * K; c += 256) cells[c] = 0;
   if (tid == 0) hits = 0;
   __syncthreads();
   float row_loss = 0.f;
   if (r < total) {
-    const int row = eval_clamp(rows[r], P - 1);
+    const int row = yl_clamp(yl_sel_rows(sel, B)[r], P - 1);
     const float* z = logits + (long)row * ld;
     float* const no_grad = nullptr;
     if (SOFTMAX) {
@@ -82,7 +78,7 @@ template <bool SOFTMAX>
 static __global__ void __launch_bounds__(1024) k_eval_final(const float* work, int n, const int* sel, int R_cap, int K,
                                                             float* loss) {
   yl_partials_tree1024(work, n, threadIdx.x, [=](float sum) {
-    const int total = eval_clamp(sel[0], R_cap);
+    const int total = yl_clamp(sel[YL_SEL_TOTAL], R_cap);
     if (SOFTMAX) {
       loss[0] = sum / (float)total;
     } else {
@@ -155,9 +151,7 @@ extern "C" int yolat_evaluate(const float* logits, int64_t ld_logits, int64_t P,
       N <= 0 || E < 0 || (E > 0 && !edge) || ld_logits < K)
     return YOLAT_E_INVALID;
   const yolat_predict_tree& t = *tree;
-  if (t.R < 0 || t.Ctot < 0 || t.B < 1 || !t.image_root_ptr || !t.child_ptr ||
-      (t.R > 0 && (!t.root_row || !t.root_range)) || (t.Ctot > 0 && (!t.child_row || !t.child_range)))
-    return YOLAT_E_INVALID;
+  if (!yl_predict_tree_ok(t, 1)) return YOLAT_E_INVALID;
   const int64_t R_cap = t.R + t.Ctot;
   if (!labels || !stats || !loss || !tp_out || !gt_ptr || !thresholds || G < 0 || T < 1) return YOLAT_E_INVALID;
   if (G > 0 && (!gt_boxes || !gt_labels)) return YOLAT_E_INVALID;

@@ -23,7 +23,7 @@
 //                       tpc / fpc are integers (exact), recall = tpc / (n_gt + 1e-16), precision = tpc / (tpc + fpc), the
 //                       envelope is the reverse running maximum, the area is summed where the recall changes; float64.
 //                       One more workgroup: the mean loss (index order), the counts, the status word and the flags.
-#include "base.hpp"
+#include "sel_record.hpp"
 
 #include <rocprim/device/device_radix_sort.hpp>
 
@@ -53,7 +53,7 @@ static __global__ void __launch_bounds__(256) k_metrics_append(MetRecord rec, co
                                                               long image_base, int batch_index) {
   const int tid = threadIdx.x, b = blockIdx.x;
   int tree = 0, status = 0;
-  if (sel != nullptr) { tree = sel[1]; status = sel[2]; }
+  if (sel != nullptr) { tree = sel[YL_SEL_TREE]; status = sel[YL_SEL_STATUS]; }
   const bool clean = tree == 0 && status == 0;
   if (b == B) {
     if (sel != nullptr && tid == 0) {

@@ -9,7 +9,7 @@
 //   edge'[q]     = (o2n[edge[eid[q],0]], o2n[edge[eid[q],1]]);  an endpoint outside the subset raises the
 //                  YOLAT_STATUS_EDGE_RANGE flag (the reference raises KeyError)
 //   bbox_idx'[i] = number of positions 0 < t <= i with bbox_idx[node_ids[t]] != bbox_idx[node_ids[t-1]]
-#include "base.hpp"
+#include "sel_record.hpp"
 #include "internal.hpp"
 
 static __global__ void k_expand_ranges(const int* __restrict__ start, const int* __restrict__ prefix, int S,
@@ -234,7 +234,7 @@ static __global__ void __launch_bounds__(256) k_predict_validate(yolat_predict_t
                                                                  const int* status, int* out) {
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
   const long R = t.R, C = t.Ctot;
-  if (i == 0 && (info[0] != 0 || status[0] != 0)) atomicOr(out + 1, 2);
+  if (i == 0 && (info[0] != 0 || status[0] != 0)) atomicOr(out + YL_SEL_TREE, 2);
   if (i >= R + C) return;
   const bool root = i < R;
   const long j = root ? i : i - R;
@@ -242,7 +242,7 @@ static __global__ void __launch_bounds__(256) k_predict_validate(yolat_predict_t
   const int* rg = (root ? t.root_range : t.child_range) + 4 * j;       // pos_s, pos_e, edge_s, edge_e
   bool ok = row >= 0 && row < P;
   if (ok) ok = rg[0] == seg_ptr[row] && rg[1] == seg_ptr[row + 1] && rg[2] == eptr[row] && rg[3] == eptr[row + 1];
-  if (!ok) atomicOr(out + 1, 1);
+  if (!ok) atomicOr(out + YL_SEL_TREE, 1);
 }
 
 // one workgroup: R roots (a few thousand at most per batch)
@@ -294,13 +294,13 @@ static __global__ void __launch_bounds__(1024) k_predict_select(yolat_predict_tr
   if (tid == 0) sel_off[R] = carry_s;
   __syncthreads();
   const int total_children = carry_s;
-  int* image_off = out + 4;                      // [B + 1]
-  int* rows = out + 4 + B + 1;                   // [R + Ctot]
+  int* image_off = yl_sel_image_off(out);        // [B + 1]
+  int* rows = yl_sel_rows(out, B);               // [R + Ctot]
   for (int i = tid; i <= B; i += 1024) {
     const int r = t.image_root_ptr[i];
     image_off[i] = r + sel_off[r];
   }
-  if (tid == 0) out[0] = R + total_children;
+  if (tid == 0) out[YL_SEL_TOTAL] = R + total_children;
   for (int r = tid; r < R; r += 1024) {
     int lo = 0, hi = B;                          // image of root r: largest i with image_root_ptr[i] <= r
     while (hi - lo > 1) {
@@ -346,9 +346,7 @@ extern "C" int yolat_predict_select(const float* logits, int64_t ld_logits, int6
       ld_logits < K)
     return YOLAT_E_INVALID;
   const yolat_predict_tree& t = *tree;
-  if (t.R < 0 || t.Ctot < 0 || t.B < 0 || !t.image_root_ptr || !t.child_ptr ||
-      (t.R > 0 && (!t.root_row || !t.root_range)) || (t.Ctot > 0 && (!t.child_row || !t.child_range)))
-    return YOLAT_E_INVALID;
+  if (!yl_predict_tree_ok(t, 0)) return YOLAT_E_INVALID;
   if (N >= (1LL << 30) || E >= (1LL << 30) || P >= (1LL << 30) || t.R + t.Ctot >= (1LL << 30)) return YOLAT_E_UNSUPPORTED;
   if (workspace_bytes < yolat_predict_select_workspace_bytes(N, P, t.R)) return YOLAT_E_INVALID;
   hipStream_t st = (hipStream_t)stream;
@@ -360,7 +358,7 @@ extern "C" int yolat_predict_select(const float* logits, int64_t ld_logits, int6
   int32_t* info = sel_off + (t.R + 1);           // [4] locality flags, then [1] status bits of malformed ids
   int32_t* status = info + 4;
   hipLaunchKernelGGL(k_predict_zero, dim3(1), dim3(64), 0, st, info, 8);
-  hipLaunchKernelGGL(k_predict_zero, dim3(1), dim3(64), 0, st, out, 4);
+  hipLaunchKernelGGL(k_predict_zero, dim3(1), dim3(64), 0, st, out, YL_SEL_HEAD);
   YL_LAUNCH_CHECK();
   int rc = yl_local_prep(edge, stride_e, stride_c, bbox_idx, N, E, P, seg_ptr, node_seg, eptr, status, info, false, st);
   if (rc != 0) return rc;

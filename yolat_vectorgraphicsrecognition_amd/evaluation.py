@@ -5,13 +5,25 @@ thresholds 0.5 .. 0.95; then AP per class and threshold.  Same inputs (``(data, 
 with ``labels, has_obj, gt_bbox, gt_labels, width, height`` next to the graph tensors) and the same value written to
 ``opt.test_value`` / returned (the mean AP at the LAST threshold, train.py:507-508); the intermediate numbers the
 reference only logs are returned in ``opt.test_report``."""
+from collections import deque
+
 import numpy as np
 import torch
 
-from .data import fixup_offsets
+from .data import fixup_offsets, DeviceLoader
 from . import ops
+from .submit import EvalHandle, image_scales
 from .postprocess import (non_max_suppression, get_batch_statistics, ap_per_class, detect_post_device,
                           non_max_suppression_batched)
+
+
+def _prepare(data, slices, fixup):
+    """what every per-batch entry starts with: the index fix-up (train.py:346-366) unless the batch carries its offsets
+    already, and the ``edge_control`` attribute of the reference's loop"""
+    if fixup:
+        fixup_offsets(data, slices)
+    if not hasattr(data, "edge_control"):
+        data.edge_control = None
 
 
 def evaluate_batch(model, criterion, data, slices, classifier="softmax", iou_thresholds=None, conf_thres=0.0,
@@ -24,10 +36,7 @@ def evaluate_batch(model, criterion, data, slices, classifier="softmax", iou_thr
     Python; same detections and flags, the softmax may differ from torch's in the last bit."""
     if iou_thresholds is None:
         iou_thresholds = np.linspace(0.5, 0.95, 10)
-    if fixup:
-        fixup_offsets(data, slices)                                   # train.py:346-366
-    if not hasattr(data, "edge_control"):
-        data.edge_control = None
+    _prepare(data, slices, fixup)
     out = model.predict(data, slices)
     keep = torch.as_tensor([int(v) for v in out[3]], dtype=torch.long)
     data.labels = data.labels[keep]
@@ -81,18 +90,12 @@ def detect_batch(model, data, slices, conf_thres=0.25, iou_thres=0.45, classifie
     class-aware NMS of all images as two device calls (ops.detect_scores, postprocess.non_max_suppression_batched).
     Returns one device tensor [k, 6] = (x1, y1, x2, y2, conf, cls) per image, boxes in pixels of the image
     (``data.width`` / ``data.height``; without them the boxes stay in the model's unit square)."""
-    if fixup:
-        fixup_offsets(data, slices)
-    if not hasattr(data, "edge_control"):
-        data.edge_control = None
+    _prepare(data, slices, fixup)
     with torch.no_grad():
         out = model.predict(data, slices)
     logits, boxes, image_ptr = out[0].detach().float(), out[1].detach().float().contiguous(), out[4]
     B = len(image_ptr) - 1
-    scales = np.ones((B, 4), dtype=np.float32)
-    if hasattr(data, "width") and hasattr(data, "height"):
-        for i in range(B):
-            scales[i] = (float(data.width[i]), float(data.height[i])) * 2
+    scales = image_scales(data, B)
     dev = logits.device
     ptr = torch.as_tensor([int(v) for v in image_ptr], dtype=torch.int32)
     up = torch.from_numpy(np.concatenate([ptr.numpy(), scales.reshape(-1).view(np.int32)])).to(dev)
@@ -105,10 +108,7 @@ def detect_batch_async(model, data, slices, conf_thres=0.25, iou_thres=0.45, cla
     """``detect_batch`` as a submission: the same ``fixup`` / ``edge_control`` handling, then
     ``model.detect_submit`` — forward, selection, scores and NMS enqueued on the current stream, nothing read back.
     Returns the ``DetectHandle``; ``handle.result()`` is the list ``detect_batch`` returns, bit for bit."""
-    if fixup:
-        fixup_offsets(data, slices)
-    if not hasattr(data, "edge_control"):
-        data.edge_control = None
+    _prepare(data, slices, fixup)
     return model.detect_submit(data, slices, conf_thres=conf_thres, iou_thres=iou_thres, agnostic=agnostic,
                                classifier=classifier)
 
@@ -124,26 +124,12 @@ def detect_stream(model, batches, depth=4, **kw):
     no handle reads a slot that has been rewritten; the batches the handles in flight hold are valid for ``slots - 1``
     further draws, one of which is the draw in progress: ``depth <= slots - 2`` is required (ValueError otherwise, also
     when the loader does not say how many slots it has)."""
-    from collections import deque
-    from .data import DeviceLoader
     depth = int(depth)
     if depth < 1:
         raise ValueError("detect_stream needs depth >= 1")
-    if isinstance(batches, DeviceLoader):
-        slots = getattr(batches, "_slots", None)
-        if not isinstance(slots, int):
-            raise ValueError("detect_stream cannot tell how many slots the loader has")
-        if depth > slots - 2:
-            raise ValueError("detect_stream(depth=%d) over a DeviceLoader needs slots >= depth + 2, the loader has %d"
-                             % (depth, slots))
+    _check_loader_depth("detect_stream", batches, depth)
     kw.setdefault("fixup", False)
-    flying = deque()
-    for data, slices in batches:
-        flying.append(detect_batch_async(model, data, slices, **kw))
-        if len(flying) >= depth:
-            yield flying.popleft().result()
-    while flying:
-        yield flying.popleft().result()
+    yield from _in_flight(_submissions(model, batches, None, kw, detect_batch_async), depth)
 
 
 def confusion_counts(y_true, y_pred, K):
@@ -166,10 +152,7 @@ def evaluate_batch_async(model, data, slices, fixup=True, **kw):
     ``evaluate_batch`` returns (the loss bit for bit) plus ``confusion``.  ``kw``: ``iou_thresholds``, ``conf_thres``,
     ``iou_thres``, ``classifier`` (default: the model's own).  ``data.labels`` and ``slices["bbox"]`` are left as they
     are; the criterion is DetectionLoss' by construction."""
-    if fixup:
-        fixup_offsets(data, slices)
-    if not hasattr(data, "edge_control"):
-        data.edge_control = None
+    _prepare(data, slices, fixup)
     return model.evaluate_submit(data, slices, **kw)
 
 
@@ -254,21 +237,19 @@ class EpochMetrics(object):
                 self._flagged.append((h, b, base, int(flags[b, 1])))
 
     def add(self, handle):
-        from .architecture import EvalHandle
         if not isinstance(handle, EvalHandle):
             raise TypeError("EpochMetrics.add takes the EvalHandle of evaluate_submit / evaluate_batch_async")
         if self._result is not None:
             raise RuntimeError("EpochMetrics.result() has closed this epoch: make a new EpochMetrics for the next one")
-        lay = handle._lay
-        if lay["T"] != self.T or lay["K"] != self.K:
+        if handle.T != self.T or handle.K != self.K:
             raise ValueError("the handle was submitted with %d thresholds and %d classes, the epoch holds %d and %d"
-                             % (lay["T"], lay["K"], self.T, self.K))
+                             % (handle.T, handle.K, self.T, self.K))
         self._poll()
-        B, stream = lay["B"], handle._stream
+        B, stream = handle.B, handle.stream
         key = stream.cuda_stream
         base, b = self._n_images, self._n_batches
         with torch.cuda.stream(stream):
-            rec = self._reserve(base + B, b + 1, handle._out.device, stream)
+            rec = self._reserve(base + B, b + 1, handle.device, stream)
             if self._seen.get(key) != self._ready_id:
                 stream.wait_event(self._ready)
                 rec.buf.record_stream(stream)
@@ -287,8 +268,7 @@ class EpochMetrics(object):
     def _upload_fallback(self, handle, b, base):
         """the synchronous evaluation of a batch whose tree was flagged -> its reserved slots"""
         res = handle._fallback()
-        lay = handle._lay
-        B, K, T = lay["B"], lay["K"], lay["T"]
+        B, T = handle.B, handle.T
         det = np.zeros((B, ops.MAX_DET, 6), dtype=np.float32)
         cnt = np.zeros(B, dtype=np.int32)
         tp = np.zeros((T, B, ops.MAX_DET), dtype=np.uint8)
@@ -299,8 +279,7 @@ class EpochMetrics(object):
                 det[i, :k, 4], det[i, :k, 5] = np.asarray(scores, dtype=np.float32), np.asarray(labels, dtype=np.float32)
                 tp[t, i, :k] = np.asarray(flags) != 0
         stats = np.concatenate([[res["n_true"], res["n_total"]], np.asarray(res["confusion"]).reshape(-1)]).astype(np.int32)
-        dev = handle._out.device
-        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(handle.device)
         ops.metrics_append_host(self._rec, up(det), up(cnt), up(tp), up(stats),
                                 up(np.asarray([res["loss"]["loss"]], dtype=np.float32)),
                                 up(np.asarray(res["labels"], dtype=np.float32).reshape(-1)), base, b)
@@ -349,39 +328,61 @@ class EpochMetrics(object):
 MAX_EVAL_STREAMS = 4
 
 
-def _submissions(model, batches, streams, kw):
-    """The handles of ``evaluate_stream``'s three ways to submit — current stream, a DeviceLoader under one stream, batch i
-    under streams[i % n] — in batch order; nothing is read (the ``metrics=`` form of evaluate_stream)."""
-    from .data import DeviceLoader
+def _submissions(model, batches, streams, kw, submit):
+    """The handles of ``submit(model, data, slices, **kw)`` — evaluate_batch_async or detect_batch_async — in batch order,
+    nothing read; the three ways to submit: on the current stream (streams None); a DeviceLoader under streams[0], the draws
+    included (the loader hands a slot back behind an event on the drawing stream); batch i under streams[i % n], behind an
+    event recorded on the caller's stream after the batch was drawn.  Every listed stream first waits for the caller's
+    stream at entry.  A handle is yielded outside its stream's ``with`` block: it is read under the caller's stream."""
     if streams is None:
         for data, slices in batches:
-            yield evaluate_batch_async(model, data, slices, **kw)
-    elif isinstance(batches, DeviceLoader):
-        entry = torch.cuda.Event()
-        entry.record(ops.current_stream_object())
-        streams[0].wait_event(entry)
+            yield submit(model, data, slices, **kw)
+        return
+    home = ops.current_stream_object()
+    entry = torch.cuda.Event()
+    entry.record(home)
+    for s in streams:
+        s.wait_event(entry)
+    if isinstance(batches, DeviceLoader):
         it = iter(batches)
         while True:
             with torch.cuda.stream(streams[0]):
                 nxt = next(it, None)
                 if nxt is None:
                     break
-                h = evaluate_batch_async(model, nxt[0], nxt[1], **kw)
+                h = submit(model, nxt[0], nxt[1], **kw)
             yield h
-    else:
-        home = ops.current_stream_object()
-        entry = torch.cuda.Event()
-        entry.record(home)
-        for s in streams:
-            s.wait_event(entry)
-        for i, (data, slices) in enumerate(batches):
-            s = streams[i % len(streams)]
-            drawn = torch.cuda.Event()
-            drawn.record(home)
-            s.wait_event(drawn)
-            with torch.cuda.stream(s):
-                h = evaluate_batch_async(model, data, slices, **kw)
-            yield h
+        return
+    for i, (data, slices) in enumerate(batches):
+        s = streams[i % len(streams)]
+        drawn = torch.cuda.Event()
+        drawn.record(home)
+        s.wait_event(drawn)
+        with torch.cuda.stream(s):
+            h = submit(model, data, slices, **kw)
+        yield h
+
+
+def _in_flight(handles, depth):
+    """``result()`` of every handle in order, handle i + depth drawn (= submitted) before handle i is read"""
+    flying = deque()
+    for h in handles:
+        flying.append(h)
+        if len(flying) >= depth:
+            yield flying.popleft().result()
+    while flying:
+        yield flying.popleft().result()
+
+
+def _check_loader_depth(name, batches, depth):
+    """over a DeviceLoader: depth <= slots - 2 (detect_stream's docstring says why)"""
+    if isinstance(batches, DeviceLoader):
+        slots = getattr(batches, "_slots", None)
+        if not isinstance(slots, int):
+            raise ValueError("%s cannot tell how many slots the loader has" % name)
+        if depth > slots - 2:
+            raise ValueError("%s(depth=%d) over a DeviceLoader needs slots >= depth + 2, the loader has %d"
+                             % (name, depth, slots))
 
 
 def evaluate_stream(model, batches, depth=4, streams=None, **kw):
@@ -399,8 +400,6 @@ def evaluate_stream(model, batches, depth=4, streams=None, **kw):
     ``metrics`` (a keyword of its own among ``kw``, default None): an ``EpochMetrics`` — every submitted handle goes to ``metrics.add`` instead of being read, and the
     generator yields the batch's number in the epoch; ``metrics.result()`` then is the epoch's report.  The same loader and
     stream rules; nothing limits the batches in flight but the polling of ``add``."""
-    from collections import deque
-    from .data import DeviceLoader
     depth = int(depth)
     metrics = kw.pop("metrics", None)
     if depth < 1:
@@ -409,60 +408,19 @@ def evaluate_stream(model, batches, depth=4, streams=None, **kw):
         streams = list(streams)
         if not 1 <= len(streams) <= MAX_EVAL_STREAMS:
             raise ValueError("evaluate_stream takes 1 to %d streams, got %d" % (MAX_EVAL_STREAMS, len(streams)))
-    if isinstance(batches, DeviceLoader):
-        if streams is not None and len(streams) > 1:
+        if isinstance(batches, DeviceLoader) and len(streams) > 1:
             raise ValueError("evaluate_stream over a DeviceLoader takes one stream: the loader's ring belongs to the stream "
                              "its batches are drawn on")
-        slots = getattr(batches, "_slots", None)
-        if not isinstance(slots, int):
-            raise ValueError("evaluate_stream cannot tell how many slots the loader has")
-        if depth > slots - 2:
-            raise ValueError("evaluate_stream(depth=%d) over a DeviceLoader needs slots >= depth + 2, the loader has %d"
-                             % (depth, slots))
+    _check_loader_depth("evaluate_stream", batches, depth)
     kw.setdefault("fixup", False)
+    if metrics is not None and not isinstance(metrics, EpochMetrics):
+        raise TypeError("evaluate_stream(metrics=) takes an EpochMetrics")
+    handles = _submissions(model, batches, streams, kw, evaluate_batch_async)
     if metrics is not None:
-        if not isinstance(metrics, EpochMetrics):
-            raise TypeError("evaluate_stream(metrics=) takes an EpochMetrics")
-        for h in _submissions(model, batches, streams, kw):
+        for h in handles:
             yield metrics.add(h)
-        return
-    flying = deque()
-    if streams is None:
-        for data, slices in batches:
-            flying.append(evaluate_batch_async(model, data, slices, **kw))
-            if len(flying) >= depth:
-                yield flying.popleft().result()
-    elif isinstance(batches, DeviceLoader):
-        # the draws themselves happen under the stream: the loader hands a slot back behind an event on the drawing stream
-        entry = torch.cuda.Event()
-        entry.record(ops.current_stream_object())
-        streams[0].wait_event(entry)
-        it = iter(batches)
-        while True:
-            with torch.cuda.stream(streams[0]):
-                nxt = next(it, None)
-                if nxt is None:
-                    break
-                flying.append(evaluate_batch_async(model, nxt[0], nxt[1], **kw))
-            if len(flying) >= depth:
-                yield flying.popleft().result()
     else:
-        home = ops.current_stream_object()
-        entry = torch.cuda.Event()
-        entry.record(home)
-        for s in streams:
-            s.wait_event(entry)
-        for i, (data, slices) in enumerate(batches):
-            s = streams[i % len(streams)]
-            drawn = torch.cuda.Event()
-            drawn.record(home)
-            s.wait_event(drawn)
-            with torch.cuda.stream(s):
-                flying.append(evaluate_batch_async(model, data, slices, **kw))
-            if len(flying) >= depth:
-                yield flying.popleft().result()
-    while flying:
-        yield flying.popleft().result()
+        yield from _in_flight(handles, depth)
 
 
 def _async_eval_applies(model, criterion, opt):
@@ -507,10 +465,18 @@ def test(model, test_loader, criterion, opt):
     confusion = None
     classifier = getattr(opt, "classifier", "softmax")
     with torch.no_grad():
+        acc = None
         if _device_metrics_apply(model, criterion, opt, steps):
             acc = EpochMetrics(model, ths, capacity_images=int(getattr(opt, "metrics_capacity", 1024)))
-            for _ in evaluate_stream(model, test_loader, depth=int(getattr(opt, "eval_depth", 4)), streams=_eval_streams(opt),
-                                     metrics=acc, fixup=True, classifier=classifier, iou_thresholds=ths):
+        if acc is not None or _async_eval_applies(model, criterion, opt):
+            reps = evaluate_stream(model, test_loader, depth=int(getattr(opt, "eval_depth", 4)), streams=_eval_streams(opt),
+                                   metrics=acc, fixup=True, classifier=classifier, iou_thresholds=ths)
+        else:
+            reps = (evaluate_batch(model, criterion, data, slices, classifier=classifier, iou_thresholds=ths,
+                                   device_post=bool(getattr(opt, "device_postprocess", False)))
+                    for data, slices in test_loader)
+        if acc is not None:
+            for _ in reps:
                 pass
             rep = acc.result()
             if rep is None:
@@ -518,13 +484,6 @@ def test(model, test_loader, criterion, opt):
             opt.test_report = {k: rep[k] for k in ("iou_thresholds", "map", "top1", "loss", "confusion", "map_all")}
             opt.test_value = rep["map"][-1]
             return opt.test_value
-        if _async_eval_applies(model, criterion, opt):
-            reps = evaluate_stream(model, test_loader, depth=int(getattr(opt, "eval_depth", 4)), streams=_eval_streams(opt),
-                                   fixup=True, classifier=classifier, iou_thresholds=ths)
-        else:
-            reps = (evaluate_batch(model, criterion, data, slices, classifier=classifier, iou_thresholds=ths,
-                                   device_post=bool(getattr(opt, "device_postprocess", False)))
-                    for data, slices in test_loader)
         for rep in reps:
             for t in range(steps):
                 metrics[t] += rep["sample_metrics"][t]

@@ -1365,12 +1365,24 @@ def detect_workspace_bytes(N, P, R, Ctot, K, B):
     return int(lib.yolat_detect_workspace_bytes(int(N), int(P), int(R), int(Ctot), int(K), int(B)))
 
 
+SEL_HEAD, SEL_STATUS = 4, 2          # yolat_predict_select's record: head words (total, tree flag, status, spare)
+
+
+def sel_words(B, R_cap):
+    """int32 words of that record (layout: include/yolat_hip.h): the head, B + 1 image offsets, at most R_cap rows"""
+    return SEL_HEAD + B + 1 + R_cap
+
+
+def sel_split(sel, B):
+    """(total, tree flag, status, image_off [B + 1], rows) of a record, a device tensor or a host copy (of the head alone, too)"""
+    return sel[0], sel[1], sel[SEL_STATUS], sel[SEL_HEAD:SEL_HEAD + B + 1], sel[SEL_HEAD + B + 1:]
+
+
 def detect_rows(logits, bbox, sel, B, R_cap, scale, softmax=True, out=None):
     """yolat_detect_rows (csrc/detect.hip): the pred rows of the asynchronous detection from the record yolat_predict_select
-    wrote.  logits [P, K], bbox [P, 4], sel [4 + B + 1 + R_cap] int32 (sel[0] = total rows, sel[4:] the per-image offsets,
-    then the proposal row of every output row), scale [B, 4] -> pred [R_cap, 4 + K]: row r < total equals the row
-    ``detect_scores`` gives on ``predict``'s logits and enlarged boxes, bit for bit; the spare rows behind are zero.  The
-    row count is read on the device; nothing is read back."""
+    wrote.  logits [P, K], bbox [P, 4], sel [sel_words(B, R_cap)] int32, scale [B, 4] -> pred [R_cap, 4 + K]: row r < total
+    equals the row ``detect_scores`` gives on ``predict``'s logits and enlarged boxes, bit for bit; the spare rows behind
+    are zero.  The row count is read on the device; nothing is read back."""
     lp = _f(logits, "logits")
     if logits.dim() != 2 or logits.shape[1] < 2:
         raise ValueError("detect_rows expects logits [P, K] with K >= 2")
@@ -1378,7 +1390,7 @@ def detect_rows(logits, bbox, sel, B, R_cap, scale, softmax=True, out=None):
     B, R_cap = int(B), int(R_cap)
     bp, sp = _dense2(bbox, "bbox", 4), _dense2(scale, "scale", 4)
     ip = _i(sel, torch.int32, "sel")
-    if bbox.shape[0] != P or B < 1 or scale.shape[0] != B or sel.dim() != 1 or sel.numel() < 4 + B + 1 + R_cap:
+    if bbox.shape[0] != P or B < 1 or scale.shape[0] != B or sel.dim() != 1 or sel.numel() < sel_words(B, R_cap):
         raise ValueError("detect_rows expects bbox [P, 4], scale [B, 4] and sel [4 + B + 1 + R_cap]")
     if out is None:
         out = torch.empty((R_cap, 4 + K), dtype=torch.float32, device=logits.device)
@@ -1395,7 +1407,7 @@ def evaluate_workspace_bytes(N, P, R, Ctot, K, B, G, T):
 def eval_rows(logits, labels, sel, B, R_cap, softmax=True):
     """yolat_eval_rows (csrc/evaluate.hip): the rows stage of the asynchronous evaluation from the record
     yolat_predict_select wrote.  logits [P, K] (the probabilities of a sigmoid model with softmax=False), labels [P] int64,
-    sel [4 + B + 1 + R_cap] int32 -> (loss [1] fp32, stats [2 + K * K] int32 = n_true, n_total, confusion[label, y_pred],
+    sel [sel_words(B, R_cap)] int32 -> (loss [1] fp32, stats [2 + K * K] int32 = n_true, n_total, confusion[label, y_pred],
     y_pred [R_cap] int32, y_true [R_cap] int32), all on the device.  The loss is bit for bit DetectionLoss' on the rows
     ``predict`` gathers; entries of y_pred / y_true behind sel[0] are not written.  Nothing is read back."""
     lp = _f(logits, "logits")
@@ -1404,7 +1416,7 @@ def eval_rows(logits, labels, sel, B, R_cap, softmax=True):
     P, K = int(logits.shape[0]), int(logits.shape[1])
     B, R_cap = int(B), int(R_cap)
     yp, ip = _i(labels, torch.int64, "labels"), _i(sel, torch.int32, "sel")
-    if labels.dim() != 1 or labels.shape[0] != P or B < 1 or sel.dim() != 1 or sel.numel() < 4 + B + 1 + R_cap:
+    if labels.dim() != 1 or labels.shape[0] != P or B < 1 or sel.dim() != 1 or sel.numel() < sel_words(B, R_cap):
         raise ValueError("eval_rows expects labels [P] and sel [4 + B + 1 + R_cap]")
     dev = logits.device
     loss = torch.empty(1, dtype=torch.float32, device=dev)
