@@ -464,12 +464,18 @@ __global__ void __launch_bounds__(256, NG == 1 ? 4 : 1) k_edge_uv_mlp2_mean(cons
   EDGE_STAMP(9);
   // ---- node side of the NEXT layer for this tile's nodes (EdgeNext, internal.hpp): [nn <= 16, 64] x [192, 64]^T
   if constexpr (NG == 1 && NEXT) {
-    // the first column tile's B fragments are fetched here, after the pass loop, and the other two under the previous
-    // tile's MFMAs: held from before the first barrier they cost 16 registers through the whole edge phase, which put
-    // the kernel over the 128 of four workgroups per CU
-    float bfa[16], bfb[16];
+    // all three column tiles' B fragments are fetched here in ONE batch of 48 loads, after the pass loop (nothing of the
+    // edge phase is live any more, so they fit the 128 registers of four workgroups per CU; held from before the first
+    // barrier they did not).  One round trip to L2 instead of three dependent ones: 16 MFMAs of 16x16x4 (~0.2 us) cover
+    // nothing of a round's latency.
+    float bf[3][16];
 #pragma unroll
-    for (int ks = 0; ks < 16; ++ks) bfa[ks] = nx.Wp[(wave * 16 + ks) * 64 + lane];
+    for (int t = 0; t < 3; ++t)
+#pragma unroll
+      for (int ks = 0; ks < 16; ++ks) bf[t][ks] = nx.Wp[((wave + 4 * t) * 16 + ks) * 64 + lane];
+    float nbias[3];                                  // in the same batch: fetched under a column tile's MFMAs they are a round trip each
+#pragma unroll
+    for (int t = 0; t < 3; ++t) nbias[t] = nx.bias[(wave + 4 * t) * 16 + (lane & 15)];
     // the loop above ended with a barrier (or never ran): Hs is free; rows >= nn hold the clamped load of row N-1 or
     // stale sums — finite or not, their products only reach output rows that are never stored
     float* frow = Hs + rb * LDH + 4 * q;
@@ -480,16 +486,12 @@ __global__ void __launch_bounds__(256, NG == 1 ? 4 : 1) k_edge_uv_mlp2_mean(cons
 #pragma unroll
     for (int t = 0; t < 3; ++t) {
       const int ct = wave + 4 * t;                   // 12 column tiles of 16: UV' 0..7, root' 8..11
-      if (t < 2) {
-#pragma unroll
-        for (int ks = 0; ks < 16; ++ks) bfb[ks] = nx.Wp[((ct + 4) * 16 + ks) * 64 + lane];
-      }
       const int col = ct * 16 + fr;
-      const float bias = nx.bias[col];
+      const float bias = nbias[t];
       f32x4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int ks = 0; ks < 16; ++ks)
-        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(Hs[fr * LDH + 4 * ks + fk], bfa[ks], acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(Hs[fr * LDH + 4 * ks + fk], bf[t][ks], acc, 0, 0, 0);
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int row = 4 * fk + r;
@@ -499,8 +501,6 @@ __global__ void __launch_bounds__(256, NG == 1 ? 4 : 1) k_edge_uv_mlp2_mean(cons
           else nx.root[(long)(n0 + row) * nx.ld_root + (col - 128)] = v;
         }
       }
-#pragma unroll
-      for (int ks = 0; ks < 16; ++ks) bfa[ks] = bfb[ks];
     }
   }
   EDGE_STAMP(10);
@@ -648,47 +648,74 @@ __device__ __forceinline__ void edge_s_tile(const EdgeNext& nx, int N, int r0, f
     if (row < N) nx.s_out[(long)row * nx.ld_so + colS] = fmaxf(fmaf(accS[r] + bS, scS, shS), 0.f);
   }
 }
-// node side of the NEXT layer for one tile's nodes (EdgeNext, internal.hpp): [nn <= 16, 64] x [192, 64]^T.  Hs must be free
-// (the pass loop ended with a barrier, or never ran); fz = the thread's final f_out columns of node rb.
-__device__ __forceinline__ void edge_next_node_side(const EdgeNext& nx, int n0, int nn, int rb, int q, int wave, int lane,
-                                                    const float4& fo0, float* Hs) {
-  // the first column tile's B fragments are fetched here, after the pass loop, and the other two under the previous
-  // tile's MFMAs: held from before the first barrier they cost 16 registers through the whole edge phase, which put
-  // the kernel over the 128 of four workgroups per CU
-  float bfa[16], bfb[16];
+// node side of the NEXT layer for the nodes of ALL of a workgroup's tiles [tA, tB) (EdgeNext, internal.hpp), run once after
+// the tile loop: per tile [nn <= 16, 64] x [192, 64]^T.  The B fragments depend on (wave, lane) only, so the 48 KB of Wp are
+// fetched once per workgroup, as one batch of 48 loads per lane, instead of three dependent rounds of 16 per tile.  The
+// tiles' finished f_out rows are re-read from global by the thread (rb, q) that wrote them (or left them as they were:
+// degree 0), in the same batch: nothing is held across the tile loop.  Up to four tiles' rows are staged into rows 16 i ..
+// of Hs (64 rows; free after the loop: it ended with a barrier or never ran) and each tile runs the three column-tile rounds
+// of the one-tile kernel on the held fragments: ks ascending, the same MFMA, bias added after, the same stores.
+__device__ __forceinline__ void edge_next_node_side_tiles(const EdgeNext& nx, const float* f_out, long ld_fo, int N, int npt,
+                                                          int tA, int tB, int rb, int q, int wave, int lane, float* Hs) {
+  // the rows of the group of tiles that starts at g0: rows of tiles past the group's last repeat that tile's and are never
+  // read.  The first group's re-reads lead the batch, ahead of the fragments: what waits for this workgroup's last f_out
+  // store then has every load of the phase in flight behind it
+  int g0 = tA, cnt = yl_min(4, tB - tA);
+  float4 fz[4];
+  auto load_rows = [&]() {
 #pragma unroll
-  for (int ks = 0; ks < 16; ++ks) bfa[ks] = nx.Wp[(wave * 16 + ks) * 64 + lane];
-  // rows >= nn hold the clamped load of row N-1 or stale sums — finite or not, their products only reach output rows
-  // that are never stored
-  float* frow = Hs + rb * EDGE_LDH + 4 * q;
-  const float4 fz = (rb < nn) ? fo0 : make_float4(0.f, 0.f, 0.f, 0.f);
-  frow[0] = fz.x; frow[1] = fz.y; frow[2] = fz.z; frow[3] = fz.w;
-  __syncthreads();
-  const int fr = lane & 15, fk = lane >> 4;
-#pragma unroll
-  for (int t = 0; t < 3; ++t) {
-    const int ct = wave + 4 * t;                   // 12 column tiles of 16: UV' 0..7, root' 8..11
-    if (t < 2) {
-#pragma unroll
-      for (int ks = 0; ks < 16; ++ks) bfb[ks] = nx.Wp[((ct + 4) * 16 + ks) * 64 + lane];
+    for (int i = 0; i < 4; ++i) {
+      const int n0 = (g0 + yl_min(i, cnt - 1)) * npt;
+      fz[i] = *reinterpret_cast<const float4*>(f_out + (long)yl_min(n0 + rb, N - 1) * ld_fo + 4 * q);
     }
-    const int col = ct * 16 + fr;
-    const float bias = nx.bias[col];
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+  };
+  load_rows();
+  float bf[3][16];
+  const float* wp = nx.Wp + (wave * 16 * 64 + lane);   // one base: the 48 loads differ by compile-time offsets
 #pragma unroll
-    for (int ks = 0; ks < 16; ++ks)
-      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(Hs[fr * EDGE_LDH + 4 * ks + fk], bfa[ks], acc, 0, 0, 0);
+  for (int t = 0; t < 3; ++t)
 #pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int row = 4 * fk + r;
-      if (row < nn) {
-        const float v = acc[r] + bias;
-        if (col < 128) nx.UV[(long)(n0 + row) * nx.ld_uv + col] = v;
-        else nx.root[(long)(n0 + row) * nx.ld_root + (col - 128)] = v;
+    for (int ks = 0; ks < 16; ++ks) bf[t][ks] = wp[(4 * t * 16 + ks) * 64];
+  const int fr = lane & 15, fk = lane >> 4;
+  float bias[3];
+#pragma unroll
+  for (int t = 0; t < 3; ++t) bias[t] = nx.bias[(wave + 4 * t) * 16 + fr];
+  for (;;) {
+    // rows >= nn are zero as in the one-tile kernel (their products only reach output rows that are never stored)
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int n0 = (g0 + yl_min(i, cnt - 1)) * npt;
+      float* frow = Hs + (16 * i + rb) * EDGE_LDH + 4 * q;
+      const bool in = rb < yl_min(npt, N - n0);
+      frow[0] = in ? fz[i].x : 0.f; frow[1] = in ? fz[i].y : 0.f; frow[2] = in ? fz[i].z : 0.f; frow[3] = in ? fz[i].w : 0.f;
+    }
+    __syncthreads();
+    for (int i = 0; i < cnt; ++i) {
+      const int n0 = (g0 + i) * npt;
+      const int nn = yl_min(npt, N - n0);
+#pragma unroll
+      for (int t = 0; t < 3; ++t) {
+        const int col = (wave + 4 * t) * 16 + fr;    // 12 column tiles of 16: UV' 0..7, root' 8..11
+        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int ks = 0; ks < 16; ++ks)
+          acc = __builtin_amdgcn_mfma_f32_16x16x4f32(Hs[(16 * i + fr) * EDGE_LDH + 4 * ks + fk], bf[t][ks], acc, 0, 0, 0);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int row = 4 * fk + r;
+          if (row < nn) {
+            const float v = acc[r] + bias[t];
+            if (col < 128) nx.UV[(long)(n0 + row) * nx.ld_uv + col] = v;
+            else nx.root[(long)(n0 + row) * nx.ld_root + (col - 128)] = v;
+          }
+        }
       }
     }
-#pragma unroll
-    for (int ks = 0; ks < 16; ++ks) bfa[ks] = bfb[ks];
+    g0 += 4;
+    if (g0 >= tB) break;
+    cnt = yl_min(4, tB - g0);
+    load_rows();
+    __syncthreads();                                 // the previous group's rows have been read
   }
 }
 
@@ -702,7 +729,9 @@ __device__ __forceinline__ void edge_next_node_side(const EdgeNext& nx, int n0, 
 // t's end: its 64 dst ids, 64 src ids and 17 row_ptr entries are ONE load per thread, issued at the top of tile t next to
 // that tile's f_out rows, landed with tile t's gathers and parked in the other half of a 2 x 145-int LDS array).  Tiles
 // after the first start at the UV gather.  Per tile every product, sum and rounding is k_edge_uv_mlp2_mean<1, *>'s, in
-// its order (the bodies above): bit-identical results (tests/test_gpu_eval_regime.py).
+// its order (the bodies above): bit-identical results (tests/test_gpu_eval_regime.py).  The next layer's node side (NEXT)
+// runs once per workgroup, behind the last tile (edge_next_node_side_tiles): the packed weight is fetched once, not per tile
+// (tests/test_gpu_edge_next_once.py).
 // Grid: wgs = ceil(tiles / T) tile workgroups, then the node-branch tiles and the pooling rider as in the one-tile kernel.
 // Bound like it: 256 threads, <= 128 VGPRs, no scratch, 4 x LDS <= 160 KB (tests/test_edge_mt_resources_host.py).
 // ------------------------------------------------------------------------------------------------
@@ -752,8 +781,9 @@ __global__ void __launch_bounds__(256, 4) k_edge_mt_uv_mlp2_mean(const float* __
     edge_w2_store(W2s, tid, rw2);
   }
   // the per-column constants of the two layers: loaded from global once.  Without the next layer's node side they stay in
-  // registers through all tiles; with it (32 B-fragment registers per tile) they would not fit the 128 of four workgroups
-  // per CU, so that instance parks them in LDS (2.5 KB) and re-reads them at the top of every tile
+  // registers through all tiles; the instance with it parks them in LDS (2.5 KB) and re-reads them at the top of every tile
+  // (from when the node side ran per tile with 32 B-fragment registers; kept: with the node side behind the loop the
+  // registers-only form was not measured)
   __shared__ EdgeL1 k1s[NEXT ? 16 : 1];
   __shared__ float c2s[NEXT ? 3 * 64 : 1];
   EdgeL1 k1;
@@ -803,14 +833,19 @@ __global__ void __launch_bounds__(256, 4) k_edge_mt_uv_mlp2_mean(const float* __
       edge_aggregate<1>(Hs, c0, rb, q, nn, my_b, my_e, sum);
       __syncthreads();
     }
-    edge_mean_out<1>(f_out, ld_fo, n0, rb, q, nn, my_b, my_e, sum, fo);
     if constexpr (NEXT) {
-      // the B-fragment addresses do not depend on the tile: hoisted out of the tile loop they are 96 registers held through
-      // every edge phase (spills at 128), so they are derived per tile from a lane id the compiler cannot see through
-      int lane_t = lane;
-      asm volatile("" : "+v"(lane_t));
-      edge_next_node_side(nx, n0, nn, rb, q, wave, lane_t, fo[0], Hs);
+      // a use of the f_out rows on every path (they landed with the gathers): a lane that stores nothing would otherwise leave
+      // the loop with the load formally pending, and the wait for it behind the loop also waits for the last tile's store
+      asm volatile("" ::"v"(fo[0].x), "v"(fo[0].y), "v"(fo[0].z), "v"(fo[0].w));
     }
+    edge_mean_out<1>(f_out, ld_fo, n0, rb, q, nn, my_b, my_e, sum, fo);
+  }
+  if constexpr (NEXT) {
+    // the B-fragment addresses are derived here from a lane id the compiler cannot see through: computed above the tile loop
+    // they would be registers held through every edge phase
+    int lane_t = lane;
+    asm volatile("" : "+v"(lane_t));
+    edge_next_node_side_tiles(nx, f_out, ld_fo, N, npt, tA, tB, rb, q, wave, lane_t, Hs);
   }
 }
 
@@ -1286,6 +1321,29 @@ extern "C" int yolat_edge_uv_mlp2_mean_eval_mt(const float* UV, int64_t ld_uv, c
                                                yolat_stream_t stream) {
   return yl_edge_uv_mlp2_mean_eval_impl(UV, ld_uv, src_csr, dst_csr, attr_csr, row_ptr, N, E, Wc4, b1, s1, t1, W2, b2, s2,
                                         t2, C, f_out, ld_fo, YOLAT_EDGE_TILES, nullptr, nullptr, nullptr, nullptr, stream,
+                                        tiles_per_wg);
+}
+
+// yolat_edge_uv_mlp2_mean_eval_mt with the next layer's node side (EdgeNext, internal.hpp) in the same launch, as the eval
+// forward's chain issues it: Wp [192 x 64 packed], bias [192] -> UV' [N, ld_uvn >= 128], root' [N, ld_root >= 64]; s_in
+// (nullable: no node-branch tiles) . Wn^T, bn (nullable), sn, tn -> s_out.  *did_next = 1 when the launch carried it
+// (tiles of <= 16 nodes).  For tests and tools, not part of the C ABI header.
+extern "C" int yolat_debug_edge_uv_mlp2_mean_eval_next(const float* UV, int64_t ld_uv, const int32_t* src_csr,
+                                                       const int32_t* dst_csr, const float* attr_csr, const int32_t* row_ptr,
+                                                       int64_t N, int64_t E, const float* Wc4, const float* b1, const float* s1,
+                                                       const float* t1, const float* W2, const float* b2, const float* s2,
+                                                       const float* t2, int64_t C, float* f_out, int64_t ld_fo, int tiles_per_wg,
+                                                       const float* Wp, const float* bias, float* UVn, int64_t ld_uvn,
+                                                       float* root, int64_t ld_root, const float* s_in, int64_t ld_si,
+                                                       const float* Wn, const float* bn, const float* sn, const float* tn,
+                                                       float* s_out, int64_t ld_so, int* did_next, yolat_stream_t stream) {
+  if (N <= 0 || !Wp || ld_uvn < 2 * C || ld_root < C || (s_in && ld_so < C)) return YOLAT_E_INVALID;
+  EdgeNext nx{};
+  nx.Wp = Wp; nx.bias = bias; nx.UV = UVn; nx.ld_uv = (long)ld_uvn; nx.root = root; nx.ld_root = (long)ld_root;
+  nx.s_in = s_in; nx.ld_si = (long)ld_si; nx.Wn = Wn; nx.bn = bn; nx.sn = sn; nx.tn = tn; nx.s_out = s_out; nx.ld_so = (long)ld_so;
+  nx.s_tiles = s_in ? (int)yl_cdiv(N, 64) : 0;
+  return yl_edge_uv_mlp2_mean_eval_impl(UV, ld_uv, src_csr, dst_csr, attr_csr, row_ptr, N, E, Wc4, b1, s1, t1, W2, b2, s2,
+                                        t2, C, f_out, ld_fo, YOLAT_EDGE_TILES, nullptr, nullptr, &nx, did_next, stream,
                                         tiles_per_wg);
 }
 

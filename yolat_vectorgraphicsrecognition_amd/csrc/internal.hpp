@@ -181,3 +181,14 @@ int yl_bwd_w_x6(const float* dY, int64_t lddy, int64_t M, int64_t Nout, const fl
 long long* yl_gemm_sk_dma_stamps();
 // switch of the LDS-DMA skinny GEMM and its stamps; exported for tools and tests, not part of the C ABI header (dense.hip)
 extern "C" void yolat_debug_gemm_sk_dma(int on, long long* stamps);
+// yolat_edge_uv_mlp2_mean_eval_mt with an EdgeNext built from plain arguments (s_in == nullptr: no node-branch tiles), the way
+// the eval forward's chain launches it; exported for tools and tests, not part of the C ABI header (edge.hip)
+extern "C" int yolat_debug_edge_uv_mlp2_mean_eval_next(const float* UV, int64_t ld_uv, const int32_t* src_csr,
+                                                       const int32_t* dst_csr, const float* attr_csr, const int32_t* row_ptr,
+                                                       int64_t N, int64_t E, const float* Wc4, const float* b1, const float* s1,
+                                                       const float* t1, const float* W2, const float* b2, const float* s2,
+                                                       const float* t2, int64_t C, float* f_out, int64_t ld_fo, int tiles_per_wg,
+                                                       const float* Wp, const float* bias, float* UVn, int64_t ld_uvn,
+                                                       float* root, int64_t ld_root, const float* s_in, int64_t ld_si,
+                                                       const float* Wn, const float* bn, const float* sn, const float* tn,
+                                                       float* s_out, int64_t ld_so, int* did_next, yolat_stream_t stream);
