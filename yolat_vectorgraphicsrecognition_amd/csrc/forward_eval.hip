@@ -14,8 +14,22 @@ struct Plan {
   uint16_t* Zs;                                        // Z pre-split for the skinny bf16x6 classifier (few proposals)
   float* act_work;                                     // leaky activation: BatchNorm output of a fusion column range
   float* rn_work;                                      // row norm, generic route: a row range of the fusion block's output
+  uint32_t* tail_tickets; float* tail_slabs;           // classifier layers 2 + 3 as one launch (cls_tail.hip), in c2's / Z's place; null: two launches
   size_t bytes;
 };
+
+// Do classifier layers 2 and 3 run as the one folded launch (cls_tail.hip)?  A function of the descriptor, P and the two
+// switches (both read once), so the workspace sizing and the forward agree: layer 2 is the shape launch_gemm_nt (dense.hip)
+// sends to k_gemm_nt_sk, BatchNorm + ReLU, fp32 route, whole 32-column tiles, at most 32 classes.
+bool cls_tail_fold(const yolat_model_eval* m, long P, bool cls_x6) {
+  return yl_cls_tail_on() && !yl_strict_fp32() && !cls_x6 && m->act == YOLAT_ACT_RELU && m->norm == YOLAT_NORM_BATCH &&
+         m->Wc2 && m->Wc3 && yl_aligned16(m->Wc3) && yl_cls_tail_shape_ok(P, m->H1, m->H2, m->n_classes);
+}
+bool cls_x6_route(const yolat_model_eval* m, bool have_zs) {
+  bool x6 = have_zs && m->H1 % 16 == 0 && m->H2 % 16 == 0;
+  for (int i = 0; i < 3; ++i) x6 = x6 && m->Wc_x6[i] != nullptr && m->tc_fold[i] != nullptr;
+  return x6;
+}
 
 Plan carve(const yolat_model_eval* m, long N, long E, long P, void* ws) {
   Carver c{reinterpret_cast<char*>(ws), 0};
@@ -44,6 +58,14 @@ Plan carve(const yolat_model_eval* m, long N, long E, long P, void* ws) {
   p.act_work = m->act != YOLAT_ACT_RELU && !act_x6 ? c.take<float>((long)yolat_fusion_pair_eval_act_work_elems(N, F)) : nullptr;
   // (likewise: only a row-norm descriptor whose fusion block takes the materialising route carves this)
   p.rn_work = m->norm != YOLAT_NORM_BATCH && !(act_x6 && yl_rn_fused(m, N)) ? c.take<float>((long)yolat_fusion_pair_eval_rn_work_elems(N, F)) : nullptr;
+  // The classifier tail takes nothing of its own: the folded launch never stores c2, so its tickets stand where c2 would
+  // (no other launch of a folding forward writes there: zeroed by an un-primed forward and left zero by every forward, like
+  // the CSR-build counters — the `primed` promise covers them), and its slabs lie in Z, dead once classifier 1 has read it.
+  // By the sizes and the switches alone: the forward's own conditions (cls_tail_fold) only ever narrow this.
+  const bool fold = yl_cls_tail_on() && !yl_strict_fp32() && yl_cls_tail_shape_ok(P, m->H1, m->H2, m->n_classes) &&
+                    (long)yl_cls_tail_slab_elems(P, m->H2) <= P * 2 * (F + D);
+  p.tail_tickets = fold ? reinterpret_cast<uint32_t*>(p.c2) : nullptr;
+  p.tail_slabs = fold ? p.Z : nullptr;
   p.bytes = c.off + 256;
   return p;
 }
@@ -100,6 +122,9 @@ StageRec& stage_rec(const char* name, double flops, double bytes) {
       YL_TRY(call);                                                         \
     }                                                                       \
   } while (0)
+
+// a stage's name is formatted only for the profiler: five or six snprintf per forward otherwise, on the enqueue path
+#define YL_NAME(buf, ...) do { if (g_profile) snprintf(buf, sizeof buf, __VA_ARGS__); } while (0)
 
 // stage hooks for the other whole-forward entry points (bf16_eval.hip)
 namespace { int g_open_stage = -1; }
@@ -333,6 +358,7 @@ static int forward_eval_impl(const yolat_model_eval* m, const float* x, int64_t 
 
   // ---- graph structure (CSR by destination, e_attr in CSR order, proposal segments)
   char nm[128];
+  nm[0] = 0;
   // The node side of layer 0 (UV products, root Linear, node-branch Linear) reads only x: its GEMM tiles are
   // co-scheduled with the last, latency-bound pre-processing launch instead of being a launch of their own.
   const yolat_conv_eval& cv0 = m->conv[0];
@@ -414,7 +440,7 @@ static int forward_eval_impl(const yolat_model_eval* m, const float* x, int64_t 
         float* uv_l = next_done ? uv_next : p.UV;
         if (!(l == 0 && node0_in_prep) && !next_done) {
           uv_l = p.UV;
-          snprintf(nm, sizeof nm, "node_uv[UV | lin_r | mlp_node, N x %ld -> %ld+%ld+%ld]", (long)cv.Cin, 2 * C, C, C);
+          YL_NAME(nm, "node_uv[UV | lin_r | mlp_node, N x %ld -> %ld+%ld+%ld]", (long)cv.Cin, 2 * C, C, C);
           // large graphs: the three GEMMs as bf16x6-emulated products on the rows kernel (A read once per 256 rows);
           // small ones stay on the fp32 64x64 tiles (more workgroups: latency).  Measured per launch: N = 200 k 94 -> 89 us,
           // N = 43.5 k 26 = 26 us, N = 10 k 12.4 -> 18 us
@@ -450,10 +476,10 @@ static int forward_eval_impl(const yolat_model_eval* m, const float* x, int64_t 
           // that GEMM set: reads s, writes UV' / root' / s')
           const bool with_next = nx.Wp != nullptr;
           if (with_next)
-            snprintf(nm, sizeof nm, "edge_uv_mlp2_mean+node_uv_next[E x (U+V+attr) -> %ld -> %ld -> mean; N x %ld -> %ld+%ld+%ld]",
+            YL_NAME(nm, "edge_uv_mlp2_mean+node_uv_next[E x (U+V+attr) -> %ld -> %ld -> mean; N x %ld -> %ld+%ld+%ld]",
                      C, C, C, 2 * C, C, C);
           else
-            snprintf(nm, sizeof nm, "edge_uv_mlp2_mean[E x (U+V+attr) -> %ld -> %ld -> mean]", C, C);
+            YL_NAME(nm, "edge_uv_mlp2_mean[E x (U+V+attr) -> %ld -> %ld -> mean]", C, C);
           // bytes: SURVEY.md 8(d) B_agg(l) of the UNFACTORISED layer, E ((2 Cin + 4) 4 + 2 * 4) + N C 4 — the credit figure
           // (what the kernel has to move is priced in bench.py executed_pricing)
           YL_STAGE(nm, 2.0 * E * (4.0 * C + C * C) + (with_next ? 8.0 * N * C * C : 0.0),
@@ -476,12 +502,12 @@ static int forward_eval_impl(const yolat_model_eval* m, const float* x, int64_t 
       // three launches per layer: edge MLP (hidden activation in LDS); root Linear | node-branch Linear as one
       // paired GEMM launch; CSR mean accumulated into the root output.
       if (E > 0) {
-        snprintf(nm, sizeof nm, "edge_mlp2[E x %ld -> %ld -> %ld, gathered]", (long)K1, C, C);
+        YL_NAME(nm, "edge_mlp2[E x %ld -> %ld -> %ld, gathered]", (long)K1, C, C);
         YL_STAGE(nm, 2.0 * E * (K1 * C + C * C), E * (K1 * 4.0 + 8.0) + 4.0 * E * C,
                  yolat_edge_mlp2_eval(f_in, ld_f, N, cv.Cin, p.src, p.dst, p.attr, E, cv.W1, cv.b1, cv.s1, cv.t1,
                                       cv.W2, cv.b2, cv.s2, cv.t2, C, p.H2, C, stream));
       }
-      snprintf(nm, sizeof nm, "node_pair[lin_r | mlp_node, N x %ld -> %ld]", (long)cv.Cin, C);
+      YL_NAME(nm, "node_pair[lin_r | mlp_node, N x %ld -> %ld]", (long)cv.Cin, C);
       YL_STAGE(nm, 4.0 * N * cv.Cin * C, 8.0 * (N * cv.Cin + N * C),
                yolat_node_side_eval(f_in, ld_f, s_in, ld_s, N, cv.Cin, cv.Wr, cv.br, cv.Wn, cv.bn, cv.sn, cv.tn,
                                     nullptr, C, p.row_ptr, 0, C, f_out, ld_out, s_out, ld_out, stream));
@@ -492,16 +518,16 @@ static int forward_eval_impl(const yolat_model_eval* m, const float* x, int64_t 
       }
     } else {
     // out = lin_r(x)
-    snprintf(nm, sizeof nm, "lin_r[N x %ld -> %ld]", (long)cv.Cin, C);
+    YL_NAME(nm, "lin_r[N x %ld -> %ld]", (long)cv.Cin, C);
     YL_STAGE(nm, 2.0 * N * cv.Cin * C, 4.0 * (N * cv.Cin + N * C + C * cv.Cin),
              yolat_linear_fwd(f_in, ld_f, N, cv.Cin, nullptr, nullptr, 0, cv.Wr, cv.Cin, cv.br, C, nullptr,
                               nullptr, 0, f_out, ld_out, 0, nullptr, stream));
     if (E > 0) {
-      snprintf(nm, sizeof nm, "edge_lin1[E x %ld -> %ld, gathered]", (long)K1, C);
+      YL_NAME(nm, "edge_lin1[E x %ld -> %ld, gathered]", (long)K1, C);
       YL_STAGE(nm, 2.0 * E * K1 * C, E * (K1 * 4.0 + 8.0) + 4.0 * E * C,
                yolat_edge_lin1_fwd(f_in, ld_f, N, cv.Cin, p.src, p.dst, p.attr, E, cv.W1, 2 * cv.Cin + 4,
                                    cv.b1, C, cv.s1, cv.t1, 1, p.H1, C, nullptr, stream));
-      snprintf(nm, sizeof nm, "edge_lin2[E x %ld -> %ld]", C, C);
+      YL_NAME(nm, "edge_lin2[E x %ld -> %ld]", C, C);
       YL_STAGE(nm, 2.0 * E * C * C, 8.0 * E * C,
                yolat_linear_fwd(p.H1, C, E, C, nullptr, nullptr, 0, cv.W2, C, cv.b2, C, cv.s2, cv.t2, 1, p.H2,
                                 C, 0, nullptr, stream));
@@ -509,7 +535,7 @@ static int forward_eval_impl(const yolat_model_eval* m, const float* x, int64_t 
                yolat_csr_mean_fwd(p.H2, C, C, nullptr, nullptr, 0, p.row_ptr, N, f_out, ld_out, 1, stream));
     }
     // node branch
-    snprintf(nm, sizeof nm, "mlp_node[N x %ld -> %ld]", (long)cv.Cin, C);
+    YL_NAME(nm, "mlp_node[N x %ld -> %ld]", (long)cv.Cin, C);
     YL_STAGE(nm, 2.0 * N * cv.Cin * C, 4.0 * (N * cv.Cin + N * C + C * cv.Cin),
              yolat_linear_fwd(s_in, ld_s, N, cv.Cin, nullptr, nullptr, 0, cv.Wn, cv.Cin, cv.bn, C, cv.sn, cv.tn, 1,
                               s_out, ld_out, 0, nullptr, stream));
@@ -529,7 +555,7 @@ static int forward_eval_impl(const yolat_model_eval* m, const float* x, int64_t 
   }
   // fusion block over the nodes + per-proposal max, and fusion_block_super over the per-proposal means
   // (arch:61-63,65-69,122): two independent GEMMs in one flattened launch
-  snprintf(nm, sizeof nm, "fusion_gemm+segmax[N x %ld -> %ld -> P] | super[P x %ld -> %ld]", D, F, D, F);
+  YL_NAME(nm, "fusion_gemm+segmax[N x %ld -> %ld -> P] | super[P x %ld -> %ld]", D, F, D, F);
   if (rn && fusion_x6 && yl_rn_fused(m, N)) {
     // GEMM + row norm + ReLU + per-proposal max in one launch; Wf_hi.. are the centred weights (yolat_hip.h).  Its time is
     // flat in N up to one workgroup per CU (93 us), the materialising route's grows with N: below ~12 k rows that one wins
@@ -576,8 +602,7 @@ static int forward_eval_impl(const yolat_model_eval* m, const float* x, int64_t 
                                               ZW, P, m->Wfs, m->bfs, m->sfs, m->tfs, p.Z + F + D, ZW, stream));
   // ---- classifier (arch:91-93,127-128)
   // few proposals: the skinny bf16x6 kernel (one workgroup per 32 x 32 outputs, weights re-read per 32 rows)
-  bool cls_x6 = p.Zs != nullptr && m->H1 % 16 == 0 && m->H2 % 16 == 0;
-  for (int i = 0; i < 3; ++i) cls_x6 = cls_x6 && m->Wc_x6[i] != nullptr && m->tc_fold[i] != nullptr;
+  const bool cls_x6 = cls_x6_route(m, p.Zs != nullptr);
   // the bf16x6 GEMM wins once there are enough 128-row tiles to run without a deep K split (measured: P = 2000
   // 41 vs 58 us, P = 8000 129 vs 187 us; P = 400: 21 us either way — profiles/r02_gemm_x6_cls1.txt)
   const bool cls1_gx = m->Wc1_gx && m->tc1_gx && ZW % 16 == 0 && P >= YOLAT_CLS1_X6_MIN_ROWS;
@@ -588,7 +613,7 @@ static int forward_eval_impl(const yolat_model_eval* m, const float* x, int64_t 
   const float *sc1 = rn ? nullptr : m->sc1, *tc1 = rn ? nullptr : m->tc1, *sc2 = rn ? nullptr : m->sc2, *tc2 = rn ? nullptr : m->tc2;
   const bool cls1_sk = sk_x6_on && !cls1_gx && !cls_x6 && !yl_strict_fp32() && ZW >= 1024 && ZW % 128 == 0 &&
                        (long)yl_cdiv(P, 64) * yl_cdiv(m->H1, 64) < 160 && yl_aligned16(p.Z) && yl_aligned16(m->Wc1);
-  snprintf(nm, sizeof nm, "cls1[P x %ld -> %ld]", ZW, (long)m->H1);
+  YL_NAME(nm, "cls1[P x %ld -> %ld]", ZW, (long)m->H1);
   YL_STAGE(nm, 2.0 * P * ZW * m->H1, 4.0 * (P * ZW + ZW * m->H1 + P * m->H1),
            cls1_gx ? yolat_gemm_x6(p.Z, ZW, P, ZW, m->Wc1_gx, m->tc1_gx, relu, m->H1, p.c1, m->H1, p.gx_work, stream)
            : cls_x6 ? cls1_x6(p.Z, ZW, P, p.Zs, m->Wc_x6[0], m->tc_fold[0], relu, m->H1, p.c1, stream)
@@ -602,7 +627,18 @@ static int forward_eval_impl(const yolat_model_eval* m, const float* x, int64_t 
   if (leaky)
     YL_STAGE("cls1_act[P x H1]", 1.0 * P * m->H1, 8.0 * P * m->H1,
              yolat_scale_shift_act(p.c1, m->H1, P, m->H1, nullptr, nullptr, m->act_slope[2], p.c1, m->H1, stream));
-  snprintf(nm, sizeof nm, "cls2[P x %ld -> %ld]", (long)m->H1, (long)m->H2);
+  // layers 2 + 3 as one launch (cls_tail.hip): layer 3's partial products ride in layer 2's tiles, the last workgroup of a
+  // row tile sums them.  A forward on a prepared graph is never primed (it zeroes the tickets first) and folds as well: the
+  // two forms of a batch give the same bytes.
+  if (p.tail_tickets != nullptr && relu && cls_tail_fold(m, P, cls_x6)) {
+    YL_NAME(nm, "cls2+cls3[P x %ld -> %ld -> %d]", (long)m->H1, (long)m->H2, (int)m->n_classes);
+    YL_STAGE(nm, 2.0 * P * m->H2 * (m->H1 + m->n_classes),
+             4.0 * (P * m->H1 + m->H1 * m->H2 + m->H2 * m->n_classes + P * m->n_classes),
+             yl_cls_tail_eval_impl(p.c1, m->H1, P, m->H1, m->Wc2, m->H1, m->bc2, sc2, tc2, m->H2, m->Wc3, m->H2, m->bc3,
+                                   m->n_classes, logits, ld_logits, p.tail_tickets, p.tail_slabs, primed, nullptr, 0, stream));
+    return 0;
+  }
+  YL_NAME(nm, "cls2[P x %ld -> %ld]", (long)m->H1, (long)m->H2);
   YL_STAGE(nm, 2.0 * P * m->H1 * m->H2, 4.0 * (P * m->H1 + m->H1 * m->H2 + P * m->H2),
            cls_x6 ? yolat_linear_x6(p.c1, m->H1, P, m->H1, m->Wc_x6[1], m->tc_fold[1], relu, m->H2, p.c2, m->H2, stream)
                   : yolat_linear_fwd(p.c1, m->H1, P, m->H1, nullptr, nullptr, 0, m->Wc2, m->H1, m->bc2, m->H2, sc2,
@@ -614,7 +650,7 @@ static int forward_eval_impl(const yolat_model_eval* m, const float* x, int64_t 
   if (leaky)
     YL_STAGE("cls2_act[P x H2]", 1.0 * P * m->H2, 8.0 * P * m->H2,
              yolat_scale_shift_act(p.c2, m->H2, P, m->H2, nullptr, nullptr, m->act_slope[3], p.c2, m->H2, stream));
-  snprintf(nm, sizeof nm, "cls3[P x %ld -> %d]", (long)m->H2, (int)m->n_classes);
+  YL_NAME(nm, "cls3[P x %ld -> %d]", (long)m->H2, (int)m->n_classes);
   YL_STAGE(nm, 2.0 * P * m->H2 * m->n_classes, 4.0 * (P * m->H2 + m->H2 * m->n_classes + P * m->n_classes),
            cls_x6 ? yolat_linear_x6(p.c2, m->H2, P, m->H2, m->Wc_x6[2], m->tc_fold[2], 0, m->n_classes, logits,
                                     ld_logits, stream)

@@ -192,3 +192,23 @@ extern "C" int yolat_debug_edge_uv_mlp2_mean_eval_next(const float* UV, int64_t 
                                                        float* root, int64_t ld_root, const float* s_in, int64_t ld_si,
                                                        const float* Wn, const float* bn, const float* sn, const float* tn,
                                                        float* s_out, int64_t ld_so, int* did_next, yolat_stream_t stream);
+// The last two classifier layers of the fp32 eval forward as one launch (cls_tail.hip): layer 2 on the split-K tiles of
+// k_gemm_nt_sk, layer 3 as per-tile partial products that the last workgroup of a row tile sums.  yl_cls_tail_on: the
+// YOLAT_CLS_TAIL_FOLD switch; yl_cls_tail_shape_ok: a function of the sizes alone, so the workspace sizing and the forward
+// agree; tickets (yl_cls_tail_ticket_elems words, zero before the launch unless !primed, zero after it) and slabs
+// (yl_cls_tail_slab_elems floats, 16-byte aligned) are the caller's.  c2_dbg != nullptr: the c2 tile is stored as well.
+bool yl_cls_tail_on();
+bool yl_cls_tail_shape_ok(int64_t P, int64_t H1, int64_t H2, int64_t n_classes);
+size_t yl_cls_tail_ticket_elems(int64_t P);
+size_t yl_cls_tail_slab_elems(int64_t P, int64_t H2);
+int yl_cls_tail_eval_impl(const float* c1, int64_t ldc1, int64_t P, int64_t H1, const float* W2, int64_t ldw2, const float* b2,
+                          const float* s2, const float* t2, int64_t H2, const float* W3, int64_t ldw3, const float* b3,
+                          int64_t n_classes, float* logits, int64_t ld_logits, uint32_t* tickets, float* slabs, bool primed,
+                          float* c2_dbg, int64_t ld_dbg, yolat_stream_t stream);
+// layers 2 + 3 as an op over one work buffer, routed like the forward (fold or two launches); exported for tools and tests, not part of the C ABI header (cls_tail.hip)
+extern "C" size_t yolat_debug_cls_tail_work_bytes(int64_t P, int64_t H2);
+extern "C" int yolat_debug_cls_tail_eval(const float* c1, int64_t ldc1, int64_t P, int64_t H1, const float* W2, int64_t ldw2,
+                                         const float* b2, const float* s2, const float* t2, int64_t H2, const float* W3,
+                                         int64_t ldw3, const float* b3, int64_t n_classes, float* logits, int64_t ld_logits,
+                                         void* work, int primed, float* c2_dbg, int64_t ld_dbg, int* folded,
+                                         yolat_stream_t stream);
