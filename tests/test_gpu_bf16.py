@@ -83,9 +83,11 @@ def test_bf16_eval_forward_vs_reference_golden(kind, golden_dir):
 
 
 @pytest.mark.parametrize("cin,blocks,blocks_out,classes,seed", [(5, 2, 2, 17, 1), (6, 3, 2, 22, 2), (5, 4, 2, 17, 3),
-                                                                 (3, 2, 1, 5, 4), (5, 4, 4, 17, 5), (5, 6, 5, 17, 6)])
+                                                                 (3, 2, 1, 5, 4), (5, 4, 4, 17, 5), (5, 6, 5, 17, 6),
+                                                                 (5, 3, 3, 17, 7)])
 def test_bf16_eval_forward_vs_cpu_oracle(cin, blocks, blocks_out, classes, seed):
-    """model shapes incl. the YOLaT++ depth (n_blocks=4, n_blocks_out=2), the 256-wide (n_blocks_out=4) and the
+    """model shapes incl. the YOLaT++ depth (n_blocks=4, n_blocks_out=2), the 192-wide (n_blocks_out=3: the rows kernel's
+    zero-filled LDS columns), the 256-wide (n_blocks_out=4) and the
     > 256-wide (n_blocks_out=5: per-tile fallback of the fusion GEMM) concatenations, on a ragged graph (proposals of 2..40 nodes,
     nodes without in-edges, duplicate edges) against the CPU oracle in fp32."""
     yv = _yv()

@@ -48,7 +48,7 @@ least 21 x the bound (dW on `random`).
 Eval (test_fusion_pair_eval_vs_fp64): yolat_fusion_pair_eval (fp32 MFMA) and yolat_fusion_pair_eval_x6 (bf16x6 rows
 kernel with the FX_NP LDS table) at the same layouts, D = 64 and D = 128 (different row tiles, FxShape), against float64
 index_reduce_(amax) with empty proposals at 0: values only (the eval kernels return no arg).  The bf16 eval rows kernel
-(fusion_h8.hip) has no entry point of its own and is not covered here.
+(fusion_h8.hip) and the other routes of the bf16 fusion pair: tests/test_gpu_bf16_eval_stages.py.
 """
 import json
 import os

@@ -692,15 +692,82 @@ int model_ok(const yolat_model_eval_bf16* mh) {
 }
 
 template <class AL>
-int launch_hgemm(const AL& A, const HOp& B, const Epilogue& ep, long M, long N, long K, hipStream_t st) {
+int launch_hgemm(const AL& A, const HOp& B, const Epilogue& ep, long M, long N, long K, hipStream_t st,
+                 int* tile_form = nullptr) {
   if (K % 64 != 0 || M <= 0 || N <= 0) return YOLAT_E_UNSUPPORTED;
   // 64x128 tiles once they still fill the GPU (cfg 5 classifier 1: 55 -> 45 us)
-  if (N % 128 == 0 && (long)yl_cdiv(M, 64) * (N / 128) >= 256)
+  const bool wide = N % 128 == 0 && (long)yl_cdiv(M, 64) * (N / 128) >= 256;
+  if (tile_form != nullptr) *tile_form = wide ? 1 : 0;
+  if (wide)
     hipLaunchKernelGGL((k_hgemm<1, 2, AL>), dim3(yl_cdiv(M, 64), N / 128), dim3(256), 0, st, A, B, ep, (int)M, (int)N,
                        (int)K);
   else
   hipLaunchKernelGGL((k_hgemm<1, 1, AL>), dim3(yl_cdiv(M, 64), yl_cdiv(N, 64)), dim3(256), 0, st, A, B, ep, (int)M, (int)N,
                      (int)K);
+  YL_LAUNCH_CHECK();
+  return 0;
+}
+
+// ---- fusion block (+ per-proposal max) | fusion_block_super in one launch, routed on D and the folded weights.  feats
+// [N, ld] bf16; Z [P, ZW] with the pooled max at 0:F (zero before the launch), the super block's fp32 input at 2F+D and its
+// output at F+D.  force_groups > 0 replaces the planned column groups of the rows routes (tests); *route names the kernel
+// (internal.hpp, yolat_debug_fusion_pair_eval_bf16), groups_ng receives the node problem's (groups, ng).
+struct FusionStageH {
+  const u16 *Wf, *Wfs; const float *bf, *sf, *tf, *bfs, *sfs, *tfs;
+  const u16 *Wf_fold; const float* tf_fold; const u16* Wfs_fold; const float* tfs_fold;
+};
+int yl_fusion_stage_bf16(const FusionStageH& w, const u16* feats, long ld, long N, long D, const int* node_seg, float* Z,
+                         long ZW, long P, long F, hipStream_t st, int force_groups = 0, int* route = nullptr,
+                         int* groups_ng = nullptr) {
+  HOp a0{feats, ld, (int)N}, b0{w.Wf, D, (int)F}, b1{w.Wfs, D, (int)F};
+  FOp a1{Z + 2 * F + D, ZW, (int)P};
+  Epilogue e0 = plain_epilogue(), e1 = plain_epilogue();
+  e0.bias = w.bf; e0.scale = w.sf; e0.shift = w.tf; e0.relu = 1; e0.seg = node_seg; e0.pool = Z; e0.ldpool = ZW;
+  e1.bias = w.bfs; e1.scale = w.sfs; e1.shift = w.tfs; e1.relu = 1; e1.Y = Z + F + D; e1.ldy = ZW;
+  const int tm1 = yl_cdiv(P, 64), tn1 = yl_cdiv(F, 64);
+  const long n1p = ((long)tm1 * tn1 + 7) & ~7L;
+  if ((D == 64 || D == 128) && w.Wf_fold && w.Wfs_fold && w.tf_fold && w.tfs_fold) {
+    // A-in-registers rows kernel on the BatchNorm-folded weights (fusion_h8.hip)
+    if (route != nullptr) *route = 0;
+    return yl_hfusion_rows8(feats, ld, N, D, w.Wf_fold, w.tf_fold, node_seg, Z, ZW, F, Z + 2 * F + D, ZW, P, w.Wfs_fold,
+                            w.tfs_fold, Z + F + D, ZW, st, force_groups, groups_ng);
+  } else if (D <= 256) {
+    // A-resident rows kernel: at least 4 column groups, and as many as it takes to put >= ~1024 workgroups on
+    // the GPU (each group walks tn / groups consecutive 64-column tiles)
+    const int tn = yl_cdiv(F, 64);
+    // measured at cfg 5 (N = 200k): 64-row tiles x 4 column groups 160 us, x 1 group 166 us, 128-row tiles 181 us
+    // (x 1) / 161 us (x 4); cfg 2 (N = 10k): 8 groups 16.1 us, 16 groups 16.8 us, 2 groups 21.2 us
+    const int tm0 = yl_cdiv(N, 64);
+    int groups = 4;
+    while ((long)tm0 * groups < 1024 && groups < tn) groups *= 2;
+    if (force_groups > 0) groups = force_groups;
+    if (groups > tn) groups = tn;
+    const int ng = yl_cdiv(tn, groups);
+    groups = yl_cdiv(tn, ng);
+    const long total = (long)tm0 * groups + n1p;
+    if (total >= (1LL << 31)) return YOLAT_E_UNSUPPORTED;
+    if (route != nullptr) *route = D <= 128 ? 1 : 2;
+    if (groups_ng != nullptr) { groups_ng[0] = groups; groups_ng[1] = ng; }
+    auto go = [&](auto kern) {
+      hipLaunchKernelGGL(kern, dim3((unsigned)total), dim3(256), 0, st, a0, b0, e0, (int)N, (int)F, (int)D, tm0, groups, ng,
+                         a1, b1, e1, (int)P, (int)F, (int)D, tm1, tn1);
+    };
+    if (D <= 128) go(k_hfusion_rows<1, 128>);
+    else go(k_hfusion_rows<1, 256>);
+  } else {
+    const bool big = N >= 65536;                       // 128x128 tiles once there are enough of them to fill the GPU
+    const int tm0 = yl_cdiv(N, big ? 128 : 64), tn0 = yl_cdiv(F, big ? 128 : 64);
+    const long total = (long)tm0 * tn0 + n1p;
+    if (total >= (1LL << 31)) return YOLAT_E_UNSUPPORTED;
+    if (route != nullptr) *route = big ? 4 : 3;
+    if (groups_ng != nullptr) { groups_ng[0] = tn0; groups_ng[1] = 1; }
+    if (big)
+      hipLaunchKernelGGL(k_hgemm_two<2>, dim3((unsigned)total), dim3(256), 0, st, a0, b0, e0, (int)N, (int)F, (int)D, tm0,
+                         tn0, a1, b1, e1, (int)P, (int)F, (int)D, tm1, tn1);
+    else
+      hipLaunchKernelGGL(k_hgemm_two<1>, dim3((unsigned)total), dim3(256), 0, st, a0, b0, e0, (int)N, (int)F, (int)D, tm0,
+                         tn0, a1, b1, e1, (int)P, (int)F, (int)D, tm1, tn1);
+  }
   YL_LAUNCH_CHECK();
   return 0;
 }
@@ -922,50 +989,9 @@ static int forward_eval_bf16_impl(const yolat_model_eval_bf16* mh, const float* 
   });
   snprintf(nm, sizeof nm, "fusion_gemm_bf16+segmax[N x %ld -> %ld -> P] | super[P x %ld -> %ld]", D, F, D, F);
   YL_HSTAGE(nm, 2.0 * (N + P) * D * F, 2.0 * (N * D + 2.0 * D * F) + 4.0 * (2.0 * P * F + N + P * D), {
-    HOp a0{p.feats, D, (int)N}, b0{mh->Wf, D, (int)F}, b1{mh->Wfs, D, (int)F};
-    FOp a1{p.Z + 2 * F + D, ZW, (int)P};
-    Epilogue e0 = plain_epilogue(), e1 = plain_epilogue();
-    e0.bias = m->bf; e0.scale = m->sf; e0.shift = m->tf; e0.relu = 1; e0.seg = p.node_seg; e0.pool = p.Z; e0.ldpool = ZW;
-    e1.bias = m->bfs; e1.scale = m->sfs; e1.shift = m->tfs; e1.relu = 1; e1.Y = p.Z + F + D; e1.ldy = ZW;
-    const int tm1 = yl_cdiv(P, 64), tn1 = yl_cdiv(F, 64);
-    const long n1p = ((long)tm1 * tn1 + 7) & ~7L;
-    if ((D == 64 || D == 128) && mh->Wf_fold && mh->Wfs_fold && mh->tf_fold && mh->tfs_fold) {
-      // A-in-registers rows kernel on the BatchNorm-folded weights (fusion_h8.hip)
-      YL_TRY(yl_hfusion_rows8(p.feats, D, N, D, mh->Wf_fold, mh->tf_fold, p.node_seg, p.Z, ZW, F, p.Z + 2 * F + D, ZW, P,
-                              mh->Wfs_fold, mh->tfs_fold, p.Z + F + D, ZW, st));
-    } else if (D <= 256) {
-      // A-resident rows kernel: at least 4 column groups, and as many as it takes to put >= ~1024 workgroups on
-      // the GPU (each group walks tn / groups consecutive 64-column tiles)
-      const int tn = yl_cdiv(F, 64);
-      // measured at cfg 5 (N = 200k): 64-row tiles x 4 column groups 160 us, x 1 group 166 us, 128-row tiles 181 us
-      // (x 1) / 161 us (x 4); cfg 2 (N = 10k): 8 groups 16.1 us, 16 groups 16.8 us, 2 groups 21.2 us
-      const int tm0 = yl_cdiv(N, 64);
-      int groups = 4;
-      while ((long)tm0 * groups < 1024 && groups < tn) groups *= 2;
-      if (groups > tn) groups = tn;
-      const int ng = yl_cdiv(tn, groups);
-      groups = yl_cdiv(tn, ng);
-      const long total = (long)tm0 * groups + n1p;
-      if (total >= (1LL << 31)) return YOLAT_E_UNSUPPORTED;
-      auto go = [&](auto kern) {
-        hipLaunchKernelGGL(kern, dim3((unsigned)total), dim3(256), 0, st, a0, b0, e0, (int)N, (int)F, (int)D, tm0, groups, ng,
-                           a1, b1, e1, (int)P, (int)F, (int)D, tm1, tn1);
-      };
-      if (D <= 128) go(k_hfusion_rows<1, 128>);
-      else go(k_hfusion_rows<1, 256>);
-    } else {
-    const bool big = N >= 65536;                       // 128x128 tiles once there are enough of them to fill the GPU
-    const int tm0 = yl_cdiv(N, big ? 128 : 64), tn0 = yl_cdiv(F, big ? 128 : 64);
-    const long total = (long)tm0 * tn0 + n1p;
-    if (total >= (1LL << 31)) return YOLAT_E_UNSUPPORTED;
-    if (big)
-      hipLaunchKernelGGL(k_hgemm_two<2>, dim3((unsigned)total), dim3(256), 0, st, a0, b0, e0, (int)N, (int)F, (int)D, tm0,
-                         tn0, a1, b1, e1, (int)P, (int)F, (int)D, tm1, tn1);
-    else
-      hipLaunchKernelGGL(k_hgemm_two<1>, dim3((unsigned)total), dim3(256), 0, st, a0, b0, e0, (int)N, (int)F, (int)D, tm0,
-                         tn0, a1, b1, e1, (int)P, (int)F, (int)D, tm1, tn1);
-    }
-    YL_LAUNCH_CHECK();
+    const FusionStageH w{mh->Wf, mh->Wfs, m->bf, m->sf, m->tf, m->bfs, m->sfs, m->tfs,
+                         mh->Wf_fold, mh->tf_fold, mh->Wfs_fold, mh->tfs_fold};
+    YL_TRY(yl_fusion_stage_bf16(w, p.feats, D, N, D, p.node_seg, p.Z, ZW, P, F, st));
   });
   {
     Epilogue e = plain_epilogue();
@@ -989,6 +1015,88 @@ static int forward_eval_bf16_impl(const yolat_model_eval_bf16* mh, const float* 
     });
   }
   return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// The dense stages of the forward above as ops of their own (internal.hpp): the same launches, built the same way.
+// ------------------------------------------------------------------------------------------------
+extern "C" int yolat_debug_fusion_pair_eval_bf16(const uint16_t* feats, int64_t ld, int64_t N, int64_t D,
+                                                 const int32_t* node_seg, float* Z, int64_t ldz, int64_t P, int64_t F,
+                                                 const uint16_t* Wf, const uint16_t* Wfs, const float* bf, const float* sf,
+                                                 const float* tf, const float* bfs, const float* sfs, const float* tfs,
+                                                 const uint16_t* Wf_fold, const float* tf_fold, const uint16_t* Wfs_fold,
+                                                 const float* tfs_fold, int force_groups, int* route, int* groups_ng,
+                                                 yolat_stream_t stream) {
+  if (!feats || !node_seg || !Z || !Wf || !Wfs || !sf || !tf || !sfs || !tfs || N <= 0 || P <= 0 || F <= 0 || D <= 0 ||
+      force_groups < 0)
+    return YOLAT_E_INVALID;
+  if (N >= (1LL << 31) || P >= (1LL << 31) || ld < D || ldz < 2 * (F + D)) return YOLAT_E_INVALID;
+  if (P * ldz >= (1LL << 32)) return YOLAT_E_UNSUPPORTED;                    // 32-bit element offsets into the pooled matrix
+  if (D % 64 != 0 || F % 32 != 0 || ld % 8 != 0 || ldz % 4 != 0 || !yl_aligned16(feats) || !yl_aligned16(Z) ||
+      !yl_aligned16(Wf) || !yl_aligned16(Wfs) || (Wf_fold && !yl_aligned16(Wf_fold)) || (Wfs_fold && !yl_aligned16(Wfs_fold)))
+    return YOLAT_E_UNSUPPORTED;
+  const FusionStageH w{Wf, Wfs, bf, sf, tf, bfs, sfs, tfs, Wf_fold, tf_fold, Wfs_fold, tfs_fold};
+  return yl_fusion_stage_bf16(w, feats, ld, N, D, node_seg, Z, ldz, P, F, (hipStream_t)stream, force_groups, route, groups_ng);
+}
+
+extern "C" int yolat_debug_pool_prepare_bf16(const uint16_t* feats, const uint16_t* fsup, int64_t ld, int64_t D, int64_t F,
+                                             const int32_t* seg_ptr, int64_t P, float* Z, int64_t ldz, yolat_stream_t stream) {
+  if (!feats || !fsup || !seg_ptr || !Z || P <= 0 || D <= 0 || F <= 0 || ld < D || ldz < 2 * (F + D)) return YOLAT_E_INVALID;
+  if (P >= (1LL << 31) || F + 2 * D >= (1LL << 30)) return YOLAT_E_UNSUPPORTED;
+  for (int64_t p0 = 0; p0 < P; p0 += 65535) {
+    const int64_t np = (P - p0) < 65535 ? (P - p0) : 65535;
+    hipLaunchKernelGGL(k_pool_prepare_h, dim3(yl_cdiv(F + 2 * D, 256), (unsigned)np), dim3(256), 0, (hipStream_t)stream, feats,
+                       fsup, (long)ld, (int)D, (int)F, seg_ptr + p0, Z + p0 * ldz, (long)ldz, YlGate{nullptr, 0}, (int)np);
+    YL_LAUNCH_CHECK();
+  }
+  return 0;
+}
+
+extern "C" int yolat_debug_node_uv_eval_bf16(const uint16_t* f_in, int64_t ld_f, const uint16_t* s_in, int64_t ld_s, int64_t N,
+                                             const uint16_t* Wuv, const uint16_t* Wr, const uint16_t* Wn,
+                                             const float* uv_scale, const float* uv_shift, const float* br, const float* bn,
+                                             const float* sn, const float* tn, uint16_t* UV, float* root, uint16_t* s_out,
+                                             int64_t ld_so, yolat_stream_t stream) {
+  const long C = 64;
+  if (!f_in || !s_in || !Wuv || !Wr || !Wn || !uv_scale || !uv_shift || !sn || !tn || !UV || !root || !s_out || N <= 0 ||
+      N >= (1LL << 31) || ld_f < C || ld_s < C || ld_so < C)
+    return YOLAT_E_INVALID;
+  if (ld_f % 8 != 0 || ld_s % 8 != 0 || ld_so % 2 != 0 || !yl_aligned16(f_in) || !yl_aligned16(s_in) || !yl_aligned16(Wuv) ||
+      !yl_aligned16(Wr) || !yl_aligned16(Wn) || (((uintptr_t)UV) & 3) != 0 || (((uintptr_t)s_out) & 3) != 0)
+    return YOLAT_E_UNSUPPORTED;
+  NodeUvH a;
+  a.af = HOp{f_in, ld_f, (int)N};
+  a.as = HOp{s_in, ld_s, (int)N};
+  a.wuv = HOp{Wuv, 64, (int)(2 * C)}; a.wr = HOp{Wr, 64, (int)C}; a.wn = HOp{Wn, 64, (int)C};
+  a.euv = plain_epilogue(); a.euv.Yh = UV; a.euv.ldy = 2 * C;
+  a.euv.scale = uv_scale; a.euv.shift = uv_shift;
+  a.er = plain_epilogue(); a.er.bias = br; a.er.Y = root; a.er.ldy = C;
+  a.en = plain_epilogue(); a.en.bias = bn; a.en.scale = sn; a.en.shift = tn; a.en.relu = 1;
+  a.en.Yh = s_out; a.en.ldy = ld_so;
+  a.N = (int)N; a.C = (int)C; a.Cin = 64;
+  hipLaunchKernelGGL(k_hgemm_node3, dim3(yl_cdiv(N, 64), 4), dim3(256), 0, (hipStream_t)stream, a);
+  YL_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int yolat_debug_hgemm_eval_bf16(const void* A, int a_f32, int64_t lda, int64_t M, int64_t K, const uint16_t* W,
+                                           int64_t ldw, int64_t Nout, const float* bias, const float* scale,
+                                           const float* shift, int relu, void* Y, int y_bf16, int64_t ldy, int* tile_form,
+                                           yolat_stream_t stream) {
+  if (!A || !W || !Y || M <= 0 || K <= 0 || Nout <= 0 || M >= (1LL << 31) || Nout >= (1LL << 31) || lda < K || ldw < K ||
+      ldy < Nout || (scale == nullptr) != (shift == nullptr))
+    return YOLAT_E_INVALID;
+  if (K % 64 != 0 || lda % (a_f32 ? 4 : 8) != 0 || ldw % 8 != 0 || !yl_aligned16(A) || !yl_aligned16(W) ||
+      (y_bf16 ? (ldy % 2 != 0 || (((uintptr_t)Y) & 3) != 0) : (((uintptr_t)Y) & 3) != 0))
+    return YOLAT_E_UNSUPPORTED;
+  Epilogue e = plain_epilogue();
+  e.bias = bias; e.scale = scale; e.shift = shift; e.relu = relu ? 1 : 0; e.ldy = ldy;
+  if (y_bf16) e.Yh = reinterpret_cast<u16*>(Y);
+  else e.Y = reinterpret_cast<float*>(Y);
+  const HOp b{W, ldw, (int)Nout};
+  if (a_f32)
+    return launch_hgemm(FOp{reinterpret_cast<const float*>(A), lda, (int)M}, b, e, M, Nout, K, (hipStream_t)stream, tile_form);
+  return launch_hgemm(HOp{reinterpret_cast<const u16*>(A), lda, (int)M}, b, e, M, Nout, K, (hipStream_t)stream, tile_form);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -204,9 +204,12 @@ __global__ void __launch_bounds__(512, 2) k_hfusion_rows8(H8Prob p0, H8Prob p1) 
 
 // A [N, lda] bf16 x Wf [F, D] (folded) with the per-proposal max into pool [*, ld_pool] (columns 0..F), and
 // As [P, lda_s] fp32 x Wfs [F, D] (folded) -> relu -> sup_out [P, ld_sup].  D in {64, 128}; F % 64 == 0.
+// force_groups > 0 replaces the planned number of column groups of the N-row problem (tests: the multi-tile loop at small
+// N); groups_ng != nullptr receives that problem's (groups, ng).
 int yl_hfusion_rows8(const uint16_t* A, int64_t lda, int64_t N, int64_t D, const uint16_t* Wf, const float* tf,
                      const int32_t* seg, float* pool, int64_t ld_pool, int64_t F, const float* As, int64_t lda_s, int64_t P,
-                     const uint16_t* Wfs, const float* tfs, float* sup_out, int64_t ld_sup, hipStream_t st) {
+                     const uint16_t* Wfs, const float* tfs, float* sup_out, int64_t ld_sup, hipStream_t st,
+                     int force_groups, int* groups_ng) {
   if ((D != 64 && D != 128) || F % 64 != 0 || N <= 0 || P <= 0) return YOLAT_E_UNSUPPORTED;
   if (!yl_aligned16(A) || !yl_aligned16(As) || !yl_aligned16(Wf) || !yl_aligned16(Wfs) || lda % 8 != 0 || lda_s % 4 != 0)
     return YOLAT_E_UNSUPPORTED;
@@ -227,6 +230,8 @@ int yl_hfusion_rows8(const uint16_t* A, int64_t lda, int64_t N, int64_t D, const
       // 32 sixteen-tile workgroups 93 us for the launch)
       groups = 1;
       while ((long)tm * groups * 2 <= 128 && groups * 2 <= tn) groups *= 2;
+    } else if (force_groups > 0) {
+      groups = force_groups;
     }
     ng = yl_cdiv(tn, groups);
     groups = yl_cdiv(tn, ng);
@@ -241,6 +246,7 @@ int yl_hfusion_rows8(const uint16_t* A, int64_t lda, int64_t N, int64_t D, const
   const long n1p = ((long)p1.tm * p1.groups + 7) & ~7L;
   const long total = n1p + (long)p0.tm * p0.groups;
   if (total >= (1LL << 31)) return YOLAT_E_UNSUPPORTED;
+  if (groups_ng != nullptr) { groups_ng[0] = p0.groups; groups_ng[1] = p0.ng; }
   if (D == 128) hipLaunchKernelGGL(k_hfusion_rows8<128>, dim3((unsigned)total), dim3(512), 0, st, p0, p1);
   else hipLaunchKernelGGL(k_hfusion_rows8<64>, dim3((unsigned)total), dim3(512), 0, st, p0, p1);
   YL_LAUNCH_CHECK();

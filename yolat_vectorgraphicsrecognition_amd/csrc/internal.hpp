@@ -168,10 +168,12 @@ bool yl_conv_local_model_ok(const yolat_model_eval_bf16* mh);
 int yl_conv_local_bf16(const yolat_model_eval_bf16* mh, const void* pack, const float* x, int64_t ldx, const YlLocalIn& in,
                        int64_t N, int64_t E, int64_t P, uint16_t* feats, int64_t ld_feats, float* Z, int64_t ldz, int32_t* flag,
                        int32_t flag_val, hipStream_t st);
-// bf16 fusion block with the per-proposal max, nodes and proposals in one launch (fusion_h8.hip)
+// bf16 fusion block with the per-proposal max, nodes and proposals in one launch (fusion_h8.hip); force_groups > 0
+// replaces the planned column groups of the N-row problem, groups_ng receives that problem's (groups, ng)
 int yl_hfusion_rows8(const uint16_t* A, int64_t lda, int64_t N, int64_t D, const uint16_t* Wf, const float* tf,
                      const int32_t* seg, float* pool, int64_t ld_pool, int64_t F, const float* As, int64_t lda_s, int64_t P,
-                     const uint16_t* Wfs, const float* tfs, float* sup_out, int64_t ld_sup, hipStream_t st);
+                     const uint16_t* Wfs, const float* tfs, float* sup_out, int64_t ld_sup, hipStream_t st,
+                     int force_groups = 0, int* groups_ng = nullptr);
 // the weight gradient of a wide Linear on the bf16x6 GEMM: worthwhile?, its workspace, the launch (gemm_x6.hip)
 bool yl_bwd_w_x6_ok(int64_t M, int64_t Nout, int64_t K);
 size_t yl_bwd_w_x6_work_elems(int64_t M, int64_t Nout, int64_t K);
@@ -212,3 +214,34 @@ extern "C" int yolat_debug_cls_tail_eval(const float* c1, int64_t ldc1, int64_t 
                                          int64_t ldw3, const float* b3, int64_t n_classes, float* logits, int64_t ld_logits,
                                          void* work, int primed, float* c2_dbg, int64_t ld_dbg, int* folded,
                                          yolat_stream_t stream);
+// Stages of the bf16-storage eval forward as ops of their own, launched the way yolat_forward_eval_bf16 launches them
+// (bf16_eval.hip); exported for tools and tests, not part of the C ABI header.
+//   fusion pair: the forward's route on D and the fold pointers.  Z [P, ldz] in the forward's column layout (pooled max at
+//     0:F, zero before the call; super output at F+D:2F+D; super input, fp32, at 2F+D:2F+2D).  force_groups > 0 replaces
+//     the planned column groups of the rows routes.  *route: 0 = k_hfusion_rows8, 1 = k_hfusion_rows<1,128>,
+//     2 = k_hfusion_rows<1,256>, 3 = k_hgemm_two<1>, 4 = k_hgemm_two<2>; groups_ng[2] = (groups, ng) of the node problem
+//     ((column tiles, 1) on the tile routes).
+extern "C" int yolat_debug_fusion_pair_eval_bf16(const uint16_t* feats, int64_t ld, int64_t N, int64_t D,
+                                                 const int32_t* node_seg, float* Z, int64_t ldz, int64_t P, int64_t F,
+                                                 const uint16_t* Wf, const uint16_t* Wfs, const float* bf, const float* sf,
+                                                 const float* tf, const float* bfs, const float* sfs, const float* tfs,
+                                                 const uint16_t* Wf_fold, const float* tf_fold, const uint16_t* Wfs_fold,
+                                                 const float* tfs_fold, int force_groups, int* route, int* groups_ng,
+                                                 yolat_stream_t stream);
+//   pooling prologue: Z[p, 0:F] = 0, Z[p, F:F+D] = max(feats rows), Z[p, 2F+D:2F+2D] = mean(fsup rows), ungated, in the
+//     forward's chunks of 65535 proposals
+extern "C" int yolat_debug_pool_prepare_bf16(const uint16_t* feats, const uint16_t* fsup, int64_t ld, int64_t D, int64_t F,
+                                             const int32_t* seg_ptr, int64_t P, float* Z, int64_t ldz, yolat_stream_t stream);
+//   node side of a conv layer > 0 (C = Cin = 64): UV [N, 128] bf16 = (f_in . Wuv^T) * uv_scale + uv_shift, root [N, 64] fp32 =
+//     f_in . Wr^T + br, s_out bf16 = relu((s_in . Wn^T + bn) * sn + tn)
+extern "C" int yolat_debug_node_uv_eval_bf16(const uint16_t* f_in, int64_t ld_f, const uint16_t* s_in, int64_t ld_s, int64_t N,
+                                             const uint16_t* Wuv, const uint16_t* Wr, const uint16_t* Wn,
+                                             const float* uv_scale, const float* uv_shift, const float* br, const float* bn,
+                                             const float* sn, const float* tn, uint16_t* UV, float* root, uint16_t* s_out,
+                                             int64_t ld_so, yolat_stream_t stream);
+//   the classifier's GEMM: Y = epi(A . W^T), A fp32 rows rounded while staging (a_f32 != 0) or bf16 rows, W [Nout, K] bf16,
+//     Y bf16 (y_bf16 != 0) or fp32; scale and shift both or none.  *tile_form: 0 = k_hgemm<1,1>, 1 = k_hgemm<1,2>
+extern "C" int yolat_debug_hgemm_eval_bf16(const void* A, int a_f32, int64_t lda, int64_t M, int64_t K, const uint16_t* W,
+                                           int64_t ldw, int64_t Nout, const float* bias, const float* scale,
+                                           const float* shift, int relu, void* Y, int y_bf16, int64_t ldy, int* tile_form,
+                                           yolat_stream_t stream);
