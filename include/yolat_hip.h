@@ -851,7 +851,12 @@ int yolat_forward_eval_csr(const yolat_model_eval* m, const float* x, int64_t ld
  * REQUIRED); the bf16 members are yolat_f32_to_bf16 copies of the named fp32 weights (row-major, same
  * shapes).  Wuv/Wr/Wn[0] are unused (layer 0 multiplies the raw fp32 features).
  * Supported shapes: C = 64, Cin0 <= 16, F, C*n_blocks_out, H1, H2 multiples of 64, N <= 2^23, E <= 2^29;
- * else YOLAT_E_UNSUPPORTED.
+ * else YOLAT_E_UNSUPPORTED.  base->norm must be YOLAT_NORM_BATCH (else YOLAT_E_UNSUPPORTED).
+ * base->act: YOLAT_ACT_RELU, or YOLAT_ACT_LEAKYRELU / YOLAT_ACT_PRELU with the four base->act_slope[] set — the activation
+ * is applied in fp32, per element before the per-proposal maximum and before the bf16 store of the classifier's hidden
+ * activations, the slope read from device memory by every launch; the forward is one launch longer and, off the
+ * C*n_blocks_out in {64, 128} route, takes yolat_fusion_pair_eval_act_work_elems(N, F) floats more workspace.  Any other
+ * act, or a NULL slope of a leaky descriptor: YOLAT_E_INVALID before anything is enqueued.
  * Accuracy: <= 1e-2 of the logits' scale against the fp32 path (tests/test_gpu_bf16.py).
  * ------------------------------------------------------------------------------------------ */
 typedef struct {

@@ -100,9 +100,59 @@ struct HProOp {
 constexpr int YL_HRS = 72;   // LDS row stride in bf16 elements (144 B)
 template <int TM, int TN> struct HTileSmem { static constexpr int elems = 64 * (TM + TN) * YL_HRS; };
 
-template <int TM, int TN, class AL>
+// wave_epilogue (epilogue.hpp) for a leaky activation (act.hip): v = act((acc + bias) * scale + shift) with
+// act(y) = y > 0 ? y : a * y computed in fp32 BEFORE the store, so a bf16 output is rounded once, like the ReLU one.  The
+// plain-store forms only (ep.Yh bf16 or ep.Y fp32, through the wave's staging region where the tile is whole and aligned,
+// element by element otherwise); a NaN stays a NaN.
+__device__ __forceinline__ void wave_epilogue_act(f32x16 acc, int row_base, int col, int lhi, const Epilogue& ep, int M, int N,
+                                                  const EpiPre& pre, float* stage, float a) {
+  const bool col_ok = col < N;
+  const float bv = ep.bias != nullptr ? pre.bias : 0.f, sc = pre.sc, sh = pre.sh;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const float y = fmaf(acc[r] + bv, sc, sh);
+    acc[r] = y > 0.f ? y : a * y;
+  }
+  const int l31s = threadIdx.x & 31, lane = threadIdx.x & 63, col_base = col - l31s;
+  if (yl_stage_ok(ep, row_base, col_base, M, N)) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) stage[((r & 3) + 8 * (r >> 2) + 4 * lhi) * YL_STAGE_LD + l31s] = acc[r];
+    if (ep.Yh != nullptr) {
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+        const int chunk = lane + 64 * t, R = chunk >> 2, c = (chunk & 3) * 8;
+        const float4 x0 = *reinterpret_cast<const float4*>(stage + R * YL_STAGE_LD + c);
+        const float4 x1 = *reinterpret_cast<const float4*>(stage + R * YL_STAGE_LD + c + 4);
+        uint4 o;
+        o.x = yl_pack_bf16(x0.x, x0.y); o.y = yl_pack_bf16(x0.z, x0.w);
+        o.z = yl_pack_bf16(x1.x, x1.y); o.w = yl_pack_bf16(x1.z, x1.w);
+        *reinterpret_cast<uint4*>(ep.Yh + (long)(row_base + R) * ep.ldy + col_base + c) = o;
+      }
+    } else {
+#pragma unroll
+      for (int t = 0; t < 4; ++t) {
+        const int chunk = lane + 64 * t, R = chunk >> 3, c = (chunk & 7) * 4;
+        *reinterpret_cast<float4*>(ep.Y + (long)(row_base + R) * ep.ldy + col_base + c) =
+            *reinterpret_cast<const float4*>(stage + R * YL_STAGE_LD + c);
+      }
+    }
+    return;
+  }
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const int row = row_base + (r & 3) + 8 * (r >> 2) + 4 * lhi;
+    if (col_ok && row < M) {
+      if (ep.Yh != nullptr) ep.Yh[(long)row * ep.ldy + col] = (u16)(yl_pack_bf16(acc[r], 0.f) & 0xFFFFu);
+      else ep.Y[(long)row * ep.ldy + col] = acc[r];
+    }
+  }
+}
+
+// ACT = 1: the epilogue is wave_epilogue_act with the slope read from *slope (nothing else differs; the ACT = 0 tile is
+// the tile as it was)
+template <int TM, int TN, class AL, int ACT = 0>
 __device__ __forceinline__ void hgemm_tile(const AL& A, const HOp& B, const Epilogue& ep, int M, int N, int K, int rt_,
-                                           int ct_, u16* smem) {
+                                           int ct_, u16* smem, const float* slope = nullptr) {
   constexpr int BM = 64 * TM, BN = 64 * TN, NA = 2 * TM, NB = 2 * TN;   // 16-byte slots per thread per K step
   u16* As = smem;
   u16* Bs = smem + BM * YL_HRS;
@@ -138,6 +188,8 @@ __device__ __forceinline__ void hgemm_tile(const AL& A, const HOp& B, const Epil
 #pragma unroll
     for (int j = 0; j < TN; ++j)
       pre[i][j] = epi_prefetch(ep, row0 + (wm * TM + i) * 32, col0 + (wn * TN + j) * 32 + l31, M, N);
+  float act_a = 0.f;
+  if constexpr (ACT != 0) act_a = *slope;               // with the epilogue constants: its latency hides under the K loop
 
   // one K step: stage the registers of step k0, refill them with step k0 + 64 PF, MFMAs
   auto kstep = [&](int k0, u32x4* qa, u32x4* qb) {
@@ -179,6 +231,15 @@ __device__ __forceinline__ void hgemm_tile(const AL& A, const HOp& B, const Epil
   // the operand tiles are dead after the loop's closing barrier: every wave stages its stores in its own 4.5 KB of them
   static_assert(HTileSmem<TM, TN>::elems * 2 >= 4 * 32 * YL_STAGE_LD * 4, "LDS too small for the store staging");
   float* stage = reinterpret_cast<float*>(smem) + wave * (32 * YL_STAGE_LD);
+  if constexpr (ACT != 0) {
+#define YL_EPI_ACT(i, j)                                                                                             \
+  if constexpr ((i) < TM && (j) < TN)                                                                                \
+    wave_epilogue_act(acc[i][j], row0 + (wm * TM + (i)) * 32, col0 + (wn * TN + (j)) * 32 + l31, lhi, ep, M, N,      \
+                      pre[i][j], stage, act_a);
+    YL_EPI_ACT(0, 0) YL_EPI_ACT(0, 1) YL_EPI_ACT(1, 0) YL_EPI_ACT(1, 1)
+#undef YL_EPI_ACT
+    return;
+  }
 #define YL_EPI(i, j)                                                                                                 \
   if constexpr ((i) < TM && (j) < TN)                                                                                \
     wave_epilogue(acc[i][j], row0 + (wm * TM + (i)) * 32, col0 + (wn * TN + (j)) * 32 + l31, lhi, ep, M, N, pre[i][j], \
@@ -193,6 +254,14 @@ static __global__ void __launch_bounds__(256) k_hgemm(AL A, HOp B, Epilogue ep, 
   int rt_, ct_;
   yl_xcd_tile(rt_, ct_);
   hgemm_tile<TM, TN, AL>(A, B, ep, M, N, K, rt_, ct_, smem);
+}
+// the same tiles with the leaky activation in the epilogue (prediction_cls.0 / .1, fusion_block_super of a leaky model)
+template <int TM, int TN, class AL>
+static __global__ void __launch_bounds__(256) k_hgemm_act(AL A, HOp B, Epilogue ep, int M, int N, int K, const float* slope) {
+  __shared__ __attribute__((aligned(16))) u16 smem[HTileSmem<TM, TN>::elems];
+  int rt_, ct_;
+  yl_xcd_tile(rt_, ct_);
+  hgemm_tile<TM, TN, AL, 1>(A, B, ep, M, N, K, rt_, ct_, smem, slope);
 }
 
 // fusion block over the nodes (+ per-proposal max epilogue) and fusion_block_super over the per-proposal
@@ -648,9 +717,16 @@ struct PlanH {
   u16* UV; float* root; u16* f_tmp[YOLAT_MAX_LAYERS]; u16* s_tmp[YOLAT_MAX_LAYERS];
   u16* feats; u16* fsup; float* Z; float* c1; float* c2;
   int* local_flag; int* eptr;
+  float* act_work;      // leaky model off the rows8 route: a column range of the fusion block's BatchNorm output, fp32
   size_t bytes;
 };
-PlanH carve_h(const yolat_model_eval* m, long N, long E, long P, void* ws) {
+// does the fusion pair run on the A-in-registers rows kernel (fusion_h8.hip)?  A function of the descriptor alone, so the
+// workspace sizing and the forward agree
+bool h8_route(const yolat_model_eval_bf16* mh, long D) {
+  return (D == 64 || D == 128) && mh->Wf_fold && mh->Wfs_fold && mh->tf_fold && mh->tfs_fold;
+}
+PlanH carve_h(const yolat_model_eval_bf16* mh, long N, long E, long P, void* ws) {
+  const yolat_model_eval* m = mh->base;
   Carver c{reinterpret_cast<char*>(ws), 0};
   PlanH p;
   const long C = m->C, F = m->F, D = C * m->n_blocks_out, Ee = E > 0 ? E : 1;
@@ -667,6 +743,9 @@ PlanH carve_h(const yolat_model_eval* m, long N, long E, long P, void* ws) {
   p.Z = c.take<float>(P * 2 * (F + D)); p.c1 = c.take<float>(P * m->H1); p.c2 = c.take<float>(P * m->H2);
   p.local_flag = c.take<int>(64);
   p.eptr = c.take<int>(P + 1);
+  // (carved last and for a leaky descriptor only: a ReLU one keeps its layout and its size)
+  p.act_work = (m->act != YOLAT_ACT_RELU && !h8_route(mh, D)) ? c.take<float>((long)yolat_fusion_pair_eval_act_work_elems(N, F))
+                                                               : nullptr;
   p.bytes = c.off + 256;
   return p;
 }
@@ -677,6 +756,10 @@ int model_ok(const yolat_model_eval_bf16* mh) {
   if (m->n_blocks < 1 || m->n_blocks > YOLAT_MAX_LAYERS || m->n_blocks_out < 1 || m->n_blocks_out > m->n_blocks)
     return YOLAT_E_INVALID;
   if (m->norm != YOLAT_NORM_BATCH) return YOLAT_E_UNSUPPORTED;     // a row-norm base (rownorm.hip) runs on the fp32 forward only
+  // the activation of the four sites behind the conv stack (act.hip): every launch reads its slope through the address
+  if (m->act != YOLAT_ACT_RELU && m->act != YOLAT_ACT_LEAKYRELU && m->act != YOLAT_ACT_PRELU) return YOLAT_E_INVALID;
+  if (m->act != YOLAT_ACT_RELU)
+    for (int i = 0; i < 4; ++i) if (!m->act_slope[i]) return YOLAT_E_INVALID;
   const long D = m->C * m->n_blocks_out;
   // shapes the bf16 kernels are written for (the reference's: n_filters 64, fusion 1024, classifier 512/256)
   if (m->C != 64 || m->F % 64 != 0 || D % 64 != 0 || (2 * (m->F + D)) % 64 != 0 || m->H1 % 64 != 0 || m->H2 % 64 != 0)
@@ -688,6 +771,9 @@ int model_ok(const yolat_model_eval_bf16* mh) {
     if (l > 0 && (!mh->Wuv[l] || !mh->Wr[l] || !mh->Wn[l])) return YOLAT_E_INVALID;
   }
   if (!mh->Wf || !mh->Wfs || !mh->Wc1 || !mh->Wc2 || !mh->Wc3) return YOLAT_E_INVALID;
+  // (a leaky forward writes the pooled start values before the rows kernel: what that launch would decline is declined here)
+  if (m->act != YOLAT_ACT_RELU && h8_route(mh, D) && (!yl_aligned16(mh->Wf_fold) || !yl_aligned16(mh->Wfs_fold)))
+    return YOLAT_E_UNSUPPORTED;
   return 0;
 }
 
@@ -704,6 +790,23 @@ int launch_hgemm(const AL& A, const HOp& B, const Epilogue& ep, long M, long N, 
   else
   hipLaunchKernelGGL((k_hgemm<1, 1, AL>), dim3(yl_cdiv(M, 64), yl_cdiv(N, 64)), dim3(256), 0, st, A, B, ep, (int)M, (int)N,
                      (int)K);
+  YL_LAUNCH_CHECK();
+  return 0;
+}
+
+// launch_hgemm with the leaky activation in the epilogue (k_hgemm_act), the slope read from *slope by the launch
+template <class AL>
+int launch_hgemm_act(const AL& A, const HOp& B, const Epilogue& ep, long M, long N, long K, const float* slope, hipStream_t st,
+                     int* tile_form = nullptr) {
+  if (K % 64 != 0 || M <= 0 || N <= 0) return YOLAT_E_UNSUPPORTED;
+  const bool wide = N % 128 == 0 && (long)yl_cdiv(M, 64) * (N / 128) >= 256;
+  if (tile_form != nullptr) *tile_form = wide ? 1 : 0;
+  if (wide)
+    hipLaunchKernelGGL((k_hgemm_act<1, 2, AL>), dim3(yl_cdiv(M, 64), N / 128), dim3(256), 0, st, A, B, ep, (int)M, (int)N,
+                       (int)K, slope);
+  else
+    hipLaunchKernelGGL((k_hgemm_act<1, 1, AL>), dim3(yl_cdiv(M, 64), yl_cdiv(N, 64)), dim3(256), 0, st, A, B, ep, (int)M,
+                       (int)N, (int)K, slope);
   YL_LAUNCH_CHECK();
   return 0;
 }
@@ -771,6 +874,39 @@ int yl_fusion_stage_bf16(const FusionStageH& w, const u16* feats, long ld, long 
   YL_LAUNCH_CHECK();
   return 0;
 }
+
+// ---- the same stage of a leaky model (act.hip): act(y) = y > 0 ? y : a * y per element before the maximum, slopes by
+// address.  Z[:, 0:F] need not be prepared: its start values are written here.
+//   route 0  yolat_pool_init_signed (-inf where a proposal has nodes, 0 where it has none), then the ACT instantiation of
+//            k_hfusion_rows8 (signed table, fusion_h8.hip)                                              2 launches
+//   route 5  every other shape, the scheme of yolat_fusion_pair_eval_act: per column range (<= 64 MiB of `work`) the
+//            BatchNorm output in fp32 by the bf16 tile GEMM, then yolat_segment_act_max (one writer per element); the super
+//            block as a tile GEMM with the activation in its epilogue                                   2 x ranges + 1
+int yl_fusion_stage_bf16_act(const FusionStageH& w, const u16* feats, long ld, long N, long D, const int* node_seg,
+                             const int* seg_ptr, float* Z, long ZW, long P, long F, const float* slope_f,
+                             const float* slope_s, float* work, bool h8, hipStream_t st, int force_groups = 0,
+                             int* route = nullptr, int* groups_ng = nullptr) {
+  if (h8) {
+    if (route != nullptr) *route = 0;
+    YL_TRY(yolat_pool_init_signed(seg_ptr, P, F, Z, ZW, (yolat_stream_t)st));
+    return yl_hfusion_rows8(feats, ld, N, D, w.Wf_fold, w.tf_fold, node_seg, Z, ZW, F, Z + 2 * F + D, ZW, P, w.Wfs_fold,
+                            w.tfs_fold, Z + F + D, ZW, st, force_groups, groups_ng, slope_f, slope_s);
+  }
+  if (work == nullptr) return YOLAT_E_INVALID;
+  if (route != nullptr) *route = 5;
+  const long fc = (long)(yolat_fusion_pair_eval_act_work_elems(N, F) / (size_t)N);
+  if (groups_ng != nullptr) { groups_ng[0] = (int)yl_cdiv(F, fc); groups_ng[1] = (int)yl_cdiv(fc, 64); }
+  for (long c0 = 0; c0 < F; c0 += fc) {
+    const long wd = F - c0 < fc ? F - c0 : fc;
+    Epilogue e = plain_epilogue();
+    e.bias = w.bf ? w.bf + c0 : nullptr; e.scale = w.sf + c0; e.shift = w.tf + c0; e.relu = 0; e.Y = work; e.ldy = wd;
+    YL_TRY(launch_hgemm(HOp{feats, ld, (int)N}, HOp{w.Wf + c0 * D, D, (int)wd}, e, N, wd, D, st));
+    YL_TRY(yolat_segment_act_max(work, wd, N, wd, slope_f, seg_ptr, P, Z + c0, ZW, (yolat_stream_t)st));
+  }
+  Epilogue e1 = plain_epilogue();
+  e1.bias = w.bfs; e1.scale = w.sfs; e1.shift = w.tfs; e1.Y = Z + F + D; e1.ldy = ZW;
+  return launch_hgemm_act(FOp{Z + 2 * F + D, ZW, (int)P}, HOp{w.Wfs, D, (int)F}, e1, P, F, D, slope_s, st);
+}
 }  // namespace
 
 // one profiled stage: `body` is a statement block that may `return` an error code
@@ -785,7 +921,7 @@ int yl_fusion_stage_bf16(const FusionStageH& w, const u16* feats, long ld, long 
 extern "C" size_t yolat_forward_eval_bf16_workspace_bytes(const yolat_model_eval_bf16* mh, int64_t N, int64_t E,
                                                           int64_t P) {
   if (!mh || !mh->base || N <= 0 || E < 0 || P <= 0) return 0;
-  return carve_h(mh->base, N, E, P, nullptr).bytes;
+  return carve_h(mh, N, E, P, nullptr).bytes;
 }
 
 static int forward_eval_bf16_impl(const yolat_model_eval_bf16* mh, const float* x, int64_t ldx, const int64_t* edge,
@@ -851,7 +987,7 @@ static int forward_eval_bf16_impl(const yolat_model_eval_bf16* mh, const float* 
   if (N > (1LL << 23) || E > (1LL << 29)) return YOLAT_E_UNSUPPORTED;     // 32-bit element offsets in the gathers
   if (P * 2 * (mh->base->F + mh->base->C * mh->base->n_blocks_out) >= (1LL << 32)) return YOLAT_E_UNSUPPORTED;
   const yolat_model_eval* m = mh->base;
-  PlanH p = carve_h(m, N, E, P, workspace);
+  PlanH p = carve_h(mh, N, E, P, workspace);
   if (p.bytes > workspace_bytes) return YOLAT_E_INVALID;
   if (g != nullptr) YL_TRY(yl_adopt_graph(g, E, &p));      // prepared graph (collate.hip): the caller's arrays
   hipStream_t st = (hipStream_t)stream;
@@ -991,6 +1127,11 @@ static int forward_eval_bf16_impl(const yolat_model_eval_bf16* mh, const float* 
   YL_HSTAGE(nm, 2.0 * (N + P) * D * F, 2.0 * (N * D + 2.0 * D * F) + 4.0 * (2.0 * P * F + N + P * D), {
     const FusionStageH w{mh->Wf, mh->Wfs, m->bf, m->sf, m->tf, m->bfs, m->sfs, m->tfs,
                          mh->Wf_fold, mh->tf_fold, mh->Wfs_fold, mh->tfs_fold};
+    if (m->act != YOLAT_ACT_RELU)
+      // leaky: signed start values over the zero block of the pooling prologue, then the activation-aware launches
+      YL_TRY(yl_fusion_stage_bf16_act(w, p.feats, D, N, D, p.node_seg, p.seg_ptr, p.Z, ZW, P, F, m->act_slope[0],
+                                      m->act_slope[1], p.act_work, h8_route(mh, D), st));
+    else
     YL_TRY(yl_fusion_stage_bf16(w, p.feats, D, N, D, p.node_seg, p.Z, ZW, P, F, st));
   });
   {
@@ -1002,11 +1143,22 @@ static int forward_eval_bf16_impl(const yolat_model_eval_bf16* mh, const float* 
     e.bias = m->bc1; e.scale = m->sc1; e.shift = m->tc1; e.relu = 1; e.Y = nullptr; e.Yh = c1h; e.ldy = m->H1;
     snprintf(nm, sizeof nm, "cls1_bf16[P x %ld -> %ld]", ZW, (long)m->H1);
     YL_HSTAGE(nm, 2.0 * P * ZW * m->H1, 4.0 * P * ZW + 2.0 * P * m->H1 + 2.0 * ZW * m->H1,
-              { YL_TRY(launch_hgemm(FOp{p.Z, ZW, (int)P}, HOp{mh->Wc1, ZW, (int)m->H1}, e, P, m->H1, ZW, st)); });
+    {
+      if (m->act != YOLAT_ACT_RELU)       // the activation in fp32 before the bf16 store (k_hgemm_act)
+        YL_TRY(launch_hgemm_act(FOp{p.Z, ZW, (int)P}, HOp{mh->Wc1, ZW, (int)m->H1}, e, P, m->H1, ZW, m->act_slope[2], st));
+      else
+      YL_TRY(launch_hgemm(FOp{p.Z, ZW, (int)P}, HOp{mh->Wc1, ZW, (int)m->H1}, e, P, m->H1, ZW, st));
+    });
     e.bias = m->bc2; e.scale = m->sc2; e.shift = m->tc2; e.Yh = c2h; e.ldy = m->H2;
     snprintf(nm, sizeof nm, "cls2_bf16[P x %ld -> %ld]", (long)m->H1, (long)m->H2);
     YL_HSTAGE(nm, 2.0 * P * m->H1 * m->H2, 2.0 * (P * m->H1 + P * m->H2) + 2.0 * m->H1 * m->H2,
-              { YL_TRY(launch_hgemm(HOp{c1h, m->H1, (int)P}, HOp{mh->Wc2, m->H1, (int)m->H2}, e, P, m->H2, m->H1, st)); });
+    {
+      if (m->act != YOLAT_ACT_RELU)
+        YL_TRY(launch_hgemm_act(HOp{c1h, m->H1, (int)P}, HOp{mh->Wc2, m->H1, (int)m->H2}, e, P, m->H2, m->H1, m->act_slope[3],
+                                st));
+      else
+      YL_TRY(launch_hgemm(HOp{c1h, m->H1, (int)P}, HOp{mh->Wc2, m->H1, (int)m->H2}, e, P, m->H2, m->H1, st));
+    });
     e = plain_epilogue();
     e.bias = m->bc3; e.Y = logits; e.ldy = ld_logits;
     snprintf(nm, sizeof nm, "cls3_bf16[P x %ld -> %d]", (long)m->H2, (int)m->n_classes);
@@ -1097,6 +1249,55 @@ extern "C" int yolat_debug_hgemm_eval_bf16(const void* A, int a_f32, int64_t lda
   if (a_f32)
     return launch_hgemm(FOp{reinterpret_cast<const float*>(A), lda, (int)M}, b, e, M, Nout, K, (hipStream_t)stream, tile_form);
   return launch_hgemm(HOp{reinterpret_cast<const u16*>(A), lda, (int)M}, b, e, M, Nout, K, (hipStream_t)stream, tile_form);
+}
+
+// the same two stages of a leaky model (act.hip), launched as the forward launches them: the fusion pair with its start
+// values (route 0: yolat_pool_init_signed + the ACT instantiation of k_hfusion_rows8; route 5: the materialising form on
+// `work`, yolat_fusion_pair_eval_act_work_elems(N, F) floats), and the tile GEMM with the activation in its epilogue
+extern "C" int yolat_debug_fusion_pair_eval_bf16_act(const uint16_t* feats, int64_t ld, int64_t N, int64_t D,
+                                                     const int32_t* node_seg, const int32_t* seg_ptr, float* Z, int64_t ldz,
+                                                     int64_t P, int64_t F, const uint16_t* Wf, const uint16_t* Wfs,
+                                                     const float* bf, const float* sf, const float* tf, const float* bfs,
+                                                     const float* sfs, const float* tfs, const uint16_t* Wf_fold,
+                                                     const float* tf_fold, const uint16_t* Wfs_fold, const float* tfs_fold,
+                                                     const float* slope_f, const float* slope_s, float* work,
+                                                     int force_groups, int* route, int* groups_ng, yolat_stream_t stream) {
+  if (!feats || !node_seg || !seg_ptr || !Z || !Wf || !Wfs || !sf || !tf || !sfs || !tfs || !slope_f || !slope_s || N <= 0 ||
+      P <= 0 || F <= 0 || D <= 0 || force_groups < 0)
+    return YOLAT_E_INVALID;
+  if (N >= (1LL << 31) || P >= (1LL << 31) || ld < D || ldz < 2 * (F + D)) return YOLAT_E_INVALID;
+  if (P * ldz >= (1LL << 32)) return YOLAT_E_UNSUPPORTED;                    // 32-bit element offsets into the pooled matrix
+  if (D % 64 != 0 || F % 32 != 0 || ld % 8 != 0 || ldz % 4 != 0 || !yl_aligned16(feats) || !yl_aligned16(Z) ||
+      !yl_aligned16(Wf) || !yl_aligned16(Wfs) || (Wf_fold && !yl_aligned16(Wf_fold)) || (Wfs_fold && !yl_aligned16(Wfs_fold)) ||
+      (work && !yl_aligned16(work)))
+    return YOLAT_E_UNSUPPORTED;
+  const bool h8 = (D == 64 || D == 128) && F % 64 == 0 && Wf_fold && Wfs_fold && tf_fold && tfs_fold;
+  if (!h8 && !work) return YOLAT_E_INVALID;
+  const FusionStageH w{Wf, Wfs, bf, sf, tf, bfs, sfs, tfs, Wf_fold, tf_fold, Wfs_fold, tfs_fold};
+  return yl_fusion_stage_bf16_act(w, feats, ld, N, D, node_seg, seg_ptr, Z, ldz, P, F, slope_f, slope_s, work, h8,
+                                  (hipStream_t)stream, force_groups, route, groups_ng);
+}
+
+extern "C" int yolat_debug_hgemm_eval_bf16_act(const void* A, int a_f32, int64_t lda, int64_t M, int64_t K, const uint16_t* W,
+                                               int64_t ldw, int64_t Nout, const float* bias, const float* scale,
+                                               const float* shift, const float* slope, void* Y, int y_bf16, int64_t ldy,
+                                               int* tile_form, yolat_stream_t stream) {
+  if (!A || !W || !Y || !slope || M <= 0 || K <= 0 || Nout <= 0 || M >= (1LL << 31) || Nout >= (1LL << 31) || lda < K ||
+      ldw < K || ldy < Nout || (scale == nullptr) != (shift == nullptr))
+    return YOLAT_E_INVALID;
+  if (K % 64 != 0 || lda % (a_f32 ? 4 : 8) != 0 || ldw % 8 != 0 || !yl_aligned16(A) || !yl_aligned16(W) ||
+      (y_bf16 ? (((uintptr_t)Y) & 1) != 0 : (((uintptr_t)Y) & 3) != 0))
+    return YOLAT_E_UNSUPPORTED;
+  Epilogue e = plain_epilogue();
+  e.bias = bias; e.scale = scale; e.shift = shift; e.ldy = ldy;
+  if (y_bf16) e.Yh = reinterpret_cast<u16*>(Y);
+  else e.Y = reinterpret_cast<float*>(Y);
+  const HOp b{W, ldw, (int)Nout};
+  if (a_f32)
+    return launch_hgemm_act(FOp{reinterpret_cast<const float*>(A), lda, (int)M}, b, e, M, Nout, K, slope, (hipStream_t)stream,
+                            tile_form);
+  return launch_hgemm_act(HOp{reinterpret_cast<const u16*>(A), lda, (int)M}, b, e, M, Nout, K, slope, (hipStream_t)stream,
+                          tile_form);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -13,6 +13,11 @@
 // atomicMax of segmax.hpp (values >= 0: integer order == float order, exact, order-independent).
 // The small problem (fusion_block_super on the P per-proposal means, fp32 rows converted while loading, plain ReLU
 // store) rides in the same launch, its workgroups first.
+// ACT = 1 (act = leakyrelu / prelu, act.hip): act(y) = y > 0 ? y : a * y per element before any maximum, the two slopes
+// read from device memory by every launch.  The values are signed, so the table holds order-preserving keys under an
+// unsigned ds_max, the walk starts from -inf and flushes every run, and the drain decodes the key (segmax.hpp,
+// fx_segmax2_lds_act / fx_tab_drain_signed); the pooled matrix starts from yolat_pool_init_signed instead of zeros.  The
+// ACT = 0 instantiations are the kernel as it was: the slopes argument is an empty structure nothing reads.
 #include "segmax.hpp"
 #include "internal.hpp"
 #include <stdlib.h>
@@ -51,8 +56,12 @@ struct H8Prob {
   int F, tm, groups, ng;
 };
 
-template <int KD>
-__global__ void __launch_bounds__(512, 2) k_hfusion_rows8(H8Prob p0, H8Prob p1) {
+// slopes of the two problems (node rows, super rows) as an argument only the ACT instantiations carry
+template <int ACT> struct H8Slopes {};
+template <> struct H8Slopes<1> { const float* s0; const float* s1; };
+
+template <int KD, int ACT>
+__global__ void __launch_bounds__(512, 2) k_hfusion_rows8(H8Prob p0, H8Prob p1, H8Slopes<ACT> slopes) {
   constexpr int KS = KD / 16, RS = KD + 8, CPR = KD / 8;    // k steps, LDS row stride (bf16), 16-byte chunks per row
   constexpr int NW = 64 * CPR / 512;                        // 16-byte pieces of one W tile per thread
   static_assert((64 * CPR) % 512 == 0, "W tile / thread mismatch");
@@ -114,6 +123,8 @@ __global__ void __launch_bounds__(512, 2) k_hfusion_rows8(H8Prob p0, H8Prob p1) 
   }
   H8_STAMP(1);
   const bool pooling = seg != nullptr;
+  float slope = 0.f;
+  if constexpr (ACT != 0) slope = *(small ? slopes.s1 : slopes.s0);
   FxTile tile{};
   if (pooling) {
     const int row_lo = rt * 256, row_hi = yl_min(row_lo + 256, N);
@@ -161,7 +172,12 @@ __global__ void __launch_bounds__(512, 2) k_hfusion_rows8(H8Prob p0, H8Prob p1) 
       load_w(ct + 1, rw);                              // in flight while the MFMAs below run
     }
     // the previous column tile's pooled maxima (complete since its closing barrier) go out while this tile's MFMAs run
+    if constexpr (ACT != 0) {
+      if (pooling && j > 0)
+        fx_tab_drain_signed(reinterpret_cast<unsigned*>(tab_s[buf ^ 1]), tile, out, (unsigned)ldo, ct - 1, F, tid, 512);
+    } else {
     if (pooling && j > 0) fx_tab_drain(tab_s[buf ^ 1], tile, out, (unsigned)ldo, ct - 1, F, tid, 512);
+    }
     if (j >= 4 && j < 8) H8_STAMP(24 + (j - 4));        // after the drain of tiles 4..7
     const u16* wb = &Ws[buf][l31 * RS + 8 * lhi];
 #pragma unroll
@@ -178,6 +194,10 @@ __global__ void __launch_bounds__(512, 2) k_hfusion_rows8(H8Prob p0, H8Prob p1) 
     __builtin_amdgcn_s_waitcnt(0x0F70);                // vmcnt(0)
     if (j >= 4 && j < 8) H8_STAMP(5 + 4 * (j - 4));
     if (pooling) {
+      if constexpr (ACT != 0)
+        fx_segmax2_lds_act(acc0, acc1, reinterpret_cast<unsigned*>(tab_s[buf]), out, (unsigned)ldo, segs, tile.seg_base, lhi,
+                           (unsigned)c0, (unsigned)l31, c0 < F, c1 < F, runs, slope);
+      else
       fx_segmax2_lds(acc0, acc1, tab_s[buf], out, (unsigned)ldo, segs, tile.seg_base, lhi, (unsigned)c0, (unsigned)l31, c0 < F,
                      c1 < F, runs);
     } else {
@@ -188,8 +208,13 @@ __global__ void __launch_bounds__(512, 2) k_hfusion_rows8(H8Prob p0, H8Prob p1) 
         const unsigned row = rb + (r & 3) + 8 * (r >> 2);
         if ((int)row < N) {
           float* o = out + (unsigned long)row * (unsigned long)ldo;
+          if constexpr (ACT != 0) {
+            if (c0 < F) o[c0] = acc0[r] > 0.f ? acc0[r] : slope * acc0[r];
+            if (c1 < F) o[c1] = acc1[r] > 0.f ? acc1[r] : slope * acc1[r];
+          } else {
           if (c0 < F) o[c0] = fmaxf(acc0[r], 0.f);
           if (c1 < F) o[c1] = fmaxf(acc1[r], 0.f);
+          }
         }
       }
     }
@@ -199,17 +224,24 @@ __global__ void __launch_bounds__(512, 2) k_hfusion_rows8(H8Prob p0, H8Prob p1) 
   }
   H8_STAMP(20);
   H8_STAMP_META();
+  if constexpr (ACT != 0) {
+    if (pooling)
+      fx_tab_drain_signed(reinterpret_cast<unsigned*>(tab_s[(ngl - 1) & 1]), tile, out, (unsigned)ldo, ct0 + ngl - 1, F, tid, 512);
+  } else {
   if (pooling) fx_tab_drain(tab_s[(ngl - 1) & 1], tile, out, (unsigned)ldo, ct0 + ngl - 1, F, tid, 512);
+  }
 }
 
 // A [N, lda] bf16 x Wf [F, D] (folded) with the per-proposal max into pool [*, ld_pool] (columns 0..F), and
 // As [P, lda_s] fp32 x Wfs [F, D] (folded) -> relu -> sup_out [P, ld_sup].  D in {64, 128}; F % 64 == 0.
 // force_groups > 0 replaces the planned number of column groups of the N-row problem (tests: the multi-tile loop at small
 // N); groups_ng != nullptr receives that problem's (groups, ng).
+// slope_f / slope_s (both or none): the ACT instantiation; `pool` then starts from yolat_pool_init_signed, not from zeros.
 int yl_hfusion_rows8(const uint16_t* A, int64_t lda, int64_t N, int64_t D, const uint16_t* Wf, const float* tf,
                      const int32_t* seg, float* pool, int64_t ld_pool, int64_t F, const float* As, int64_t lda_s, int64_t P,
                      const uint16_t* Wfs, const float* tfs, float* sup_out, int64_t ld_sup, hipStream_t st,
-                     int force_groups, int* groups_ng) {
+                     int force_groups, int* groups_ng, const float* slope_f, const float* slope_s) {
+  if ((slope_f == nullptr) != (slope_s == nullptr)) return YOLAT_E_INVALID;
   if ((D != 64 && D != 128) || F % 64 != 0 || N <= 0 || P <= 0) return YOLAT_E_UNSUPPORTED;
   if (!yl_aligned16(A) || !yl_aligned16(As) || !yl_aligned16(Wf) || !yl_aligned16(Wfs) || lda % 8 != 0 || lda_s % 4 != 0)
     return YOLAT_E_UNSUPPORTED;
@@ -247,8 +279,15 @@ int yl_hfusion_rows8(const uint16_t* A, int64_t lda, int64_t N, int64_t D, const
   const long total = n1p + (long)p0.tm * p0.groups;
   if (total >= (1LL << 31)) return YOLAT_E_UNSUPPORTED;
   if (groups_ng != nullptr) { groups_ng[0] = p0.groups; groups_ng[1] = p0.ng; }
-  if (D == 128) hipLaunchKernelGGL(k_hfusion_rows8<128>, dim3((unsigned)total), dim3(512), 0, st, p0, p1);
-  else hipLaunchKernelGGL(k_hfusion_rows8<64>, dim3((unsigned)total), dim3(512), 0, st, p0, p1);
+  if (slope_f != nullptr) {
+    const H8Slopes<1> sl{slope_f, slope_s};
+    if (D == 128) hipLaunchKernelGGL((k_hfusion_rows8<128, 1>), dim3((unsigned)total), dim3(512), 0, st, p0, p1, sl);
+    else hipLaunchKernelGGL((k_hfusion_rows8<64, 1>), dim3((unsigned)total), dim3(512), 0, st, p0, p1, sl);
+  } else if (D == 128) {
+    hipLaunchKernelGGL((k_hfusion_rows8<128, 0>), dim3((unsigned)total), dim3(512), 0, st, p0, p1, H8Slopes<0>{});
+  } else {
+    hipLaunchKernelGGL((k_hfusion_rows8<64, 0>), dim3((unsigned)total), dim3(512), 0, st, p0, p1, H8Slopes<0>{});
+  }
   YL_LAUNCH_CHECK();
   return 0;
 }

@@ -169,11 +169,14 @@ int yl_conv_local_bf16(const yolat_model_eval_bf16* mh, const void* pack, const 
                        int64_t N, int64_t E, int64_t P, uint16_t* feats, int64_t ld_feats, float* Z, int64_t ldz, int32_t* flag,
                        int32_t flag_val, hipStream_t st);
 // bf16 fusion block with the per-proposal max, nodes and proposals in one launch (fusion_h8.hip); force_groups > 0
-// replaces the planned column groups of the N-row problem, groups_ng receives that problem's (groups, ng)
+// replaces the planned column groups of the N-row problem, groups_ng receives that problem's (groups, ng); slope_f /
+// slope_s (both or none): the activation-aware instantiation for a leaky activation — `pool` then starts from
+// yolat_pool_init_signed, not from zeros
 int yl_hfusion_rows8(const uint16_t* A, int64_t lda, int64_t N, int64_t D, const uint16_t* Wf, const float* tf,
                      const int32_t* seg, float* pool, int64_t ld_pool, int64_t F, const float* As, int64_t lda_s, int64_t P,
                      const uint16_t* Wfs, const float* tfs, float* sup_out, int64_t ld_sup, hipStream_t st,
-                     int force_groups = 0, int* groups_ng = nullptr);
+                     int force_groups = 0, int* groups_ng = nullptr, const float* slope_f = nullptr,
+                     const float* slope_s = nullptr);
 // the weight gradient of a wide Linear on the bf16x6 GEMM: worthwhile?, its workspace, the launch (gemm_x6.hip)
 bool yl_bwd_w_x6_ok(int64_t M, int64_t Nout, int64_t K);
 size_t yl_bwd_w_x6_work_elems(int64_t M, int64_t Nout, int64_t K);
@@ -245,3 +248,20 @@ extern "C" int yolat_debug_hgemm_eval_bf16(const void* A, int a_f32, int64_t lda
                                            int64_t ldw, int64_t Nout, const float* bias, const float* scale,
                                            const float* shift, int relu, void* Y, int y_bf16, int64_t ldy, int* tile_form,
                                            yolat_stream_t stream);
+//   the two stages above for a leaky model (act.hip): the slopes by address, as every launch reads them.  Fusion pair: the
+//     start values of Z[:, 0:F] are written by the call (seg_ptr [P+1]); *route: 0 = yolat_pool_init_signed + the ACT
+//     instantiation of k_hfusion_rows8 (D in {64, 128}, F % 64 == 0, fold pointers given), 5 = the materialising form for
+//     every other shape on `work` (yolat_fusion_pair_eval_act_work_elems(N, F) floats; groups_ng = (column ranges, tiles per
+//     range)).  Tile GEMM: Y = act(epi(A . W^T)) computed in fp32 before a bf16 store
+extern "C" int yolat_debug_fusion_pair_eval_bf16_act(const uint16_t* feats, int64_t ld, int64_t N, int64_t D,
+                                                     const int32_t* node_seg, const int32_t* seg_ptr, float* Z, int64_t ldz,
+                                                     int64_t P, int64_t F, const uint16_t* Wf, const uint16_t* Wfs,
+                                                     const float* bf, const float* sf, const float* tf, const float* bfs,
+                                                     const float* sfs, const float* tfs, const uint16_t* Wf_fold,
+                                                     const float* tf_fold, const uint16_t* Wfs_fold, const float* tfs_fold,
+                                                     const float* slope_f, const float* slope_s, float* work,
+                                                     int force_groups, int* route, int* groups_ng, yolat_stream_t stream);
+extern "C" int yolat_debug_hgemm_eval_bf16_act(const void* A, int a_f32, int64_t lda, int64_t M, int64_t K, const uint16_t* W,
+                                               int64_t ldw, int64_t Nout, const float* bias, const float* scale,
+                                               const float* shift, const float* slope, void* Y, int y_bf16, int64_t ldy,
+                                               int* tile_form, yolat_stream_t stream);

@@ -237,6 +237,67 @@ __device__ __forceinline__ void fx_tab_drain(int* tab, const FxTile& t, float* p
     }
   }
 }
+
+// ---- the same pre-reduction for SIGNED values (leaky activations, act.hip; the bf16 rows kernel fusion_h8.hip) ----------
+// The table holds order-preserving KEYS (the transform of fx_key below): u -> sign bit set ? ~u : u | 0x80000000 maps a
+// float to an unsigned number whose order is the float order, so an unsigned ds_max on the keys is the float maximum, exact
+// and order-independent.  -inf maps to 0x007FFFFF and no float maps to 0 once a NaN is merged as the positive quiet NaN
+// 0x7FC00000 (key 0xFFC00000: above +inf = 0xFF800000, so it wins and stays): key 0 means "empty", the table starts and is
+// left as zeros like the ReLU one.
+__device__ __forceinline__ unsigned fx_skey(float v) {
+  unsigned u = (v != v) ? 0x7FC00000u : __float_as_uint(v);
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float fx_skey_value(unsigned k) {
+  return __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k);
+}
+// fx_segmax2_lds for act(y) = y > 0 ? y : a * y applied per element BEFORE the maximum (see fx_segmax2_off_act): the
+// running maximum starts at -inf and keeps a NaN, every run is flushed; proposals beyond the table go to the pooled
+// matrix with fx_signed_max (which starts from yolat_pool_init_signed, like the elements the drain merges).
+__device__ __forceinline__ void fx_segmax2_lds_act(const f32x16& acc0, const f32x16& acc1, unsigned* tab, float* pool,
+                                                   unsigned ldpool, const int* segs, int seg_base, int lhi, unsigned c0,
+                                                   unsigned cl, bool ok0, bool ok1, const FxRuns& sr, float a) {
+  float cur0 = -INFINITY, cur1 = -INFINITY;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const float v0 = acc0[r] > 0.f ? acc0[r] : a * acc0[r], v1 = acc1[r] > 0.f ? acc1[r] : a * acc1[r];
+    cur0 = (v0 > cur0 || v0 != v0) ? v0 : cur0;
+    cur1 = (v1 > cur1 || v1 != v1) ? v1 : cur1;
+    if ((sr.uflush >> r) & 1u) {
+      if ((sr.flush_bits >> r) & 1u) {
+        const int sg = segs[(r & 3) + 8 * (r >> 2) + 4 * lhi];
+        const unsigned pos = (unsigned)(sg - seg_base);
+        if (pos < (unsigned)FX_NP) {
+          if (ok0) atomicMax(tab + pos * 64 + cl, fx_skey(cur0));
+          if (ok1) atomicMax(tab + pos * 64 + 32 + cl, fx_skey(cur1));
+        } else {
+          float* o = pool + ((unsigned)sg * ldpool + c0);
+          if (ok0) fx_signed_max(o, cur0);
+          if (ok1) fx_signed_max(o + 32, cur1);
+        }
+        cur0 = -INFINITY; cur1 = -INFINITY;              // the lane's next row starts a new run
+      }
+    }
+  }
+}
+// fx_tab_drain for the key table: a proposal wholly inside the tile's rows is written with a plain store (every one of its
+// rows went through this table), the at most two shared with the neighbouring row tiles are merged with fx_signed_max
+__device__ __forceinline__ void fx_tab_drain_signed(unsigned* tab, const FxTile& t, float* pool, unsigned ldpool, int ct, int F,
+                                                    int tid, int nthreads) {
+  for (int e = tid; e < t.np * 64; e += nthreads) {
+    const unsigned k = tab[e];
+    if (k != 0u) {
+      tab[e] = 0u;
+      const int pos = e >> 6, col = ct * 64 + (e & 63);
+      if (col < F) {
+        float* o = pool + ((unsigned)(t.seg_base + pos) * ldpool + (unsigned)col);
+        const float v = fx_skey_value(k);
+        if ((pos == 0 && t.first_shared) || pos == t.last_shared_pos) fx_signed_max(o, v);
+        else *o = v;
+      }
+    }
+  }
+}
 }  // namespace
 
 namespace {

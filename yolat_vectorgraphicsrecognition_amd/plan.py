@@ -91,9 +91,7 @@ class EvalPlan(object):
     def __init__(self, model, precision="fp32"):
         if precision not in ("fp32", "bf16"):
             raise ValueError("precision must be 'fp32' or 'bf16'")
-        from .engine import model_is_relu, model_norm
-        if precision != "fp32" and not model_is_relu(model):
-            raise ValueError("the %s eval plan covers act = relu only (this model's act is not)" % precision)
+        from .engine import model_norm
         if precision != "fp32" and model_norm(model) != "batch":
             raise ValueError("the %s eval plan covers norm = batch only (this model's norm is %s)"
                              % (precision, model_norm(model)))
