@@ -623,7 +623,7 @@ def test_edge_chain_kernel_soak_50_runs_bit_identical_and_exact(shape):
 @pytest.mark.gpu
 @pytest.mark.parametrize("M,pro", [(70001, True), (65536, False), (131072 + 33, True)])
 def test_linear64_bf16_row_stream_is_bit_identical_to_the_tile_kernel(M, pro):
-    """k_hlin64_stream (bf16_eval.hip, round 4; taken by yolat_linear_fwd_h for K = Nout = 64, M >= 65536: the second edge
+    """k_hlin64_stream (bf16_linear.hip, round 4; taken by yolat_linear_fwd_h for K = Nout = 64, M >= 65536: the second edge
     Linear of a bf16-storage training conv layer, torch_vertex.py:331 nn.3) against the hgemm tile kernel run on row ranges
     below the threshold (48 000 rows: a multiple of 32, the statistics' group size): bf16 outputs and fp32 (sum, M2)
     statistics BIT-identical, ragged last tile included; fp64 check of the product on the widened values."""

@@ -42,7 +42,7 @@ STAGES_BF16 = {
     "conv_local_bf16[all conv layers + pooling prologue, one launch]": ("k_conv_local_h", srcs("conv_local.hip", "base", "internal"), "all"),
     "edge_uv_mlp2_mean_bf16[E x (U+V+attr) -> 64 -> 64 -> mean]": ("k_edge_chain_h", srcs("edge_chain.hip", "base", "internal"), "all"),
     "fusion_gemm_bf16+segmax[N x 128 -> 1024 -> P] | super[P x 128 -> 1024]": ("k_hfusion_rows8<128", srcs("fusion_h8.hip", "base", "segmax", "internal"), "all"),
-    "node_uv_bf16[UV | lin_r | mlp_node, N x 64 -> 128+64+64]": ("k_hgemm_node3", srcs("bf16_eval.hip", *GEMM_NT, "internal"), "all"),
+    "node_uv_bf16[UV | lin_r | mlp_node, N x 64 -> 128+64+64]": ("k_hgemm_node3", srcs("bf16_eval.hip", *GEMM_NT, "hgemm", "internal"), "all"),
     "graph_prep[csr+attr+segments] + node_uv[layer 0, bf16 out]": ("k_prep_rows_node3", srcs("graph.hip", *GEMM_NT, "internal"), "all"),
 }
 

@@ -6,7 +6,7 @@
 // by the node-side GEMM) and the 4 attr columns:   h1_e = relu(U'[dst_e] + V'[src_e] + Wc4' . attr_e).
 //
 // Why a new structure (profiles/r01_fwd_cfg5_bf16_kernel_stats_v1.txt: 99 us per layer at E = 1.2 M, 0.17 of its bound):
-// the node-tile kernel (bf16_eval.hip, k_edge_uv_mlp2_mean_h) unpacks every gathered bf16 pair, adds, runs four packed
+// the node-tile kernel (k_edge_uv_mlp2_mean_h, below) unpacks every gathered bf16 pair, adds, runs four packed
 // FMAs, packs, writes the 64 x 64 tile to LDS, reads it back as MFMA fragments, writes the fp32 messages to LDS and
 // reads them a third time for the per-node sums: ~13 vector-ALU operations and three LDS passes per hidden element.
 // The matrix cores, which run BESIDE the vector ALUs, sit at 4 % utilisation.
@@ -28,6 +28,8 @@
 //       the start of the step), scale by 1/deg and store the bf16 output row with 8-byte stores.
 // Vector-ALU work per hidden element drops from ~13 to ~1 (ReLU/convert) + 2 per message (ReLU, add); 20 MFMAs per 32
 // edges.  Deterministic: fixed summation order, no float atomics.
+// The file is the whole edge stage of the bf16 forward: this kernel, the node-tile kernel it replaced for large graphs (still
+// the choice for small or sparse ones), the dispatcher between them and the stage as an op of the C ABI.
 #include "base.hpp"
 #include "internal.hpp"
 #include <stdlib.h>
@@ -399,10 +401,10 @@ __global__ void __launch_bounds__(256, 3) k_edge_chain_h(
 }  // namespace
 
 // Launch: `wgs` workgroups of 4 independent waves; every wave walks two streams of `chunk` edges.
-int yl_edge_chain_bf16(const uint16_t* UV, int64_t ld_uv, const int32_t* src_csr, const int32_t* dst_csr,
-                       const float* attr_csr, const int32_t* row_ptr, int64_t N, int64_t E, const float* Wc4,
-                       const float* s1, const uint16_t* W2f, const float* t2f, const float* root, int64_t ld_r,
-                       uint16_t* f_out, int64_t ld_fo, hipStream_t st, YlGate gate) {
+static int yl_edge_chain_bf16(const uint16_t* UV, int64_t ld_uv, const int32_t* src_csr, const int32_t* dst_csr,
+                              const float* attr_csr, const int32_t* row_ptr, int64_t N, int64_t E, const float* Wc4,
+                              const float* s1, const uint16_t* W2f, const float* t2f, const float* root, int64_t ld_r,
+                              uint16_t* f_out, int64_t ld_fo, hipStream_t st, YlGate gate) {
   const long wgs = 768;        // measured: 256 / 512 / 768 / 1024 workgroups 63 / 52 / 49 / 62 us at cfg 5
   const long streams = 8 * wgs;
   long chunk = ((E + streams - 1) / streams + 15) / 16 * 16;
@@ -410,12 +412,197 @@ int yl_edge_chain_bf16(const uint16_t* UV, int64_t ld_uv, const int32_t* src_csr
   // every node must fall into some wave's node range: the last wave's range ends at N by construction
   const long need = (E + 2 * chunk - 1) / (2 * chunk);           // waves that own at least one chunk boundary < E
   const long grid = (need + 3) / 4 > 0 ? (need + 3) / 4 : 1;
-#define EC_LAUNCH(A)                                                                                                    \
-  hipLaunchKernelGGL(k_edge_chain_h<A>, dim3((unsigned)grid), dim3(256), 0, st, UV, (unsigned)ld_uv, src_csr, dst_csr,    \
-                     attr_csr, row_ptr, (int)N, (int)E, (int)chunk, Wc4, s1, W2f, t2f, root, (unsigned)ld_r, f_out,       \
-                     (unsigned)ld_fo, gate)
-  EC_LAUNCH(0);       // (template argument: the phase-ablation variants behind profiles/r03_edge_chain_bf16_ablation.txt)
-#undef EC_LAUNCH
+  // (template argument: the phase-ablation variants behind profiles/r03_edge_chain_bf16_ablation.txt)
+  hipLaunchKernelGGL(k_edge_chain_h<0>, dim3((unsigned)grid), dim3(256), 0, st, UV, (unsigned)ld_uv, src_csr, dst_csr, attr_csr,
+                     row_ptr, (int)N, (int)E, (int)chunk, Wc4, s1, W2f, t2f, root, (unsigned)ld_r, f_out, (unsigned)ld_fo, gate);
   YL_LAUNCH_CHECK();
   return 0;
 }
+
+// ------------------------------------------------------------------------------------------------
+// Factorised edge MLP + mean aggregation, bf16 storage (see k_edge_uv_mlp2_mean, edge.hip, for the scheme).
+// One workgroup = npt (<= 16) consecutive destination nodes = a contiguous CSR edge range, in passes of 64
+// edges.  Per pass: gather U'[dst] + V'[src] (bf16, 128 B per row) + W1c'.attr -> ReLU (fp32) -> bf16 tile in
+// LDS -> second Linear on bf16 MFMAs (this wave's W2 fragments live in registers for the whole kernel) ->
+// BN+ReLU -> fp32 tile in LDS -> per-node running sums in CSR order.  Output: f_out = bf16(root + sum/deg)
+// for EVERY node of the tile (nodes without in-edges get the root Linear alone, torch_vertex.py:324,337).
+//
+// Built to cut VALU work (PMC at cfg 5: a first version that applied layer 1's BatchNorm per edge in scalar fp32
+// kept the vector ALUs ~60 % busy — the kernel is instruction-bound, not latency-bound; a higher-occupancy variant
+// with the per-column constants in LDS was slower, 480 vs 435 us for the 4 layers; this one takes 383 us):
+//   * layer 1's folded BatchNorm is applied where it is cheap: the node-side GEMM epilogue stores
+//     U' = s1*U + (s1*b1 + t1) and V' = s1*V (uv_scale / uv_shift of yolat_model_eval_bf16), this kernel scales the
+//     four W1c columns once per workgroup, so a hidden activation is relu(U' + V' + W1c'.attr): 6 flops instead of 8;
+//   * those run as packed fp32 pairs (v_pk_add_f32 / v_pk_fma_f32), as does layer 2's folded BN (bias folded into
+//     the shift);
+//   * 32-bit element offsets for the gathers, 16-byte message rows (LDM = 68) for the per-node sums.
+typedef float ec_f32x2 __attribute__((ext_vector_type(2)));
+// NG = 16-node groups per tile: 1 (<= 16 nodes) or 4 (<= 64 nodes, for graphs with ~1 edge per node).
+template <int NG>
+static __global__ void __launch_bounds__(256, (NG == 1 ? 4 : 3)) k_edge_uv_mlp2_mean_h(
+    const u16* __restrict__ UV, unsigned ld_uv, const int* __restrict__ src, const int* __restrict__ dst,
+    const float* __restrict__ attr, const int* __restrict__ row_ptr, int N, int npt, const float* __restrict__ Wc4,
+    const float* __restrict__ s1, const u16* __restrict__ W2h, const float* __restrict__ b2,
+    const float* __restrict__ s2, const float* __restrict__ t2, const float* __restrict__ root, unsigned ld_r,
+    u16* __restrict__ f_out, unsigned ld_fo, int E, YlGate gate) {
+  if (yl_gate_dead(gate)) return;      // fall-back of the one-launch conv stack (conv_local.hip): dead launch
+  constexpr int LDH = 72, LDM = 68;       // 72 bf16 = 144 B rows (16-byte fragment reads: hgemm.hpp's YL_HRS)
+  __shared__ __attribute__((aligned(16))) u16 Hs[64 * LDH];   // layer-1 activations of the pass (bf16)
+  __shared__ __attribute__((aligned(16))) float Ms[64 * LDM];   // layer-2 messages of the pass (fp32)
+  __shared__ int rp[16 * NG + 1];
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int wm = wave >> 1, wn = wave & 1, l31 = lane & 31, lhi = lane >> 5;
+  const int n0 = blockIdx.x * npt;
+  const int nn = yl_min(npt, N - n0);
+  if (tid <= 16 * NG) rp[tid] = row_ptr[yl_min(n0 + tid, n0 + nn)];
+  const int q = tid & 15, rb = tid >> 4;              // gather role: columns 4q..4q+3 of rows rb + 16t
+  const int col = wn * 32 + l31;                      // MFMA role: output column of this lane
+  ec_bf16x8 w2f[4];
+#pragma unroll
+  for (int ks = 0; ks < 4; ++ks)
+    w2f[ks] = *reinterpret_cast<const ec_bf16x8*>(W2h + col * 64 + ks * 16 + lhi * 8);
+  // W1c' = s1 * W1c for this thread's 4 columns, as (column pair) x (attr component) packed pairs
+  ec_f32x2 wp[2][4];
+  {
+    float4 sc = make_float4(1.f, 1.f, 1.f, 1.f);
+    if (s1) sc = *reinterpret_cast<const float4*>(s1 + 4 * q);
+    const float scv[4] = {sc.x, sc.y, sc.z, sc.w};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const float4 w = *reinterpret_cast<const float4*>(Wc4 + (4 * q + j) * 4);
+      wp[j >> 1][0][j & 1] = w.x * scv[j]; wp[j >> 1][1][j & 1] = w.y * scv[j];
+      wp[j >> 1][2][j & 1] = w.z * scv[j]; wp[j >> 1][3][j & 1] = w.w * scv[j];
+    }
+  }
+  // folded form (the product path since ABI 4): W2h already carries s2, t2 is the complete shift -> b2 = s2 = NULL
+  const float sc2 = s2 ? s2[col] : 1.f;
+  const float sh2 = fmaf(b2 ? b2[col] : 0.f, sc2, t2 ? t2[col] : 0.f);    // (acc + b2)*s2 + t2 = acc*s2 + sh2
+  __syncthreads();
+  const int e0 = rp[0], e1 = rp[nn];
+  int my_b[NG], my_e[NG];                             // aggregation role: nodes rb + 16 j, columns 4q..
+  float4 rootv[NG], sum[NG];
+#pragma unroll
+  for (int j = 0; j < NG; ++j) {
+    my_b[j] = rp[yl_min(rb + 16 * j, nn)]; my_e[j] = rp[yl_min(rb + 16 * j + 1, nn)];
+    rootv[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (rb + 16 * j < nn) rootv[j] = *reinterpret_cast<const float4*>(root + (unsigned)(n0 + rb + 16 * j) * ld_r + 4 * q);
+    sum[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+  }
+  for (int c0 = e0; c0 < e1; c0 += 64) {
+    unsigned di[4], si[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      const int e = yl_min(c0 + rb + 16 * t, E - 1);
+      di[t] = (unsigned)dst[e]; si[t] = (unsigned)src[e];
+    }
+    ec_u32x2 u[4], v[4];
+    float4 a[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      const unsigned e = (unsigned)yl_min(c0 + rb + 16 * t, E - 1);
+      u[t] = *reinterpret_cast<const ec_u32x2*>(UV + (di[t] * ld_uv + 4 * q));
+      v[t] = *reinterpret_cast<const ec_u32x2*>(UV + (si[t] * ld_uv + 64 + 4 * q));
+      a[t] = *reinterpret_cast<const float4*>(attr + e * 4u);
+    }
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      ec_f32x2 z0, z1, uu, vv;
+      uu.x = yl_bf16_lo(u[t].x); uu.y = yl_bf16_hi(u[t].x); vv.x = yl_bf16_lo(v[t].x); vv.y = yl_bf16_hi(v[t].x);
+      z0 = uu + vv;
+      uu.x = yl_bf16_lo(u[t].y); uu.y = yl_bf16_hi(u[t].y); vv.x = yl_bf16_lo(v[t].y); vv.y = yl_bf16_hi(v[t].y);
+      z1 = uu + vv;
+      const ec_f32x2 ax = {a[t].x, a[t].x}, ay = {a[t].y, a[t].y}, az = {a[t].z, a[t].z}, aw = {a[t].w, a[t].w};
+      z0 = __builtin_elementwise_fma(ax, wp[0][0], z0); z1 = __builtin_elementwise_fma(ax, wp[1][0], z1);
+      z0 = __builtin_elementwise_fma(ay, wp[0][1], z0); z1 = __builtin_elementwise_fma(ay, wp[1][1], z1);
+      z0 = __builtin_elementwise_fma(az, wp[0][2], z0); z1 = __builtin_elementwise_fma(az, wp[1][2], z1);
+      z0 = __builtin_elementwise_fma(aw, wp[0][3], z0); z1 = __builtin_elementwise_fma(aw, wp[1][3], z1);
+      ec_u32x2 hp;
+      hp.x = yl_pack_bf16(fmaxf(z0.x, 0.f), fmaxf(z0.y, 0.f));
+      hp.y = yl_pack_bf16(fmaxf(z1.x, 0.f), fmaxf(z1.y, 0.f));
+      *reinterpret_cast<ec_u32x2*>(Hs + (rb + 16 * t) * LDH + 4 * q) = hp;
+    }
+    __syncthreads();                      // Hs complete; also: every thread is past the previous pass's Ms reads
+    f32x16 acc2;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc2[r] = 0.f;
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks) {
+      const ec_bf16x8 av = *reinterpret_cast<const ec_bf16x8*>(Hs + (wm * 32 + l31) * LDH + ks * 16 + lhi * 8);
+      acc2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av, w2f[ks], acc2, 0, 0, 0);
+    }
+    {
+      const ec_f32x2 s2p = {sc2, sc2}, h2p = {sh2, sh2};
+#pragma unroll
+      for (int r = 0; r < 16; r += 2) {
+        ec_f32x2 m = {acc2[r], acc2[r + 1]};
+        m = __builtin_elementwise_fma(m, s2p, h2p);
+        const int row = wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * lhi;
+        Ms[row * LDM + col] = fmaxf(m.x, 0.f);
+        Ms[(row + 1) * LDM + col] = fmaxf(m.y, 0.f);
+      }
+    }
+    __syncthreads();                      // Ms complete; every wave is done reading Hs
+#pragma unroll
+    for (int j = 0; j < NG; ++j) {
+      if (rb + 16 * j < nn) {             // rows of node rb + 16 j inside this pass, ascending edge order
+        const int lo = (my_b[j] > c0 ? my_b[j] : c0) - c0;
+        const int hi = (my_e[j] < c0 + 64 ? my_e[j] : c0 + 64) - c0;
+        for (int e = lo; e < hi; ++e) {
+          const float4 m = *reinterpret_cast<const float4*>(Ms + e * LDM + 4 * q);
+          sum[j].x += m.x; sum[j].y += m.y; sum[j].z += m.z; sum[j].w += m.w;
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < NG; ++j) {
+    if (rb + 16 * j < nn) {
+      const int deg = my_e[j] - my_b[j];
+      const float inv = 1.f / (float)(deg > 1 ? deg : 1);
+      ec_u32x2 o;
+      o.x = yl_pack_bf16(fmaf(sum[j].x, inv, rootv[j].x), fmaf(sum[j].y, inv, rootv[j].y));
+      o.y = yl_pack_bf16(fmaf(sum[j].z, inv, rootv[j].z), fmaf(sum[j].w, inv, rootv[j].w));
+      *reinterpret_cast<ec_u32x2*>(f_out + ((unsigned)(n0 + rb + 16 * j) * ld_fo + 4 * q)) = o;
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
+// edge stage dispatch: register-chained MFMA waves (k_edge_chain_h) for large, dense-enough graphs, node tiles
+// otherwise.  Both take the folded second Linear (W2f = bf16(diag(s2) W2), t2f = s2 b2 + t2).
+// ------------------------------------------------------------------------------------------------
+int yl_edge_uv_mlp2_mean_bf16_impl(const u16* UV, long ld_uv, const int* src, const int* dst, const float* attr,
+                                   const int* row_ptr, long N, long E, const float* Wc4, const float* s1, const u16* W2f,
+                                   const float* t2f, const float* root, long ld_r, u16* f_out, long ld_fo, int variant,
+                                   hipStream_t st, YlGate gate) {
+  // the chained kernel walks the EDGE list: it needs enough edges to fill 2048 waves and pays per finished node
+  if (variant == 0) variant = (E >= 131072 && E >= 2 * N) ? 2 : 1;
+  if (variant == 2) {
+    if (E < 16) return YOLAT_E_UNSUPPORTED;
+    return yl_edge_chain_bf16(UV, ld_uv, src, dst, attr, row_ptr, N, E, Wc4, s1, W2f, t2f, root, ld_r, f_out, ld_fo, st, gate);
+  }
+  const long npt = yl_edge_tile_npt(N, E);
+  hipLaunchKernelGGL((npt <= 16 ? k_edge_uv_mlp2_mean_h<1> : k_edge_uv_mlp2_mean_h<4>), dim3(yl_cdiv(N, npt)), dim3(256), 0,
+                     st, UV, (unsigned)ld_uv, src, dst, attr, row_ptr, (int)N, (int)npt, Wc4, s1, W2f, (const float*)nullptr,
+                     (const float*)nullptr, t2f, root, (unsigned)ld_r, f_out, (unsigned)ld_fo, (int)(E > 0 ? E : 1), gate);
+  YL_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int yolat_edge_uv_mlp2_mean_eval_bf16(const uint16_t* UV, int64_t ld_uv, const int32_t* src_csr,
+                                                 const int32_t* dst_csr, const float* attr_csr, const int32_t* row_ptr,
+                                                 int64_t N, int64_t E, const float* Wc4, const float* s1,
+                                                 const uint16_t* W2f, const float* t2f, const float* root, int64_t ld_r,
+                                                 uint16_t* f_out, int64_t ld_fo, int variant, yolat_stream_t stream) {
+  if (!UV || !row_ptr || !Wc4 || !W2f || !t2f || !root || !f_out || N <= 0 || E < 0 || variant < 0 || variant > 2)
+    return YOLAT_E_INVALID;
+  if (E > 0 && (!src_csr || !dst_csr || !attr_csr)) return YOLAT_E_INVALID;
+  if (N > (1LL << 23) || E > (1LL << 29)) return YOLAT_E_UNSUPPORTED;          // 32-bit element offsets in the gathers
+  if (ld_uv < 128 || ld_uv % 8 != 0 || ld_r < 64 || ld_r % 4 != 0 || ld_fo < 64 || ld_fo % 4 != 0 || !yl_aligned16(UV) ||
+      !yl_aligned16(root) || !yl_aligned16(attr_csr) || !yl_aligned16(Wc4) || (((uintptr_t)f_out) & 7) != 0 ||
+      (((uintptr_t)W2f) & 7) != 0)
+    return YOLAT_E_UNSUPPORTED;
+  return yl_edge_uv_mlp2_mean_bf16_impl(UV, ld_uv, src_csr, dst_csr, attr_csr, row_ptr, N, E, Wc4, s1, W2f, t2f, root, ld_r,
+                                        f_out, ld_fo, variant, (hipStream_t)stream);
+}
+

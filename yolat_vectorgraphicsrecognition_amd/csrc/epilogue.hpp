@@ -96,6 +96,29 @@ __device__ __forceinline__ bool yl_stage_ok(const Epilogue& ep, int row_base, in
   if (ep.Yh != nullptr) return ep.ldy % 8 == 0 && (((uintptr_t)ep.Yh) & 15) == 0;
   return ep.ldy % 4 == 0 && (((uintptr_t)ep.Y) & 15) == 0;
 }
+// the staged sub-tile out of the wave's region as 16-byte row pieces: bf16 (two stores per lane) / fp32 (four)
+__device__ __forceinline__ void yl_stage_store_bf16(const float* stage, const Epilogue& ep, int row_base, int col_base,
+                                                    int lane) {
+#pragma unroll
+  for (int t = 0; t < 2; ++t) {
+    const int chunk = lane + 64 * t, R = chunk >> 2, c = (chunk & 3) * 8;
+    const float4 x0 = *reinterpret_cast<const float4*>(stage + R * YL_STAGE_LD + c);
+    const float4 x1 = *reinterpret_cast<const float4*>(stage + R * YL_STAGE_LD + c + 4);
+    uint4 o;
+    o.x = yl_pack_bf16(x0.x, x0.y); o.y = yl_pack_bf16(x0.z, x0.w);
+    o.z = yl_pack_bf16(x1.x, x1.y); o.w = yl_pack_bf16(x1.z, x1.w);
+    *reinterpret_cast<uint4*>(ep.Yh + (long)(row_base + R) * ep.ldy + col_base + c) = o;
+  }
+}
+__device__ __forceinline__ void yl_stage_store_f32(const float* stage, const Epilogue& ep, int row_base, int col_base,
+                                                   int lane) {
+#pragma unroll
+  for (int t = 0; t < 4; ++t) {
+    const int chunk = lane + 64 * t, R = chunk >> 3, c = (chunk & 7) * 4;
+    *reinterpret_cast<float4*>(ep.Y + (long)(row_base + R) * ep.ldy + col_base + c) =
+        *reinterpret_cast<const float4*>(stage + R * YL_STAGE_LD + c);
+  }
+}
 __device__ __forceinline__ void wave_epilogue(f32x16 acc, int row_base, int col, int lhi,
                                               const Epilogue& ep, int M, int N, const EpiPre& pre,
                                               float* stage = nullptr) {
@@ -170,16 +193,7 @@ __device__ __forceinline__ void wave_epilogue(f32x16 acc, int row_base, int col,
 #pragma unroll
     for (int r = 0; r < 16; ++r)
       stage[((r & 3) + 8 * (r >> 2) + 4 * lhi) * YL_STAGE_LD + l31s] = fmaxf(fmaf(acc[r], sc, sh), floor);
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-      const int chunk = lane + 64 * t, R = chunk >> 2, c = (chunk & 3) * 8;
-      const float4 x0 = *reinterpret_cast<const float4*>(stage + R * YL_STAGE_LD + c);
-      const float4 x1 = *reinterpret_cast<const float4*>(stage + R * YL_STAGE_LD + c + 4);
-      uint4 o;
-      o.x = yl_pack_bf16(x0.x, x0.y); o.y = yl_pack_bf16(x0.z, x0.w);
-      o.z = yl_pack_bf16(x1.x, x1.y); o.w = yl_pack_bf16(x1.z, x1.w);
-      *reinterpret_cast<uint4*>(ep.Yh + (long)(row_base + R) * ep.ldy + col_base + c) = o;
-    }
+    yl_stage_store_bf16(stage, ep, row_base, col_base, lane);
     return;
   }
   if (ep.Yh != nullptr) {
@@ -257,12 +271,7 @@ __device__ __forceinline__ void wave_epilogue(f32x16 acc, int row_base, int col,
 #pragma unroll
     for (int r = 0; r < 16; ++r)
       stage[((r & 3) + 8 * (r >> 2) + 4 * lhi) * YL_STAGE_LD + l31s] = fmaxf(fmaf(acc[r], sc, sh), floor) + old[r];
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      const int chunk = lane + 64 * t, R = chunk >> 3, c = (chunk & 7) * 4;
-      *reinterpret_cast<float4*>(ep.Y + (long)(row_base + R) * ep.ldy + col_base + c) =
-          *reinterpret_cast<const float4*>(stage + R * YL_STAGE_LD + c);
-    }
+    yl_stage_store_f32(stage, ep, row_base, col_base, lane);
     return;
   }
 #pragma unroll

@@ -6,6 +6,7 @@
 #include "base.hpp"
 
 struct NodeUv;        // gemm_nt.hpp: operands / epilogues of the node side of a factorised conv layer
+struct Epilogue; struct HOp;      // epilogue.hpp; hgemm.hpp: bf16 rows as an operand of the tile GEMM
 
 // fills the node side of a factorised conv layer (dense.hip)
 int yl_build_node_uv(NodeUv* a, const float* f_in, int64_t ld_f, const float* s_in, int64_t ld_s, int64_t N,
@@ -157,11 +158,15 @@ int yl_graph_prepare_impl(const int64_t* edge, int64_t stride_e, int64_t stride_
                           int32_t* work, int32_t* status, const NodeUv* extra, bool primed, yolat_stream_t stream,
                           int regime = YL_REGIME_LATENCY);
 
-// register-chained MFMA edge stage of the bf16 forward on folded weights (edge_chain.hip)
-int yl_edge_chain_bf16(const uint16_t* UV, int64_t ld_uv, const int32_t* src_csr, const int32_t* dst_csr,
-                       const float* attr_csr, const int32_t* row_ptr, int64_t N, int64_t E, const float* Wc4,
-                       const float* s1, const uint16_t* W2f, const float* t2f, const float* root, int64_t ld_r,
-                       uint16_t* f_out, int64_t ld_fo, hipStream_t st, YlGate gate);
+// edge stage of the bf16 forward on folded weights (edge_chain.hip): variant 0 = automatic, 1 = node tiles, 2 = chained waves
+int yl_edge_uv_mlp2_mean_bf16_impl(const uint16_t* UV, long ld_uv, const int* src, const int* dst, const float* attr,
+                                   const int* row_ptr, long N, long E, const float* Wc4, const float* s1,
+                                   const uint16_t* W2f, const float* t2f, const float* root, long ld_r, uint16_t* f_out,
+                                   long ld_fo, int variant, hipStream_t st, YlGate gate = YlGate{nullptr, 0});
+// the bf16 tile GEMM (hgemm.hpp) for a caller in another file: bf16_eval.hip holds every k_hgemm instance.  a_scale given:
+// A's rows pass the producer's BatchNorm (a_scale, a_shift) and the floor while staging (HProOp)
+int yl_launch_hgemm(const HOp& A, const float* a_scale, const float* a_shift, float a_floor, const HOp& B, const Epilogue& ep,
+                    long M, long N, long K, hipStream_t st);
 // can the one-launch conv stack run this model at all (conv_local.hip)
 bool yl_conv_local_model_ok(const yolat_model_eval_bf16* mh);
 // the one-launch conv stack; *flag = flag_val when the batch turns out not to be proposal-local (conv_local.hip)
