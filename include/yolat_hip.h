@@ -1316,7 +1316,7 @@ int yolat_fusion_pair_eval_x6(const float* A, int64_t lda, int64_t N, int64_t D,
                               int64_t ldpool, const float* S, int64_t lds, int64_t P, const uint16_t* Wsh,
                               const uint16_t* Wsm, const uint16_t* Wsl, const float* tsfold, float* Ys, int64_t ldys,
                               yolat_stream_t stream);
-/* The same pair launch with the GEMM emulated by THREE half-precision products (fusion_x6.hip k_fusion_rows_f16x3,
+/* The same pair launch with the GEMM emulated by THREE half-precision products (fusion_f16x3.hip k_fusion_rows_f16x3,
  * csrc/f16x3.hpp): every row of either operand is scaled by a power of two so that its largest magnitude lies in
  * [2^14, 2^15), split into two fp16 terms by round to nearest (residual <= 2^-23 relative for elements within 2^16 of
  * their row's maximum; further down the error is relative to the ROW's maximum), three v_mfma_f32_32x32x16_f16 products

@@ -1,4 +1,4 @@
-"""CPU test (-m "not gpu") of the footprint of the f16x3 eval fusion kernel (csrc/fusion_x6.hip k_fusion_rows_f16x3).
+"""CPU test (-m "not gpu") of the footprint of the f16x3 eval fusion kernel (csrc/fusion_f16x3.hip k_fusion_rows_f16x3).
 
 Half the matrix work is one half of the claim; the other is what the launch holds on a CU while it runs (DESIGN.md 6 "The
 loaded regime": the fusion launch is the largest reservation of a forward).  Against k_fusion_rows_x6<128, true>, the
@@ -21,7 +21,8 @@ from kernel_meta import CSRC, find_hipcc, kernel_resources, one
 def resources():
     if find_hipcc() is None:
         pytest.skip("hipcc is not on this machine")
-    return kernel_resources(os.path.join(CSRC, "fusion_x6.hip"))
+    # (the x6 siblings are fusion_x6.hip's)
+    return {**kernel_resources(os.path.join(CSRC, "fusion_f16x3.hip")), **kernel_resources(os.path.join(CSRC, "fusion_x6.hip"))}
 
 
 def _inst(kernel, kd, rider, act):

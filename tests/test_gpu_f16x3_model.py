@@ -1,5 +1,5 @@
 """GPU tests, forward level: the eval plan with its fusion launch on three half-precision products (YOLAT_FUSION_F16X3, default
-on; csrc/fusion_x6.hip k_fusion_rows_f16x3) — a small model of cfg 2's shape (two conv layers, fusion 128 -> 1024).
+on; csrc/fusion_f16x3.hip k_fusion_rows_f16x3) — a small model of cfg 2's shape (two conv layers, fusion 128 -> 1024).
 
   * logits with the switch on against the fp32 CPU oracle at RTOL_FWD = 1e-4 of the largest reference logit (the bar of
     tests/test_gpu_model.py), ReLU and leaky;

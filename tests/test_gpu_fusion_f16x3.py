@@ -1,4 +1,4 @@
-"""GPU tests, op level: the eval fusion pair with the GEMM emulated by three half-precision products (csrc/fusion_x6.hip
+"""GPU tests, op level: the eval fusion pair with the GEMM emulated by three half-precision products (csrc/fusion_f16x3.hip
 k_fusion_rows_f16x3, csrc/f16x3.hpp) against float64 and against the bf16x6 entry point on the same operands.
 
   yolat_split_f16x2                  the scaled two-term split alone: exponents, residual, zero / denormal rows

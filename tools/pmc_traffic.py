@@ -26,7 +26,7 @@ GEMM_NT = ("base", "operands", "epilogue", "gemm_nt")
 #   side (EdgeNext: smaller grids)
 STAGES = {
     # (the f16x3 form is the forward's default; YOLAT_FUSION_F16X3=0 / YOLAT_STRICT_FP32=1 runs launch the x6 form)
-    "fusion_gemm+segmax[N x 128 -> 1024 -> P] | super[P x 128 -> 1024]": (("k_fusion_rows_f16x3<128", "k_fusion_rows_x6<128"), srcs("fusion_x6.hip", "base", "x6", "f16x3", "segmax", "operands", "internal"), "all"),
+    "fusion_gemm+segmax[N x 128 -> 1024 -> P] | super[P x 128 -> 1024]": (("k_fusion_rows_f16x3<128", "k_fusion_rows_x6<128"), srcs("fusion_f16x3.hip", "base", "x6", "f16x3", "fx_rows", "segmax", "operands", "internal") + [CS + "fusion_x6.hip", CS + "fx_wg_map.inc", CS + "fx_w_movers.inc"], "all"),
     "edge_uv_mlp2_mean[E x (U+V+attr) -> 64 -> 64 -> mean]": ("k_edge_uv_mlp2_mean", srcs("edge.hip", *GEMM_NT, "gemm_nt_two", "internal"), "last_layer"),
     "edge_uv_mlp2_mean+node_uv_next[E x (U+V+attr) -> 64 -> 64 -> mean; N x 64 -> 128+64+64]": ("k_edge_uv_mlp2_mean", srcs("edge.hip", *GEMM_NT, "gemm_nt_two", "internal"), "with_next"),
     "node_uv[UV | lin_r | mlp_node, N x 64 -> 128+64+64]": ("k_gemm_nt_node3", srcs("dense.hip", *GEMM_NT, "gemm_nt_two", "gemm_sk", "gemm_tn", "internal"), "all"),

@@ -1,4 +1,4 @@
-// f16x3.hpp — shared pieces of the f16x3-emulated fp32 GEMM (fusion_x6.hip k_fusion_rows_f16x3): a round-to-nearest split
+// f16x3.hpp — shared pieces of the f16x3-emulated fp32 GEMM (fusion_f16x3.hip k_fusion_rows_f16x3): a round-to-nearest split
 // of SCALED fp32 values into two half-precision terms, the sibling of x6.hpp's three-way bfloat16 split.
 //
 // A half-precision term holds 11 significand bits, so two terms (plus the sign of the second) cover fp32's 24 where three

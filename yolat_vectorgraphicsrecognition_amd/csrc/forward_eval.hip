@@ -401,7 +401,7 @@ static int forward_eval_impl(const yolat_model_eval* m, const float* x, int64_t 
   static const bool riders_on = []() { const char* v = getenv("YOLAT_POOL_RIDERS"); return !(v && v[0] == '0'); }();
   const bool fusion_x6 = m->Wf_hi && m->Wf_mid && m->Wf_lo && m->tf_fold && m->Wfs_hi && m->Wfs_mid && m->Wfs_lo &&
                          m->tfs_fold && (D == 64 || D == 128) && F % 64 == 0 && (long)P * ZW < (1LL << 32);
-  // the BatchNorm fusion launch (ReLU or leaky) on three half-precision products instead of six bfloat16 ones (fusion_x6.hip
+  // the BatchNorm fusion launch (ReLU or leaky) on three half-precision products instead of six bfloat16 ones (fusion_f16x3.hip
   // k_fusion_rows_f16x3): same grid, same rider, same epilogues, half the MFMAs.  YOLAT_FUSION_F16X3=0: the bf16x6 launch —
   // the forward of a descriptor without the f16 fields, launch for launch.  Read per forward (a getenv, no HIP call), so one
   // process can run both forms; both launch regimes take the same kernel.

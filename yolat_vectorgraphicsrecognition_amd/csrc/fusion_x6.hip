@@ -18,21 +18,18 @@
 // bf16_eval.hip's rows kernel (values >= 0: int order == float order, exact, order-independent).
 // fusion_block_super (P rows, its own weights, plain relu store) is a second problem of the same launch.
 // The EVAL pair launch also exists with three half-precision products per 16 k instead of six bfloat16 ones
-// (k_fusion_rows_f16x3 below, f16x3.hpp) — the eval forward's default; the training, node-side and Linear uses of the rows
-// kernel stay on k_fusion_rows_x6.
+// (fusion_f16x3.hip k_fusion_rows_f16x3) — the eval forward's default; the training, node-side and Linear uses of the rows
+// kernel stay on k_fusion_rows_x6.  Both kernels' workgroup shape and the launcher that picks an instantiation are
+// fx_rows.hpp; the grid planner (fx_plan) and the pair launch's set-up (yl_fx_pair_setup) are here.
 #include "x6.hpp"
-#include "f16x3.hpp"
+#include "fx_rows.hpp"
 #ifdef YOLAT_FX_STAMPS
 extern __device__ long long fx_stamps_d[4096 * 32];
 #define FX_EPI_STAMP(k) do { if (threadIdx.x == 0 && blockIdx.x < 4096) fx_stamps_d[blockIdx.x * 32 + 25 + (k)] = wall_clock64(); } while (0)
 #endif
 #include "segmax.hpp"
 #include "operands.hpp"
-#include "internal.hpp"
-#include <algorithm>
 #include <map>
-#include <queue>
-#include <vector>
 
 #ifdef YOLAT_FX_STAMPS
 // debug build only (tools/exp/r06_fx_stamps.sh): wall-clock stamps (100 MHz) of thread 0 of every workgroup of the K = 128
@@ -60,41 +57,31 @@ extern "C" int yolat_debug_fx_stamps(long long* out, int n) {
 
 // One GEMM problem of the launch: rows of A against the pre-split weights [F, KD]; seg != NULL -> pooling epilogue into
 // `out` (pool); else plain store of act(.) — column tiles [0, ct2) into out [rows, ldo], column tiles [ct2, ...) into
-// out2 [rows, ldo2] (its column 0 = column 64 * ct2 of the product), act = ReLU when relu != 0.
+// out2 [rows, ldo2] (its column 0 = column 64 * ct2 of the product), act = ReLU when relu != 0.  The defaults are a plain
+// problem's: a launch site sets what differs.  (Field order and types are the kernel argument layout.)
 struct FxProb {
   const float* A; long lda; int N;
   const yl_bf16_t *Wh, *Wm, *Wl;
   const float* tfold;
   const int* seg;
   float* out; long ldo;
-  float* out2; long ldo2; int ct2;
+  float* out2 = nullptr; long ldo2 = 0; int ct2 = 1 << 30;
   int F, relu;
   int tm, groups, ng;
   int full = 0;          // the first `full` row tiles (a multiple of 8) are walked WHOLE by one workgroup each (fx_plan)
   // training-mode pooling (fusion_train.hip): key64 != NULL (with seg) -> for every (proposal, column) the row with the
   // largest s*z (s = sign of sgn[column], z = the accumulator) is recorded by a 64-bit atomicMax on
   // orderable(s*z) << 32 | ~row (ties -> lowest row); nothing else is written
-  unsigned long long* key64; const float* sgn;
+  unsigned long long* key64 = nullptr; const float* sgn = nullptr;
   // training-mode Linear (yolat_linear_fwd_rows_x6): optional prologue on A, v = max(a * a_scale[k] + a_shift[k],
   // a_floor) (BatchNorm + ReLU of the producer), and optional BatchNorm partial statistics of the stored values:
   // stats[(row / 32) * F + col] = (sum, M2) of the 32-row group (the layout yolat_bn_finalize reads)
-  const float *a_scale, *a_shift; float a_floor;
-  float* stats;
+  const float *a_scale = nullptr, *a_shift = nullptr; float a_floor = 0.f;
+  float* stats = nullptr;
 };
 
 // RIDER = false: the rider argument is never read (an instantiation that reads it keeps more kernel arguments live:
 // 75 -> 121 spilled SGPRs, and the cfg-5 fusion launch went 332 -> 365 us until the two were separated)
-// Threads per workgroup (32 rows per wave).  K = 128 (fusion blocks): 512 threads = 256 rows, one workgroup per CU (248
-// registers, 105 KB of LDS).  K = 64 (node side, training Linear: one to three column tiles per workgroup, store-heavy):
-// 256 threads = 128 rows and 75 KB of LDS, so that TWO workgroups share a CU and one's prologue / stores run under the
-// other's MFMAs.
-template <int KD> struct FxShape { static constexpr int T = KD == 64 ? 256 : 512, ROWS = T / 2; };
-// ACT != 0: the activation-aware instantiation (leaky activations, act.hip) of the eval pair launch — act(y) = y > 0 ? y :
-// a * y per element, signed pooling (segmax.hpp fx_segmax2_off_act) for the problem with seg, act in the plain store of
-// the other.  The slopes (device pointers to one float each, read by every workgroup) are an argument only that
-// instantiation has: FxSlopes<0> is empty, and nothing in the ACT == 0 code reads it.
-template <int ACT> struct FxSlopes {};
-template <> struct FxSlopes<1> { const float* s0; const float* s1; };
 template <int KD, bool RIDER = false, int ACT = 0>
 __global__ void __launch_bounds__(FxShape<KD>::T, 2) k_fusion_rows_x6(FxProb p0, FxProb p1, PoolRider rider,
                                                                       FxSlopes<ACT> slopes) {
@@ -111,38 +98,9 @@ __global__ void __launch_bounds__(FxShape<KD>::T, 2) k_fusion_rows_x6(FxProb p0,
   // sits at 248 registers and spilled with it
   __shared__ __attribute__((aligned(16))) float st_s[KD == 64 ? NWAVE * 32 * FX_STG_LD : 4];
   const int tid = threadIdx.x;
-  // the small problem's workgroups come first (padded to a multiple of 8 so that the big problem keeps its
-  // id % 8 = XCD alignment): they start with the first round of workgroups instead of forming a tail
-  const int n1 = p1.tm * p1.groups, n1p = (n1 + 7) & ~7;
-  const int id = blockIdx.x;
-  // workgroups past both problems: pooling-prologue rider (internal.hpp; reads A like the GEMM, writes columns of the
-  // pooled rows that nothing in this launch reads)
-  // the big problem: p0.full whole-row-tile workgroups first, then the remaining row tiles split into column groups
-  const int n0t = (p0.tm - p0.full) * p0.groups, n0 = p0.full + n0t;
-  if constexpr (RIDER) {
-    if (id >= n1p + n0) {
-      yl_pool_rider(rider, id - (n1p + n0), rider.blocks, tid, T);
-      return;
-    }
-  }
-  int logical;
-  bool whole = false;
-  if (id < n1p) {
-    if (id >= n1) return;
-    logical = id;
-  } else if (id - n1p < p0.full) {
-    logical = id - n1p;
-    whole = true;
-  } else {
-    // (row tile, column group) pairs, column group fastest, dealt to the XCDs in contiguous ranges
-    const int j0 = id - n1p - p0.full;
-    const int chunk = n0t >> 3, rem = n0t & 7;
-    const int xcd = j0 & 7, slot = j0 >> 3;
-    logical = xcd * chunk + (xcd < rem ? xcd : rem) + slot;
-  }
+#include "fx_wg_map.inc"
   // the problem's fields as wave-uniform scalars (a reference to "p0 or p1" would make the compiler index the
   // kernel arguments through memory)
-  const bool small = id < n1p;
   struct { const float* A; long lda; int N; const float* tfold; const int* seg; float* out; long ldo; float* out2;
            long ldo2; int ct2, relu, groups, ng; unsigned long long* key64; const float* sgn; const float *a_scale,
            *a_shift; float a_floor; float* stats; } P;
@@ -185,27 +143,9 @@ __global__ void __launch_bounds__(FxShape<KD>::T, 2) k_fusion_rows_x6(FxProb p0,
   // workgroup's 23.5 lay between the end of the split and the first MFMA)
   const int sv_pre = (P.seg != nullptr && row0 + l31 < N) ? P.seg[row0 + l31] : -1;
   const yl_bf16_t* const wparts[3] = {small ? p1.Wh : p0.Wh, small ? p1.Wm : p0.Wm, small ? p1.Wl : p0.Wl};
-  // W tile pieces: thread tid moves 16-byte piece (tid + T t) of the [3][64][KD] tile; 64 * CPR is a multiple of
-  // T, so the part (hi / mid / lo) of piece t is a compile-time constant
-  constexpr int PER = 64 * CPR / T;                         // pieces per thread and part
-  static_assert((64 * CPR) % T == 0, "part boundary inside a thread's pieces");
-  const unsigned wr0 = (unsigned)tid / CPR, wk = ((unsigned)tid % CPR) * 8;   // row (of the first piece), k offset
-  auto load_w = [&](int ct, fx_u32x4* rw) {
-#pragma unroll
-    for (int t = 0; t < NW; ++t) {
-      const int part = t / PER;
-      const unsigned r = wr0 + (unsigned)(t % PER) * (T / CPR);
-      rw[t] = *reinterpret_cast<const fx_u32x4*>(wparts[part] + (unsigned)yl_min(ct * 64 + (int)r, F - 1) * KD + wk);
-    }
-  };
-  auto store_w = [&](int buf, const fx_u32x4* rw) {
-#pragma unroll
-    for (int t = 0; t < NW; ++t) {
-      const int part = t / PER;
-      const unsigned r = wr0 + (unsigned)(t % PER) * (T / CPR);
-      *reinterpret_cast<fx_u32x4*>(&Ws[buf][part * 64 * RS + r * RS + wk]) = rw[t];
-    }
-  };
+#define FX_W_CLAMP 1
+#include "fx_w_movers.inc"
+#undef FX_W_CLAMP
   fx_u32x4 rw[NW];
   load_w(ct0, rw);
   // shifts (and, training mode, the sign-bit masks of the key) of the first tile; later tiles: fetched one tile ahead,
@@ -496,7 +436,46 @@ FxPlan fx_plan(int tm, int tn, long n_small, int slots) {
   if (used < 8) ++used;
   return best;
 }
+
+struct FxX6 {
+  using Prob = FxProb;
+  template <int KD, bool RIDER, int ACT>
+  static void launch(unsigned grid, hipStream_t st, const FxProb& p0, const FxProb& p1, const PoolRider& pr, FxSlopes<ACT> sl) {
+    hipLaunchKernelGGL((k_fusion_rows_x6<KD, RIDER, ACT>), dim3(grid), dim3(FxShape<KD>::T), 0, st, p0, p1, pr, sl);
+  }
+};
 }  // namespace
+
+// What the x6 and the f16x3 pair launch share before the launch: the argument check, the grid and the rider copy.  The
+// weights differ in number and kind, so their NULL and alignment terms arrive evaluated (w_null, w_unaligned).  The two
+// checks differ in ONE term, kept as it was: f16x3 also declines P * ldys >= 2^32 (ys_span32), x6 does not.
+// Grid.  A workgroup costs one prologue (load + split of its rows of A, measured ~ one column tile's time) plus its column
+// tiles; fx_plan splits the node problem, the small problem always gets the finest split (its few row tiles must not become
+// the longest workgroups).
+int yl_fx_pair_setup(const float* A, int64_t lda, int64_t N, int64_t D, const float* tfold, int64_t F, const int32_t* node_seg,
+                     float* pool, int64_t ldpool, const float* S, int64_t lds, int64_t P, const float* tsfold, float* Ys,
+                     int64_t ldys, bool w_null, bool w_unaligned, bool ys_span32, const PoolRider* rider, const float* slope_f,
+                     const float* slope_s, FxPairGrid* g) {
+  if ((slope_f == nullptr) != (slope_s == nullptr)) return YOLAT_E_INVALID;
+  if (N <= 0 || P <= 0 || F <= 0 || !A || w_null || !tfold || !node_seg || !pool || !S || !tsfold || !Ys) return YOLAT_E_INVALID;
+  if (N >= (1LL << 31) - 256 || lda < D || lds < D || ldpool < F || ldys < F) return YOLAT_E_INVALID;
+  if ((D != 64 && D != 128) || F % 64 != 0 || lda % 4 != 0 || lds % 4 != 0 || !yl_aligned16(A) || !yl_aligned16(S) ||
+      w_unaligned || (int64_t)P * ldpool >= (1LL << 32) || (ys_span32 && (int64_t)P * ldys >= (1LL << 32)))
+    return YOLAT_E_UNSUPPORTED;
+  const int rows_wg = D == 64 ? FxShape<64>::ROWS : FxShape<128>::ROWS, wg_round = D == 64 ? 512 : 256;
+  g->tn = (int)(F / 64);
+  g->tm0 = yl_cdiv(N, rows_wg);
+  g->tm1 = yl_cdiv(P, rows_wg);
+  const long n1 = (((long)g->tm1 * g->tn + 7) & ~7L);
+  const FxPlan plan = fx_plan(g->tm0, g->tn, n1, wg_round);
+  g->full = plan.full; g->groups = plan.groups; g->ng = plan.ng;
+  g->rider = PoolRider{};
+  if (rider && rider->blocks > 0) g->rider = *rider;
+  const long total = (long)g->full + (long)(g->tm0 - g->full) * g->groups + n1 + g->rider.blocks;
+  if (total >= (1LL << 31)) return YOLAT_E_UNSUPPORTED;
+  g->total = (unsigned)total;
+  return 0;
+}
 
 // pool[p, 0:F] = max over the rows of proposal p of relu(A . (sf (.) Wf)^T + tfold),  Ys = relu(S . (sfs (.) Wfs)^T
 // + tsfold): both fusion blocks with pre-split weights (yolat_split_bf16x3 of the scaled rows) and folded shifts
@@ -507,58 +486,22 @@ int yl_fusion_pair_eval_x6_impl(const float* A, int64_t lda, int64_t N, int64_t 
                                 const uint16_t* Wsm, const uint16_t* Wsl, const float* tsfold, float* Ys, int64_t ldys,
                                 const PoolRider* rider, yolat_stream_t stream, const float* slope_f,
                                 const float* slope_s) {
-  if ((slope_f == nullptr) != (slope_s == nullptr)) return YOLAT_E_INVALID;
-  if (N <= 0 || P <= 0 || F <= 0 || !A || !Wh || !Wm || !Wl || !tfold || !node_seg || !pool || !S || !Wsh || !Wsm || !Wsl ||
-      !tsfold || !Ys)
-    return YOLAT_E_INVALID;
-  if (N >= (1LL << 31) - 256 || lda < D || lds < D || ldpool < F || ldys < F) return YOLAT_E_INVALID;
-  if ((D != 64 && D != 128) || F % 64 != 0 || lda % 4 != 0 || lds % 4 != 0 || !yl_aligned16(A) || !yl_aligned16(S) ||
-      !yl_aligned16(Wh) || !yl_aligned16(Wm) || !yl_aligned16(Wl) || !yl_aligned16(Wsh) || !yl_aligned16(Wsm) ||
-      !yl_aligned16(Wsl) || (int64_t)P * ldpool >= (1LL << 32))
-    return YOLAT_E_UNSUPPORTED;
-  const int tn = (int)(F / 64);
-  // Column groups.  One workgroup per CU is resident (8 waves x ~240 VGPRs), so the launch runs in rounds of 256
-  // workgroups; a workgroup costs one prologue (load + split of its 256 rows of A, measured ~ one column tile's time)
-  // plus its column tiles.  Pick the power-of-two split with the fewest (rounds x workgroup cost); the small problem
-  // always gets the finest split (its few row tiles must not become the longest workgroups).
+  FxPairGrid g;
+  YL_TRY(yl_fx_pair_setup(A, lda, N, D, tfold, F, node_seg, pool, ldpool, S, lds, P, tsfold, Ys, ldys,
+                          !Wh || !Wm || !Wl || !Wsh || !Wsm || !Wsl,
+                          !yl_aligned16(Wh) || !yl_aligned16(Wm) || !yl_aligned16(Wl) || !yl_aligned16(Wsh) ||
+                              !yl_aligned16(Wsm) || !yl_aligned16(Wsl),
+                          /*ys_span32=*/false, rider, slope_f, slope_s, &g));
+  // (leaky activation: `pool` holds -inf / 0 per proposal, yolat_pool_init_signed, not zeros)
+  const int relu = slope_f == nullptr;
   FxProb p0, p1;
   p0.A = A; p0.lda = lda; p0.N = (int)N; p0.Wh = Wh; p0.Wm = Wm; p0.Wl = Wl; p0.tfold = tfold; p0.seg = node_seg;
-  p0.out = pool; p0.ldo = ldpool; p0.out2 = nullptr; p0.ldo2 = 0; p0.ct2 = 1 << 30; p0.F = (int)F; p0.relu = 1; p0.key64 = nullptr; p0.sgn = nullptr; p0.a_scale = nullptr; p0.a_shift = nullptr; p0.a_floor = 0.f; p0.stats = nullptr;
+  p0.out = pool; p0.ldo = ldpool; p0.F = (int)F; p0.relu = relu;
+  p0.tm = g.tm0; p0.full = g.full; p0.groups = g.groups; p0.ng = g.ng;
   p1.A = S; p1.lda = lds; p1.N = (int)P; p1.Wh = Wsh; p1.Wm = Wsm; p1.Wl = Wsl; p1.tfold = tsfold; p1.seg = nullptr;
-  p1.out = Ys; p1.ldo = ldys; p1.out2 = nullptr; p1.ldo2 = 0; p1.ct2 = 1 << 30; p1.F = (int)F; p1.relu = 1; p1.key64 = nullptr; p1.sgn = nullptr; p1.a_scale = nullptr; p1.a_shift = nullptr; p1.a_floor = 0.f; p1.stats = nullptr;
-  const int rows_wg = D == 64 ? FxShape<64>::ROWS : FxShape<128>::ROWS, wg_round = D == 64 ? 512 : 256;
-  p0.tm = yl_cdiv(N, rows_wg);
-  p1.tm = yl_cdiv(P, rows_wg);
-  p1.groups = tn; p1.ng = 1;
-  const long n1 = (((long)p1.tm * tn + 7) & ~7L);
-  const FxPlan plan = fx_plan(p0.tm, tn, n1, wg_round);
-  p0.full = plan.full; p0.groups = plan.groups; p0.ng = plan.ng;
-  PoolRider pr{};
-  if (rider && rider->blocks > 0) pr = *rider;
-  const long total = (long)p0.full + (long)(p0.tm - p0.full) * p0.groups + n1 + pr.blocks;
-  if (total >= (1LL << 31)) return YOLAT_E_UNSUPPORTED;
-  hipStream_t st = (hipStream_t)stream;
-  if (slope_f != nullptr) {
-    // leaky activation: `pool` holds -inf / 0 per proposal (yolat_pool_init_signed), not zeros
-    const FxSlopes<1> sl{slope_f, slope_s};
-    p0.relu = 0; p1.relu = 0;
-    if (pr.blocks > 0) {
-      if (D == 128) hipLaunchKernelGGL((k_fusion_rows_x6<128, true, 1>), dim3((unsigned)total), dim3(FxShape<128>::T), 0, st, p0, p1, pr, sl);
-      else hipLaunchKernelGGL((k_fusion_rows_x6<64, true, 1>), dim3((unsigned)total), dim3(FxShape<64>::T), 0, st, p0, p1, pr, sl);
-    } else {
-      if (D == 128) hipLaunchKernelGGL((k_fusion_rows_x6<128, false, 1>), dim3((unsigned)total), dim3(FxShape<128>::T), 0, st, p0, p1, pr, sl);
-      else hipLaunchKernelGGL((k_fusion_rows_x6<64, false, 1>), dim3((unsigned)total), dim3(FxShape<64>::T), 0, st, p0, p1, pr, sl);
-    }
-    YL_LAUNCH_CHECK();
-    return 0;
-  }
-  if (pr.blocks > 0) {
-    if (D == 128) hipLaunchKernelGGL((k_fusion_rows_x6<128, true>), dim3((unsigned)total), dim3(FxShape<128>::T), 0, st, p0, p1, pr, FxSlopes<0>{});
-    else hipLaunchKernelGGL((k_fusion_rows_x6<64, true>), dim3((unsigned)total), dim3(FxShape<64>::T), 0, st, p0, p1, pr, FxSlopes<0>{});
-  } else {
-    if (D == 128) hipLaunchKernelGGL((k_fusion_rows_x6<128>), dim3((unsigned)total), dim3(FxShape<128>::T), 0, st, p0, p1, pr, FxSlopes<0>{});
-    else hipLaunchKernelGGL((k_fusion_rows_x6<64>), dim3((unsigned)total), dim3(FxShape<64>::T), 0, st, p0, p1, pr, FxSlopes<0>{});
-  }
+  p1.out = Ys; p1.ldo = ldys; p1.F = (int)F; p1.relu = relu;
+  p1.tm = g.tm1; p1.groups = g.tn; p1.ng = 1;
+  fx_launch_rows<FxX6>(D, g.total, p0, p1, g.rider, slope_f, slope_s, (hipStream_t)stream);
   YL_LAUNCH_CHECK();
   return 0;
 }
@@ -589,367 +532,6 @@ extern "C" int yolat_fusion_pair_eval_x6_act(const float* A, int64_t lda, int64_
                                      tsfold, Ys, ldys, nullptr, stream, slope_f, slope_s);
 }
 
-// ------------------------------------------------------------------------------------------------------------------
-// The eval pair launch with the GEMM emulated by THREE half-precision products instead of six bfloat16 ones (f16x3.hpp):
-// the same launch — 256 rows per 512-thread workgroup at K = 128 (128 per 256 at K = 64), A split once per wave into
-// registers, W tiles double-buffered in LDS, one barrier per column tile, fx_plan's grid, the XCD mapping, the rider and
-// the fx_segmax2_off / fx_segmax2_off_act epilogues of k_fusion_rows_x6 — with half the matrix work:
-//   * per k step 6 MFMAs (v_mfma_f32_32x32x16_f16, the bf16 form's cycle count) on 4 B fragments, where x6 issues 12 on 6:
-//     48 instead of 96 per wave and column tile at K = 128; one accumulator per column block, small terms first, so the
-//     summation order is fixed;
-//   * the W tile is 2 x 64 columns x K halves = 32 KB (x6: 48 KB): a third less L2 -> LDS traffic and LDS writes, and
-//     69.6 KB of LDS for the two buffers (x6: 104 KB) — at K = 128 exactly the size of the prologue's transposition tiles;
-//   * A's fragments are 2 x K/16 x 4 = 64 registers at K = 128 (x6: 96).
-// Scaling.  Every row of A is multiplied by 2^s_row before the split (f16x3.hpp; the row maximum is one 64-element max chain
-// per lane and one exchange with the partner lane l31 + 32 that holds the row's other k halves), every row of W — an output
-// column — by 2^s_col in yolat_split_f16x2.  The accumulators start at ZERO and the epilogue un-scales each element with
-// ldexp(acc, -(s_row + s_col)) before it adds the shift: exact, three vector instructions per element (integer add, v_ldexp,
-// add).  The alternative — the shift pre-scaled per (row, column) as the accumulators' start value and one ldexp at the end —
-// costs the same integer add and TWO ldexp per element, so the zero start is the cheaper one.  The 16 row exponents of a
-// lane's accumulator rows live in 16 registers for the whole column walk (one __shfl each, once per workgroup, as the
-// proposal offsets do): the epilogue needs no LDS round trip for them.
-// Problems are described by FhProb — only what the eval pair needs; FxProb and the x6 instantiations are untouched.
-struct FhProb {
-  const float* A; long lda; int N;
-  const _Float16 *Wh, *Wl;      // yolat_split_f16x2 of the (scaled) weights [F, KD]
-  const int* wexp;              // its scale exponent per weight row
-  const float* tfold;
-  const int* seg;               // != NULL: pooling epilogue into `out`; NULL: plain store of act(.) into out [N, ldo]
-  float* out; long ldo;
-  int F;
-  int tm, groups, ng;
-  int full = 0;
-};
-template <int KD, bool RIDER = false, int ACT = 0>
-__global__ void __launch_bounds__(FxShape<KD>::T, 2) k_fusion_rows_f16x3(FhProb p0, FhProb p1, PoolRider rider,
-                                                                         FxSlopes<ACT> slopes) {
-  constexpr int T = FxShape<KD>::T, NWAVE = T / 64;
-  constexpr int KS = KD / 16, RS = KD + 8, CPR = KD / 8;    // k steps, LDS row stride (halves), 16-byte chunks per row
-  constexpr int CHUNKS = 2 * 64 * CPR, NW = CHUNKS / T;     // 16-byte chunks of one W tile, per thread
-  static_assert(CHUNKS % T == 0, "W tile / thread mismatch");
-  constexpr int TK = 64, TS = TK + 4;                       // the prologue's transposition tile: [32 rows][TK + 4] floats per wave
-  constexpr int SMEM_W = 2 * 2 * 64 * RS * 2, SMEM_T = NWAVE * 32 * TS * 4;
-  __shared__ __attribute__((aligned(16))) char smem[SMEM_W > SMEM_T ? SMEM_W : SMEM_T];
-  _Float16 (*Ws)[2 * 64 * RS] = reinterpret_cast<_Float16 (*)[2 * 64 * RS]>(smem);
-  const int tid = threadIdx.x;
-  // workgroup -> (problem, row tile, column group): k_fusion_rows_x6's mapping
-  const int n1 = p1.tm * p1.groups, n1p = (n1 + 7) & ~7;
-  const int id = blockIdx.x;
-  const int n0t = (p0.tm - p0.full) * p0.groups, n0 = p0.full + n0t;
-  if constexpr (RIDER) {
-    if (id >= n1p + n0) {
-      yl_pool_rider(rider, id - (n1p + n0), rider.blocks, tid, T);
-      return;
-    }
-  }
-  int logical;
-  bool whole = false;
-  if (id < n1p) {
-    if (id >= n1) return;
-    logical = id;
-  } else if (id - n1p < p0.full) {
-    logical = id - n1p;
-    whole = true;
-  } else {
-    const int j0 = id - n1p - p0.full;
-    const int chunk = n0t >> 3, rem = n0t & 7;
-    const int xcd = j0 & 7, slot = j0 >> 3;
-    logical = xcd * chunk + (xcd < rem ? xcd : rem) + slot;
-  }
-  const bool small = id < n1p;
-  const float* __restrict__ A = small ? p1.A : p0.A;
-  const long lda = small ? p1.lda : p0.lda;
-  const int N = small ? p1.N : p0.N;
-  const float* const tfold = small ? p1.tfold : p0.tfold;
-  const int* const wexp = small ? p1.wexp : p0.wexp;
-  const int* const seg = small ? p1.seg : p0.seg;
-  float* const out = small ? p1.out : p0.out;
-  const long ldo = small ? p1.ldo : p0.ldo;
-  const int F = small ? p1.F : p0.F;
-  const int groups = small ? p1.groups : p0.groups, ng = small ? p1.ng : p0.ng;
-  const int tn = (F + 63) >> 6;
-  float slope = 0.f;
-  if constexpr (ACT != 0) slope = *(small ? slopes.s1 : slopes.s0);
-  const int rt = whole ? logical : (small ? 0 : p0.full) + logical / groups;
-  const int cg = whole ? 0 : logical % groups;
-  const int ct0 = cg * ng;
-  const int ngl = whole ? tn : yl_min(ng, tn - ct0);
-  if (ngl <= 0) return;
-
-  const int wave = tid >> 6, lane = tid & 63, l31 = lane & 31, lhi = lane >> 5;
-  const int row0 = rt * (T / 2) + wave * 32;
-  // everything the tile loop needs besides A goes out first: its latency runs under the A prologue
-  const int sv_pre = (seg != nullptr && row0 + l31 < N) ? seg[row0 + l31] : -1;
-  const _Float16* const wparts[2] = {small ? p1.Wh : p0.Wh, small ? p1.Wl : p0.Wl};
-  // W tile pieces: thread tid moves 16-byte piece (tid + T t) of the [2][64][KD] tile; the part (hi / lo) of piece t is a
-  // compile-time constant
-  constexpr int PER = 64 * CPR / T;                         // pieces per thread and part
-  static_assert((64 * CPR) % T == 0, "part boundary inside a thread's pieces");
-  const unsigned wr0 = (unsigned)tid / CPR, wk = ((unsigned)tid % CPR) * 8;   // row (of the first piece), k offset
-  auto load_w = [&](int ct, fx_u32x4* rw) {
-#pragma unroll
-    for (int t = 0; t < NW; ++t) {
-      const int part = t / PER;
-      const unsigned r = wr0 + (unsigned)(t % PER) * (T / CPR);
-      rw[t] = *reinterpret_cast<const fx_u32x4*>(wparts[part] + (unsigned)yl_min(ct * 64 + (int)r, F - 1) * KD + wk);
-    }
-  };
-  auto store_w = [&](int buf, const fx_u32x4* rw) {
-#pragma unroll
-    for (int t = 0; t < NW; ++t) {
-      const int part = t / PER;
-      const unsigned r = wr0 + (unsigned)(t % PER) * (T / CPR);
-      *reinterpret_cast<fx_u32x4*>(&Ws[buf][part * 64 * RS + r * RS + wk]) = rw[t];
-    }
-  };
-  fx_u32x4 rw[NW];
-  load_w(ct0, rw);
-  // shifts and column exponents of the first tile; later tiles: fetched one tile ahead, before that tile's W loads
-  float t0 = tfold[yl_min(ct0 * 64 + l31, F - 1)], t1 = tfold[yl_min(ct0 * 64 + 32 + l31, F - 1)];
-  int e0 = wexp[yl_min(ct0 * 64 + l31, F - 1)], e1 = wexp[yl_min(ct0 * 64 + 32 + l31, F - 1)];
-  // ---- this wave's 32 rows of A: loaded row by row and turned into the MFMA operand order (lane = row, 8 consecutive k)
-  // through a [32][TK + 4] fp32 tile in LDS (the weights' buffers, not yet in use), as k_fusion_rows_x6 does — but kept as
-  // fp32 until the row's maximum is known: a lane holds 64 of its row's 128 values (K = 128), its partner the others
-  fh_f16x8 Ah[KS], Al[KS];
-  int nrow;                                                 // -(scale exponent) of row l31 of this wave
-  {
-    float xs[KS][8];
-    float* Tt = reinterpret_cast<float*>(smem) + wave * (32 * TS);
-    const int lr = lane >> 4, lc = (lane & 15) * 4;
-#pragma unroll
-    for (int q = 0; q < KD / TK; ++q) {
-      float4 v[8];
-#pragma unroll
-      for (int i = 0; i < 8; ++i)
-        v[i] = *reinterpret_cast<const float4*>(A + (long)yl_min(row0 + 4 * i + lr, N - 1) * lda + TK * q + lc);
-#pragma unroll
-      for (int i = 0; i < 8; ++i) *reinterpret_cast<float4*>(Tt + (4 * i + lr) * TS + lc) = v[i];
-#pragma unroll
-      for (int u = 0; u < TK / 16; ++u) {
-        const int ks = (TK / 16) * q + u;
-        const float4 a0 = *reinterpret_cast<const float4*>(Tt + l31 * TS + 16 * u + 8 * lhi);
-        const float4 a1 = *reinterpret_cast<const float4*>(Tt + l31 * TS + 16 * u + 8 * lhi + 4);
-        xs[ks][0] = a0.x; xs[ks][1] = a0.y; xs[ks][2] = a0.z; xs[ks][3] = a0.w;
-        xs[ks][4] = a1.x; xs[ks][5] = a1.y; xs[ks][6] = a1.z; xs[ks][7] = a1.w;
-      }
-    }
-    float mx = 0.f;                                         // (fmaxf drops a NaN: the maximum of the row's numbers)
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks)
-#pragma unroll
-      for (int e = 0; e < 8; ++e) mx = fmaxf(mx, fabsf(xs[ks][e]));
-    mx = fmaxf(mx, __shfl_xor(mx, 32));
-    const int s = fh_scale_exp(mx);
-    const float sc = fh_pow2(s);
-    nrow = -s;
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks) {
-      float y[8];
-#pragma unroll
-      for (int e = 0; e < 8; ++e) y[e] = xs[ks][e] * sc;
-      fh_split8(y, Ah[ks], Al[ks]);
-    }
-  }
-  const bool pooling = seg != nullptr;
-  FxRuns runs;
-  unsigned roff[16];                                    // element offset of each of the lane's rows' proposal in the output
-  fx_seg_runs_off(sv_pre, lhi, (unsigned)ldo, runs, roff);
-  int nr[16];                                           // -(scale exponent) of each of the lane's 16 accumulator rows
-#pragma unroll
-  for (int r = 0; r < 16; ++r) nr[r] = __shfl(nrow, (r & 3) + 8 * (r >> 2) + 4 * lhi);
-  __syncthreads();                                          // every wave is done with its transposition tile
-  store_w(0, rw);
-  __syncthreads();
-  for (int j = 0; j < ngl; ++j) {
-    const int ct = ct0 + j, buf = j & 1;
-    const int c0 = ct * 64 + l31, c1 = c0 + 32;
-    f32x16 acc0, acc1;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) { acc0[r] = 0.f; acc1[r] = 0.f; }
-    const float s0 = t0, s1 = t1;
-    const int n0 = -e0, n1c = -e1;
-    if (j + 1 < ngl) {
-      t0 = tfold[yl_min(c0 + 64, F - 1)];
-      t1 = tfold[yl_min(c1 + 64, F - 1)];
-      e0 = wexp[yl_min(c0 + 64, F - 1)];
-      e1 = wexp[yl_min(c1 + 64, F - 1)];
-      load_w(ct + 1, rw);                              // in flight while the MFMAs below run
-    }
-    const _Float16* wb = &Ws[buf][l31 * RS + 8 * lhi];
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks) {
-      fh_f16x8 bf[4];                                  // [0] b0h [1] b1h [2] b0l [3] b1l
-#pragma unroll
-      for (int q = 0; q < 4; ++q) bf[q] = *reinterpret_cast<const fh_f16x8*>(wb + q * 32 * RS + 16 * ks);
-      // small terms first; the empty asm pins the MFMAs' program order (k_fusion_rows_x6)
-#define FH_MFMA(acc, a, b)                                          \
-  acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, acc, 0, 0, 0); \
-  asm volatile("" : "+v"(acc0), "+v"(acc1))
-      FH_MFMA(acc0, Al[ks], bf[0]);
-      FH_MFMA(acc1, Al[ks], bf[1]);
-      FH_MFMA(acc0, Ah[ks], bf[2]);
-      FH_MFMA(acc1, Ah[ks], bf[3]);
-      FH_MFMA(acc0, Ah[ks], bf[0]);
-      FH_MFMA(acc1, Ah[ks], bf[1]);
-#undef FH_MFMA
-    }
-    // next W tile into the other buffer (its readers finished before the last barrier) BEFORE the epilogue, and everything
-    // in flight waited for here, a whole MFMA phase after its issue (k_fusion_rows_x6)
-    if (j + 1 < ngl) store_w(buf ^ 1, rw);
-    __builtin_amdgcn_s_waitcnt(0x0F70);                // vmcnt(0)
-    // un-scale, then the shift: y = acc * 2^-(s_row + s_col) + t
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      acc0[r] = ldexpf(acc0[r], nr[r] + n0) + s0;
-      acc1[r] = ldexpf(acc1[r], nr[r] + n1c) + s1;
-    }
-    if (pooling) {
-      if constexpr (ACT != 0) fx_segmax2_off_act(acc0, acc1, out, roff, (unsigned)c0, c0 < F, c1 < F, runs, slope);
-      else fx_segmax2_off(acc0, acc1, out, roff, (unsigned)c0, c0 < F, c1 < F, runs);
-    } else {
-      // plain store of act(.) (fusion_block_super: P rows): the accumulator layout as it is — a few row tiles per launch
-      unsigned rb = (unsigned)(row0 + 4 * lhi);
-      asm volatile("" : "+v"(rb));
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const unsigned row = rb + (r & 3) + 8 * (r >> 2);
-        if ((int)row < N) {
-          float* o = out + (unsigned long)row * (unsigned long)ldo;
-          if constexpr (ACT != 0) {
-            if (c0 < F) o[c0] = acc0[r] > 0.f ? acc0[r] : slope * acc0[r];
-            if (c1 < F) o[c1] = acc1[r] > 0.f ? acc1[r] : slope * acc1[r];
-          } else {
-            if (c0 < F) o[c0] = fmaxf(acc0[r], 0.f);
-            if (c1 < F) o[c1] = fmaxf(acc1[r], 0.f);
-          }
-        }
-      }
-    }
-    __syncthreads();
-  }
-}
-
-// W [rows, cols] fp32 (optionally scaled per row) -> two half-precision matrices hi / lo [rows, cols] and one scale
-// exponent per row (f16x3.hpp): hi + lo == fl(row_scale * W) * 2^exp[r] to 2^-23 relative for every element within 2^16 of
-// its row's largest magnitude.  One wave per row.
-static __global__ void __launch_bounds__(64) k_split_f16x2(const float* __restrict__ W, long ldw, int cols,
-                                                           const float* __restrict__ row_scale, _Float16* __restrict__ hi,
-                                                           _Float16* __restrict__ lo, int* __restrict__ exps) {
-  const long r = blockIdx.x;
-  const int lane = threadIdx.x;
-  const float rs = row_scale != nullptr ? row_scale[r] : 1.f;
-  float mx = 0.f;
-  for (int c = lane; c < cols; c += 64) mx = fmaxf(mx, fabsf(W[r * ldw + c] * rs));
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) mx = fmaxf(mx, __shfl_xor(mx, d));
-  const int s = fh_scale_exp(mx);
-  const float sc = fh_pow2(s);
-  if (lane == 0) exps[r] = s;
-  for (int c = lane; c < cols; c += 64) {
-    const float x = (W[r * ldw + c] * rs) * sc;
-    const _Float16 h = (_Float16)x;
-    hi[r * cols + c] = h;
-    lo[r * cols + c] = (_Float16)(x - (float)h);
-  }
-}
-
-extern "C" int yolat_split_f16x2(const float* W, int64_t ldw, int64_t rows, int64_t cols, const float* row_scale,
-                                 uint16_t* hi, uint16_t* lo, int32_t* exps, yolat_stream_t stream) {
-  if (rows <= 0 || cols <= 0 || !W || !hi || !lo || !exps || ldw < cols) return YOLAT_E_INVALID;
-  if (rows >= (1LL << 31) || cols >= (1LL << 31)) return YOLAT_E_UNSUPPORTED;
-  hipLaunchKernelGGL(k_split_f16x2, dim3((unsigned)rows), dim3(64), 0, (hipStream_t)stream, W, (long)ldw, (int)cols,
-                     row_scale, reinterpret_cast<_Float16*>(hi), reinterpret_cast<_Float16*>(lo), exps);
-  YL_LAUNCH_CHECK();
-  return 0;
-}
-
-// yl_fusion_pair_eval_x6_impl with the weights as yolat_split_f16x2 gives them (hi, lo, exponents): same contract, same
-// grid, k_fusion_rows_f16x3.
-int yl_fusion_pair_eval_f16x3_impl(const float* A, int64_t lda, int64_t N, int64_t D, const uint16_t* Wh, const uint16_t* Wl,
-                                   const int32_t* Wexp, const float* tfold, int64_t F, const int32_t* node_seg, float* pool,
-                                   int64_t ldpool, const float* S, int64_t lds, int64_t P, const uint16_t* Wsh,
-                                   const uint16_t* Wsl, const int32_t* Wsexp, const float* tsfold, float* Ys, int64_t ldys,
-                                   const PoolRider* rider, yolat_stream_t stream, const float* slope_f,
-                                   const float* slope_s) {
-  if ((slope_f == nullptr) != (slope_s == nullptr)) return YOLAT_E_INVALID;
-  if (N <= 0 || P <= 0 || F <= 0 || !A || !Wh || !Wl || !Wexp || !tfold || !node_seg || !pool || !S || !Wsh || !Wsl ||
-      !Wsexp || !tsfold || !Ys)
-    return YOLAT_E_INVALID;
-  if (N >= (1LL << 31) - 256 || lda < D || lds < D || ldpool < F || ldys < F) return YOLAT_E_INVALID;
-  if ((D != 64 && D != 128) || F % 64 != 0 || lda % 4 != 0 || lds % 4 != 0 || !yl_aligned16(A) || !yl_aligned16(S) ||
-      !yl_aligned16(Wh) || !yl_aligned16(Wl) || !yl_aligned16(Wsh) || !yl_aligned16(Wsl) ||
-      (int64_t)P * ldpool >= (1LL << 32) || (int64_t)P * ldys >= (1LL << 32))
-    return YOLAT_E_UNSUPPORTED;
-  const int tn = (int)(F / 64);
-  FhProb p0, p1;
-  p0.A = A; p0.lda = lda; p0.N = (int)N; p0.Wh = reinterpret_cast<const _Float16*>(Wh);
-  p0.Wl = reinterpret_cast<const _Float16*>(Wl); p0.wexp = Wexp; p0.tfold = tfold; p0.seg = node_seg; p0.out = pool;
-  p0.ldo = ldpool; p0.F = (int)F;
-  p1.A = S; p1.lda = lds; p1.N = (int)P; p1.Wh = reinterpret_cast<const _Float16*>(Wsh);
-  p1.Wl = reinterpret_cast<const _Float16*>(Wsl); p1.wexp = Wsexp; p1.tfold = tsfold; p1.seg = nullptr; p1.out = Ys;
-  p1.ldo = ldys; p1.F = (int)F;
-  const int rows_wg = D == 64 ? FxShape<64>::ROWS : FxShape<128>::ROWS, wg_round = D == 64 ? 512 : 256;
-  p0.tm = yl_cdiv(N, rows_wg);
-  p1.tm = yl_cdiv(P, rows_wg);
-  p1.groups = tn; p1.ng = 1;
-  const long n1 = (((long)p1.tm * tn + 7) & ~7L);
-  const FxPlan plan = fx_plan(p0.tm, tn, n1, wg_round);
-  p0.full = plan.full; p0.groups = plan.groups; p0.ng = plan.ng;
-  PoolRider pr{};
-  if (rider && rider->blocks > 0) pr = *rider;
-  const long total = (long)p0.full + (long)(p0.tm - p0.full) * p0.groups + n1 + pr.blocks;
-  if (total >= (1LL << 31)) return YOLAT_E_UNSUPPORTED;
-  hipStream_t st = (hipStream_t)stream;
-  const dim3 grid((unsigned)total);
-  if (slope_f != nullptr) {
-    // leaky activation: `pool` holds -inf / 0 per proposal (yolat_pool_init_signed), not zeros
-    const FxSlopes<1> sl{slope_f, slope_s};
-    if (pr.blocks > 0) {
-      if (D == 128) hipLaunchKernelGGL((k_fusion_rows_f16x3<128, true, 1>), grid, dim3(FxShape<128>::T), 0, st, p0, p1, pr, sl);
-      else hipLaunchKernelGGL((k_fusion_rows_f16x3<64, true, 1>), grid, dim3(FxShape<64>::T), 0, st, p0, p1, pr, sl);
-    } else {
-      if (D == 128) hipLaunchKernelGGL((k_fusion_rows_f16x3<128, false, 1>), grid, dim3(FxShape<128>::T), 0, st, p0, p1, pr, sl);
-      else hipLaunchKernelGGL((k_fusion_rows_f16x3<64, false, 1>), grid, dim3(FxShape<64>::T), 0, st, p0, p1, pr, sl);
-    }
-    YL_LAUNCH_CHECK();
-    return 0;
-  }
-  if (pr.blocks > 0) {
-    if (D == 128) hipLaunchKernelGGL((k_fusion_rows_f16x3<128, true>), grid, dim3(FxShape<128>::T), 0, st, p0, p1, pr, FxSlopes<0>{});
-    else hipLaunchKernelGGL((k_fusion_rows_f16x3<64, true>), grid, dim3(FxShape<64>::T), 0, st, p0, p1, pr, FxSlopes<0>{});
-  } else {
-    if (D == 128) hipLaunchKernelGGL((k_fusion_rows_f16x3<128>), grid, dim3(FxShape<128>::T), 0, st, p0, p1, pr, FxSlopes<0>{});
-    else hipLaunchKernelGGL((k_fusion_rows_f16x3<64>), grid, dim3(FxShape<64>::T), 0, st, p0, p1, pr, FxSlopes<0>{});
-  }
-  YL_LAUNCH_CHECK();
-  return 0;
-}
-
-extern "C" int yolat_fusion_pair_eval_f16x3(const float* A, int64_t lda, int64_t N, int64_t D, const uint16_t* Wh,
-                                            const uint16_t* Wl, const int32_t* Wexp, const float* tfold, int64_t F,
-                                            const int32_t* node_seg, float* pool, int64_t ldpool, const float* S,
-                                            int64_t lds, int64_t P, const uint16_t* Wsh, const uint16_t* Wsl,
-                                            const int32_t* Wsexp, const float* tsfold, float* Ys, int64_t ldys,
-                                            yolat_stream_t stream) {
-  return yl_fusion_pair_eval_f16x3_impl(A, lda, N, D, Wh, Wl, Wexp, tfold, F, node_seg, pool, ldpool, S, lds, P, Wsh, Wsl,
-                                        Wsexp, tsfold, Ys, ldys, nullptr, stream, nullptr, nullptr);
-}
-
-// the activation-aware form (yolat_fusion_pair_eval_x6_act's contract): signed start values of `pool`, then the ACT
-// instantiation
-extern "C" int yolat_fusion_pair_eval_f16x3_act(const float* A, int64_t lda, int64_t N, int64_t D, const uint16_t* Wh,
-                                                const uint16_t* Wl, const int32_t* Wexp, const float* tfold, int64_t F,
-                                                const float* slope_f, const int32_t* node_seg, const int32_t* seg_ptr,
-                                                float* pool, int64_t ldpool, const float* S, int64_t lds, int64_t P,
-                                                const uint16_t* Wsh, const uint16_t* Wsl, const int32_t* Wsexp,
-                                                const float* tsfold, const float* slope_s, float* Ys, int64_t ldys,
-                                                yolat_stream_t stream) {
-  if (!slope_f || !slope_s || !seg_ptr) return YOLAT_E_INVALID;
-  YL_TRY(yolat_pool_init_signed(seg_ptr, P, F, pool, ldpool, stream));
-  return yl_fusion_pair_eval_f16x3_impl(A, lda, N, D, Wh, Wl, Wexp, tfold, F, node_seg, pool, ldpool, S, lds, P, Wsh, Wsl,
-                                        Wsexp, tsfold, Ys, ldys, nullptr, stream, slope_f, slope_s);
-}
-
 // Training-mode fusion GEMM (fusion_train.hip step 4) on the rows kernel: z = A . W^T + bias never stored, per
 // (proposal, column) extreme-of-z keys.  W [F, K] fp32 is split here (it changes every step) into `wsplit`
 // (3 * F * K bfloat16, 16-byte aligned).  K in {64, 128}, F % 64 == 0; returns YOLAT_E_UNSUPPORTED otherwise.
@@ -966,9 +548,8 @@ int yl_fusion_rows_x6_key64(const float* A, long lda, long N, long K, const floa
   const int tn = (int)(F / 64);
   FxProb p0, p1;
   p0.A = A; p0.lda = lda; p0.N = (int)N; p0.Wh = wh; p0.Wm = wm; p0.Wl = wl; p0.tfold = bias; p0.seg = node_seg;
-  p0.out = nullptr; p0.ldo = F; p0.out2 = nullptr; p0.ldo2 = 0; p0.ct2 = 1 << 30; p0.F = (int)F; p0.relu = 0;
+  p0.out = nullptr; p0.ldo = F; p0.F = (int)F; p0.relu = 0;
   p0.key64 = keys; p0.sgn = sgn;
-  p0.a_scale = nullptr; p0.a_shift = nullptr; p0.a_floor = 0.f; p0.stats = nullptr;
   const int rows_wg = K == 64 ? FxShape<64>::ROWS : FxShape<128>::ROWS, wg_round = K == 64 ? 512 : 256;
   p0.tm = yl_cdiv(N, rows_wg);
   const FxPlan plan = fx_plan(p0.tm, tn, 0, wg_round);
@@ -977,9 +558,7 @@ int yl_fusion_rows_x6_key64(const float* A, long lda, long N, long K, const floa
   p1.tm = 0; p1.groups = 1; p1.ng = 1; p1.full = 0;
   const long total = (long)p0.full + (long)(p0.tm - p0.full) * p0.groups;
   if (total >= (1LL << 31)) return YOLAT_E_UNSUPPORTED;
-  hipStream_t st = (hipStream_t)stream;
-  if (K == 128) hipLaunchKernelGGL(k_fusion_rows_x6<128>, dim3((unsigned)total), dim3(FxShape<128>::T), 0, st, p0, p1, PoolRider{}, FxSlopes<0>{});
-  else hipLaunchKernelGGL(k_fusion_rows_x6<64>, dim3((unsigned)total), dim3(FxShape<64>::T), 0, st, p0, p1, PoolRider{}, FxSlopes<0>{});
+  fx_launch_rows<FxX6>(K, (unsigned)total, p0, p1, PoolRider{}, nullptr, nullptr, (hipStream_t)stream);
   YL_LAUNCH_CHECK();
   return 0;
 }
@@ -1004,17 +583,14 @@ extern "C" int yolat_linear_fwd_rows_x6(const float* A, int64_t lda, int64_t M, 
   const int tn = (int)(Nout / 64);                     // the bias is the accumulators' initial value
   FxProb p0, p1;
   p0.A = A; p0.lda = lda; p0.N = (int)M; p0.Wh = wh; p0.Wm = wm; p0.Wl = wl; p0.tfold = bias; p0.seg = nullptr;
-  p0.out = Y; p0.ldo = ldy; p0.out2 = nullptr; p0.ldo2 = 0; p0.ct2 = 1 << 30; p0.F = (int)Nout; p0.relu = 0;
-  p0.key64 = nullptr; p0.sgn = nullptr;
+  p0.out = Y; p0.ldo = ldy; p0.F = (int)Nout; p0.relu = 0;
   p0.a_scale = a_scale; p0.a_shift = a_shift; p0.a_floor = a_relu ? 0.f : -INFINITY; p0.stats = stats;
   p0.tm = yl_cdiv(M, K == 64 ? FxShape<64>::ROWS : FxShape<128>::ROWS); p0.groups = 1; p0.ng = tn;
   p1 = p0;
   p1.tm = 0; p1.groups = 1; p1.ng = 1;
   const long total = (long)p0.tm;
   if (total >= (1LL << 31)) return YOLAT_E_UNSUPPORTED;
-  hipStream_t st = (hipStream_t)stream;
-  if (K == 128) hipLaunchKernelGGL(k_fusion_rows_x6<128>, dim3((unsigned)total), dim3(FxShape<128>::T), 0, st, p0, p1, PoolRider{}, FxSlopes<0>{});
-  else hipLaunchKernelGGL(k_fusion_rows_x6<64>, dim3((unsigned)total), dim3(FxShape<64>::T), 0, st, p0, p1, PoolRider{}, FxSlopes<0>{});
+  fx_launch_rows<FxX6>(K, (unsigned)total, p0, p1, PoolRider{}, nullptr, nullptr, (hipStream_t)stream);
   YL_LAUNCH_CHECK();
   return 0;
 }
@@ -1039,189 +615,13 @@ extern "C" int yolat_node_uv_eval_x6(const float* f_in, int64_t ld_f, const floa
   FxProb p0, p1;
   p0.A = f_in; p0.lda = ld_f; p0.N = (int)N; p0.Wh = Wfr_h; p0.Wm = Wfr_m; p0.Wl = Wfr_l; p0.tfold = tfr; p0.seg = nullptr;
   p0.out = UV; p0.ldo = ld_uv; p0.out2 = f_out; p0.ldo2 = ld_fo; p0.ct2 = 2; p0.F = 192; p0.relu = 0;
-  p0.key64 = nullptr; p0.sgn = nullptr; p1.key64 = nullptr; p1.sgn = nullptr;
-  p0.a_scale = p0.a_shift = p1.a_scale = p1.a_shift = nullptr; p0.a_floor = p1.a_floor = 0.f; p0.stats = p1.stats = nullptr; p1.a_scale = nullptr; p1.a_shift = nullptr; p1.a_floor = 0.f; p1.stats = nullptr;
   p0.tm = yl_cdiv(N, FxShape<64>::ROWS); p0.groups = 1; p0.ng = 3;
   p1.A = s_in; p1.lda = ld_s; p1.N = (int)N; p1.Wh = Wn_h; p1.Wm = Wn_m; p1.Wl = Wn_l; p1.tfold = tn_fold; p1.seg = nullptr;
-  p1.out = s_out; p1.ldo = ld_so; p1.out2 = nullptr; p1.ldo2 = 0; p1.ct2 = 1 << 30; p1.F = 64; p1.relu = 1;
+  p1.out = s_out; p1.ldo = ld_so; p1.F = 64; p1.relu = 1;
   p1.tm = yl_cdiv(N, FxShape<64>::ROWS); p1.groups = 1; p1.ng = 1;
   const long total = (long)p0.tm * p0.groups + (((long)p1.tm * p1.groups + 7) & ~7L);
   if (total >= (1LL << 31)) return YOLAT_E_UNSUPPORTED;
-  hipLaunchKernelGGL(k_fusion_rows_x6<64>, dim3((unsigned)total), dim3(FxShape<64>::T), 0, (hipStream_t)stream, p0, p1, PoolRider{}, FxSlopes<0>{});
+  fx_launch_rows<FxX6>(64, (unsigned)total, p0, p1, PoolRider{}, nullptr, nullptr, (hipStream_t)stream);
   YL_LAUNCH_CHECK();
   return 0;
-}
-
-// ------------------------------------------------------------------------------------------------------------------
-// Skinny Linear (+ folded BatchNorm + ReLU) with long K as a bf16x6-emulated fp32 GEMM — the per-proposal classifier
-// layers (architecture3cc_rpn_gp_iter2.py:91-93,127-128: P x 2304 -> 512 -> 256 -> n_classes).  Few rows, long K:
-// one 512-thread workgroup owns a 32 x 32 output tile and its 8 waves split K (wave w takes the 16-wide k steps w,
-// w+8, ...), everything in registers: the wave's A values are loaded as fp32 and split on the fly (VALU, beside the
-// matrix pipe); the weights are pre-split AND pre-packed in MFMA operand order (yolat_split_bf16x3_packed: one k
-// step of one 32-column tile = 3 x 1 KB, each a fully coalesced wave load); four k steps in flight per wave.
-// Column tiles are dealt to the XCDs (blockIdx % 8), so each XCD's L2 holds only its own eighth of the weights.
-// The partial accumulators are summed through LDS by wave 0 in a fixed order (no atomics: deterministic), which
-// applies shift (+ ReLU) and stores.  vs k_gemm_nt_sk (fp32 MFMA, 64 cycles per 2 k): 6 x 32 cycles per 16 k.
-// ------------------------------------------------------------------------------------------------------------------
-#define FX_SK_WAVES 8
-// APRE: A is given pre-split and packed like the weights (yolat_split_bf16x3_packed of its rows) — no VALU in the loop;
-// otherwise fp32 A [M, lda], split on the fly (36+ VALU per k step: the VALU then bounds the kernel, fine for short K).
-template <bool APRE>
-__global__ void __launch_bounds__(64 * FX_SK_WAVES) k_linear_x6_sk(const void* __restrict__ Av, long lda, int M, int K,
-                                                                   const yl_bf16_t* __restrict__ Wp,
-                                                                   const float* __restrict__ shift, int relu, int N,
-                                                                   float* __restrict__ out, long ldo, int tm, int tn) {
-  constexpr int NW = FX_SK_WAVES, DEPTH = 4;                  // k steps in flight per wave (the loads are latency bound)
-  __shared__ float red[NW - 1][16][64];
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, l31 = lane & 31, lhi = lane >> 5;
-  // column tile ct = xcd + 8 * (slot / tm), row tile = slot % tm
-  const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-  const int ct = xcd + 8 * (slot / tm), rt = slot % tm;
-  if (ct >= tn) return;
-  const int row0 = rt * 32, col0 = ct * 32;
-  const int nks = K >> 4;
-  const float* ap = APRE ? nullptr : reinterpret_cast<const float*>(Av) + (long)yl_min(row0 + l31, M - 1) * lda + 8 * lhi;
-  const yl_bf16_t* app = APRE ? reinterpret_cast<const yl_bf16_t*>(Av) + (long)rt * nks * (3 * 512) + lane * 8 : nullptr;
-  const yl_bf16_t* wp = Wp + (long)ct * nks * (3 * 512) + lane * 8;
-  // two accumulators: the six products of a k step alternate between them (no MFMA waits on the one before it)
-  f32x16 acc, acc2;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) { acc[r] = 0.f; acc2[r] = 0.f; }
-  struct Stage { float4 a0, a1; fx_bf16x8 a[3]; fx_bf16x8 w[3]; };
-  // unconditional, clamped loads (a wave past its last k step re-reads that step; its products are zeroed): the
-  // number of loads in flight is static
-  auto load = [&](int ks, Stage& s) {
-    const int kc = yl_min(ks, nks - 1);
-    if (APRE) {
-#pragma unroll
-      for (int q = 0; q < 3; ++q) s.a[q] = *reinterpret_cast<const fx_bf16x8*>(app + (long)kc * (3 * 512) + q * 512);
-    } else {
-      s.a0 = *reinterpret_cast<const float4*>(ap + 16 * kc);
-      s.a1 = *reinterpret_cast<const float4*>(ap + 16 * kc + 4);
-    }
-#pragma unroll
-    for (int q = 0; q < 3; ++q) s.w[q] = *reinterpret_cast<const fx_bf16x8*>(wp + (long)kc * (3 * 512) + q * 512);
-  };
-  // branch-free: a step past the end contributes zeros (a branch here would make the compiler's vmcnt bookkeeping
-  // give up and wait for ALL loads at the loop top)
-  auto compute = [&](const Stage& s, bool valid) {
-    fx_bf16x8 ah, am, al;
-    if (APRE) {
-      fx_u32x4 z = {0u, 0u, 0u, 0u};
-      const fx_bf16x8 zero = *reinterpret_cast<fx_bf16x8*>(&z);
-      ah = valid ? s.a[0] : zero; am = valid ? s.a[1] : zero; al = valid ? s.a[2] : zero;
-    } else {
-      const float g = valid ? 1.f : 0.f;
-      const float x[8] = {s.a0.x * g, s.a0.y * g, s.a0.z * g, s.a0.w * g, s.a1.x * g, s.a1.y * g, s.a1.z * g, s.a1.w * g};
-      fx_split8(x, ah, am, al);
-    }
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, s.w[0], acc, 0, 0, 0);      // small terms first
-    acc2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, s.w[2], acc2, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am, s.w[1], acc, 0, 0, 0);
-    acc2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am, s.w[0], acc2, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, s.w[1], acc, 0, 0, 0);
-    acc2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, s.w[0], acc2, 0, 0, 0);
-  };
-  Stage st[DEPTH];
-#pragma unroll
-  for (int d = 0; d < DEPTH; ++d) load(wave + NW * d, st[d]);
-  for (int ks = wave; ks < nks; ks += NW * DEPTH) {
-#pragma unroll
-    for (int d = 0; d < DEPTH; ++d) {
-      compute(st[d], ks + NW * d < nks);
-      __builtin_amdgcn_sched_barrier(0);               // keep the refill HERE (the scheduler would sink it to its use)
-      load(ks + NW * (d + DEPTH), st[d]);
-      __builtin_amdgcn_sched_barrier(0);
-    }
-  }
-#pragma unroll
-  for (int r = 0; r < 16; ++r) acc[r] += acc2[r];
-  if (wave > 0) {
-#pragma unroll
-    for (int r = 0; r < 16; ++r) red[wave - 1][r][lane] = acc[r];
-  }
-  __syncthreads();
-  if (wave == 0) {
-    const int col = col0 + l31;
-    const float sh = (shift && col < N) ? shift[col] : 0.f;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      float v = acc[r];
-#pragma unroll
-      for (int w = 0; w < NW - 1; ++w) v += red[w][r][lane];               // fixed order
-      v += sh;
-      if (relu) v = fmaxf(v, 0.f);
-      const int row = row0 + (r & 3) + 8 * (r >> 2) + 4 * lhi;
-      if (row < M && col < N) out[(long)row * ldo + col] = v;
-    }
-  }
-}
-
-// W [rows = N, cols = K] fp32 (optionally scaled per row) -> its exact 3-way bfloat16 split in the operand order of
-// k_linear_x6_sk: packed[ct][ks][part][lane][8] with ct = n / 32, ks = k / 16, lane = n % 32 + 32 * ((k % 16) / 8),
-// element k % 8; rows beyond N are zero.  One thread per 8 consecutive k.
-static __global__ void k_split_bf16x3_packed(const float* __restrict__ W, long ldw, int N, int K,
-                                             const float* __restrict__ row_scale, yl_bf16_t* __restrict__ packed) {
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;         // (ct, ks, lane)
-  const int nks = K >> 4, tn = (N + 31) >> 5;
-  if (i >= (long)tn * nks * 64) return;
-  const int lane = (int)(i & 63), ks = (int)((i >> 6) % nks), ct = (int)((i >> 6) / nks);
-  const int n = ct * 32 + (lane & 31), k0 = ks * 16 + 8 * (lane >> 5);
-  float x[8];
-#pragma unroll
-  for (int e = 0; e < 8; ++e) x[e] = n < N ? W[(long)n * ldw + k0 + e] * (row_scale ? row_scale[n] : 1.f) : 0.f;
-  fx_bf16x8 h, m, l;
-  fx_split8(x, h, m, l);
-  yl_bf16_t* o = packed + (((long)ct * nks + ks) * 3) * 512 + lane * 8;
-  *reinterpret_cast<fx_bf16x8*>(o) = h;
-  *reinterpret_cast<fx_bf16x8*>(o + 512) = m;
-  *reinterpret_cast<fx_bf16x8*>(o + 1024) = l;
-}
-
-extern "C" size_t yolat_split_bf16x3_packed_elems(int64_t N, int64_t K) {
-  return (N <= 0 || K <= 0) ? 0 : (size_t)yl_cdiv(N, 32) * (size_t)(K / 16) * 3 * 512;
-}
-// packed: yolat_split_bf16x3_packed_elems(N, K) bfloat16 values, 16-byte aligned.  K % 16 == 0.
-extern "C" int yolat_split_bf16x3_packed(const float* W, int64_t ldw, int64_t N, int64_t K, const float* row_scale,
-                                         uint16_t* packed, yolat_stream_t stream) {
-  if (N <= 0 || K <= 0 || !W || !packed || ldw < K || N >= (1LL << 31) - 32 || K >= (1LL << 31)) return YOLAT_E_INVALID;
-  if (K % 16 != 0 || !yl_aligned16(packed)) return YOLAT_E_UNSUPPORTED;
-  const long items = (long)yl_cdiv(N, 32) * (K / 16) * 64;
-  hipLaunchKernelGGL(k_split_bf16x3_packed, dim3((unsigned)yl_cdiv(items, 256)), dim3(256), 0, (hipStream_t)stream, W,
-                     (long)ldw, (int)N, (int)K, row_scale, reinterpret_cast<yl_bf16_t*>(packed));
-  YL_LAUNCH_CHECK();
-  return 0;
-}
-
-// out [M, N] = act(A [M, K] . (s (.) W)^T + shift),  W given pre-split and packed (yolat_split_bf16x3_packed of the
-// scaled rows), shift = s*b + t folded (NULL: none), act = ReLU when relu != 0.  K % 16 == 0, lda % 4 == 0, A and Wp
-// 16-byte aligned.  Meant for few rows (the launch has cdiv(M,32) * cdiv(N,32) workgroups and re-reads the weights
-// once per 32 rows).  yolat_linear_x6_pre: A given as yolat_split_bf16x3_packed(A, lda, M, K, NULL) — the choice for
-// long K (on-the-fly splitting of A costs more VALU time than the products cost matrix-pipe time).
-static int linear_x6_launch(const void* A, bool pre, int64_t lda, int64_t M, int64_t K, const uint16_t* Wp,
-                            const float* shift, int relu, int64_t N, float* out, int64_t ldo, yolat_stream_t stream) {
-  if (M <= 0 || N <= 0 || K <= 0 || !A || !Wp || !out) return YOLAT_E_INVALID;
-  if ((!pre && lda < K) || ldo < N || M >= (1LL << 31) - 32 || N >= (1LL << 31) - 64) return YOLAT_E_INVALID;
-  if (K % 16 != 0 || (!pre && lda % 4 != 0) || !yl_aligned16(A) || !yl_aligned16(Wp)) return YOLAT_E_UNSUPPORTED;
-  const long tm = yl_cdiv(M, 32), tn = yl_cdiv(N, 32);
-  const long total = 8 * yl_cdiv(tn, 8) * tm;
-  if (total >= (1LL << 31)) return YOLAT_E_UNSUPPORTED;
-  const dim3 grid((unsigned)total), block(64 * FX_SK_WAVES);
-  const yl_bf16_t* wp = reinterpret_cast<const yl_bf16_t*>(Wp);
-  if (pre)
-    hipLaunchKernelGGL(k_linear_x6_sk<true>, grid, block, 0, (hipStream_t)stream, A, (long)lda, (int)M, (int)K, wp, shift,
-                       relu, (int)N, out, (long)ldo, (int)tm, (int)tn);
-  else
-    hipLaunchKernelGGL(k_linear_x6_sk<false>, grid, block, 0, (hipStream_t)stream, A, (long)lda, (int)M, (int)K, wp, shift,
-                       relu, (int)N, out, (long)ldo, (int)tm, (int)tn);
-  YL_LAUNCH_CHECK();
-  return 0;
-}
-extern "C" int yolat_linear_x6(const float* A, int64_t lda, int64_t M, int64_t K, const uint16_t* Wp, const float* shift,
-                               int relu, int64_t N, float* out, int64_t ldo, yolat_stream_t stream) {
-  return linear_x6_launch(A, false, lda, M, K, Wp, shift, relu, N, out, ldo, stream);
-}
-extern "C" int yolat_linear_x6_pre(const uint16_t* Ap, int64_t M, int64_t K, const uint16_t* Wp, const float* shift,
-                                   int relu, int64_t N, float* out, int64_t ldo, yolat_stream_t stream) {
-  return linear_x6_launch(Ap, true, K, M, K, Wp, shift, relu, N, out, ldo, stream);
 }

@@ -115,7 +115,7 @@ int yl_fusion_pair_eval_x6_impl(const float* A, int64_t lda, int64_t N, int64_t 
                                 const uint16_t* Wsm, const uint16_t* Wsl, const float* tsfold, float* Ys, int64_t ldys,
                                 const PoolRider* rider, yolat_stream_t stream, const float* slope_f = nullptr,
                                 const float* slope_s = nullptr);
-// the same launch with the GEMM emulated by three half-precision products (fusion_x6.hip k_fusion_rows_f16x3): the weights
+// the same launch with the GEMM emulated by three half-precision products (fusion_f16x3.hip k_fusion_rows_f16x3): the weights
 // as yolat_split_f16x2 gives them
 int yl_fusion_pair_eval_f16x3_impl(const float* A, int64_t lda, int64_t N, int64_t D, const uint16_t* Wh, const uint16_t* Wl,
                                    const int32_t* Wexp, const float* tfold, int64_t F, const int32_t* node_seg, float* pool,
@@ -123,6 +123,15 @@ int yl_fusion_pair_eval_f16x3_impl(const float* A, int64_t lda, int64_t N, int64
                                    const uint16_t* Wsl, const int32_t* Wsexp, const float* tsfold, float* Ys, int64_t ldys,
                                    const PoolRider* rider, yolat_stream_t stream, const float* slope_f = nullptr,
                                    const float* slope_s = nullptr);
+// what the two launches above share before the launch (fusion_x6.hip): the argument check — w_null / w_unaligned: the
+// weights' NULL and alignment terms, ys_span32: P * ldys >= 2^32 is declined too — then the grid (row tiles of both
+// problems, fx_plan's split of the node problem, the small problem's tn column groups of one tile, the workgroup count
+// with the rider's) and the copy of a rider with blocks
+struct FxPairGrid { int tm0, full, groups, ng, tm1, tn; unsigned total; PoolRider rider; };
+int yl_fx_pair_setup(const float* A, int64_t lda, int64_t N, int64_t D, const float* tfold, int64_t F, const int32_t* node_seg,
+                     float* pool, int64_t ldpool, const float* S, int64_t lds, int64_t P, const float* tsfold, float* Ys,
+                     int64_t ldys, bool w_null, bool w_unaligned, bool ys_span32, const PoolRider* rider, const float* slope_f,
+                     const float* slope_s, FxPairGrid* g);
 // the fusion pair behind a row norm (rownorm.hip): does a batch of N nodes run the fused kernel (true) or the materialising
 // route?  The descriptor's rn_route, or N >= YOLAT_RN_FUSED_MIN_ROWS when that is YOLAT_RN_ROUTE_AUTO: a function of the
 // descriptor and N alone, so the workspace sizing and the forward always agree.

@@ -210,10 +210,10 @@ __global__ void __launch_bounds__(256) k_rn_range_max(const float* __restrict__ 
 
 // ---- the fused eval kernel --------------------------------------------------------------------------------------------
 // pool[p, :] = max over the rows of proposal p of relu(rownorm(A . W^T + b) gamma + beta); second problem of the launch
-// (fusion_block_super, P rows): plain store of the same.  Built from the blocks of k_fusion_rows_x6 (fusion_x6.hip): exact
-// 3-way bf16 split and six products, A split once into registers and kept, W tiles double-buffered through LDS, run-length
-// integer atomicMax epilogue.  The work split differs: a workgroup owns RN_ROWS WHOLE rows and walks all F / 64 column
-// tiles, twice.
+// (fusion_block_super, P rows): plain store of the same.  Built from the blocks of k_fusion_rows_x6 (fusion_x6.hip; the
+// W-tile movers are the same text, fx_w_movers.inc): exact 3-way bf16 split and six products, A split once into registers
+// and kept, W tiles double-buffered through LDS, run-length integer atomicMax epilogue.  The work split differs: a
+// workgroup owns RN_ROWS WHOLE rows and walks all F / 64 column tiles, twice.
 // The mean never appears.  The caller hands in the CENTRED weights Wc = W - (mean over the F outputs of W), bc = b - mean(b):
 //   (A . Wc^T + bc)[r, c] = y[r, c] - mean_c(y[r, :])   algebraically, for every row,
 // so an accumulator IS the deviation d, however far the row mean is from zero, and var = mean_c(d^2) is a centred sum.
@@ -261,25 +261,9 @@ __global__ void __launch_bounds__(RN_T) k_fusion_rows_rn(RnProb p0, RnProb p1, i
   const int row0 = rt * RN_ROWS + wave * 32;
   const int sv_pre = (seg != nullptr && row0 + l31 < N) ? seg[row0 + l31] : -1;
   const yl_bf16_t* const wparts[3] = {small ? p1.Wh : p0.Wh, small ? p1.Wm : p0.Wm, small ? p1.Wl : p0.Wl};
-  constexpr int PER = 64 * CPR / T;                         // pieces per thread and part
-  static_assert((64 * CPR) % T == 0, "part boundary inside a thread's pieces");
-  const unsigned wr0 = (unsigned)tid / CPR, wk = ((unsigned)tid % CPR) * 8;   // row (of the first piece), k offset
-  auto load_w = [&](int ct, fx_u32x4* rw) {
-#pragma unroll
-    for (int t = 0; t < NW; ++t) {
-      const int part = t / PER;
-      const unsigned r = wr0 + (unsigned)(t % PER) * (T / CPR);
-      rw[t] = *reinterpret_cast<const fx_u32x4*>(wparts[part] + (unsigned)(ct * 64 + (int)r) * KD + wk);
-    }
-  };
-  auto store_w = [&](int buf, const fx_u32x4* rw) {
-#pragma unroll
-    for (int t = 0; t < NW; ++t) {
-      const int part = t / PER;
-      const unsigned r = wr0 + (unsigned)(t % PER) * (T / CPR);
-      *reinterpret_cast<fx_u32x4*>(&Ws[buf][part * 64 * RS + r * RS + wk]) = rw[t];
-    }
-  };
+#define FX_W_CLAMP 0                                        // (F % 64 == 0)
+#include "fx_w_movers.inc"
+#undef FX_W_CLAMP
   fx_u32x4 rw[NW];
   load_w(0, rw);
   float t0 = tcen[l31], t1 = tcen[32 + l31];

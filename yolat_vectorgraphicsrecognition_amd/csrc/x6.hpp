@@ -1,11 +1,11 @@
-// x6.hpp — shared pieces of the bf16x6-emulated fp32 GEMM kernels (fusion_x6.hip, gemm_x6.hip): exact 3-way bfloat16
+// x6.hpp — shared pieces of the bf16x6-emulated fp32 GEMM kernels (fusion_x6.hip, linear_x6.hip, gemm_x6.hip): exact 3-way bfloat16
 // split of fp32 values.  x = h + m + l with h = the top 8 significand bits of x, m the next 8, l the last 8
 // (truncation splits: every term is exactly representable in bfloat16); six of the nine products a_i * b_j — all but
 // the three O(2^-24) ones — reproduce the fp32 product to ~3e-7 relative with fp32 accumulation.
 // Sibling: f16x3.hpp — two half-precision terms per operand (11 significand bits each) and THREE products, after a
 // power-of-two scale per row that this split does not need (bfloat16 shares fp32's exponent range, so the terms here are
 // exact relative to the ELEMENT; there the error of an element far below its row's maximum is relative to that maximum).
-// The eval fusion pair runs on f16x3 (fusion_x6.hip k_fusion_rows_f16x3); the training instantiations of the rows
+// The eval fusion pair runs on f16x3 (fusion_f16x3.hip k_fusion_rows_f16x3); the training instantiations of the rows
 // kernel, its node-side and Linear uses, rownorm.hip, gemm_x6.hip, linear_sk_x6.hip and edge.hip stay on this split.
 //
 // Non-finite and tiny inputs.  The split is exact for every finite x whose three terms are normal or zero.  It is NOT a
