@@ -878,7 +878,8 @@ __global__ void __launch_bounds__(256, 4) k_edge_mt_uv_mlp2_mean(const float* __
 //   significand bits: the split is exact), a.b = a_h b_h + (a_h b_m + a_m b_h + a_h b_l + a_l b_h + a_m b_m) + O(2^-24):
 //   six v_mfma_f32_32x32x16_bf16 (32 cycles each) per 16 k instead of eight fp32 MFMAs (64 cycles each), exact
 //   products, fp32 accumulation.  The result differs from the fp32-MFMA kernels only by the summation order
-//   (measured ~1e-7 relative); tests/test_gpu_ops.py compares the two at 2e-6 of scale.
+//   and the three dropped cross terms (< (8 + 2^-6) 2^-24 |a||b| per product); tests/test_gpu_edge_eval_elements.py holds
+//   it per element to the fp32 kernels' derived bound plus that term (tests/edge_eval_ref.py: edge_stage_ref, x6).
 // FOLD: layer 1's bias / BatchNorm live in UV and Wc4 (node-side epilogue; b1 = s1 = t1 = NULL) and layer 2's bias
 //   in t2 (b2 = NULL): h1 = relu(U + V + Wc4.attr), message = relu(s2 * (W2.h1) + t2) — 6 instead of 8 VALU
 //   operations per hidden activation (packed fp32 math) and 2 instead of 3 per message.
