@@ -323,6 +323,12 @@ int yolat_rownorm_act_bwd(const float* dZ, int64_t lddz, const float* Y, int64_t
 #define YOLAT_RN_ROUTE_AUTO 0
 #define YOLAT_RN_ROUTE_FUSED 1
 #define YOLAT_RN_ROUTE_MATERIALISE 2
+/* Or-ed into rn_route by the author of a ROW-NORM base that is handed to yolat_forward_eval_bf16*: the opt-in of the bf16
+ * storage for such a model (its logit gap against fp32 is a measured figure of its own).  Without the bit the
+ * bf16 forward declines a row-norm base (YOLAT_E_UNSUPPORTED) as it always did; the fp32 forward declines a route that carries
+ * it (YOLAT_E_INVALID).  The low bits keep their meaning; for the bf16 forward AUTO is the fused kernel wherever the shape
+ * fits it (D in {64, 128}, every *_fold pointer given) and the materialising route elsewhere.                          */
+#define YOLAT_RN_ROUTE_BF16 0x100
 int yolat_fusion_pair_eval_x6_rn(const float* A, int64_t lda, int64_t N, int64_t D, const uint16_t* Wh, const uint16_t* Wm,
                                  const uint16_t* Wl, const float* tcen, int64_t F, const float* gamma_f, const float* beta_f,
                                  const int32_t* node_seg, float* pool, int64_t ldpool, const float* S, int64_t lds, int64_t P,
@@ -698,8 +704,8 @@ typedef struct {
   const float *act_slope[4];
   /* YOLAT_NORM_*: the norm of the same four sites (csrc/rownorm.hip).  0 = BatchNorm: none of the fields below is read, the
    * launches, the workspace and the logits are those of a descriptor that never heard of them.  norm != 0 (act must be 0,
-   * else YOLAT_E_INVALID; the bf16 descriptor declines such a base): the BatchNorm scale / shift pointers of the four sites are
-   * not read; Wf_hi.. / Wfs_hi.. hold the split of the CENTRED weights and tf_fold / tfs_fold the centred bias
+   * else YOLAT_E_INVALID; the bf16 descriptor takes such a base only with YOLAT_RN_ROUTE_BF16 in rn_route): the BatchNorm
+   * scale / shift pointers of the four sites are not read; Wf_hi.. / Wfs_hi.. hold the split of the CENTRED weights and tf_fold / tfs_fold the centred bias
    * (yolat_fusion_pair_eval_x6_rn); Wc1_gx / Wc_x6 are packed without a row scale and tc1_gx / tc_fold are the bias.
    * rn_gamma / rn_beta: LayerNorm weight / bias per site (site order as act_slope), NULL for the instance norm.       */
   int32_t norm;
@@ -851,7 +857,16 @@ int yolat_forward_eval_csr(const yolat_model_eval* m, const float* x, int64_t ld
  * REQUIRED); the bf16 members are yolat_f32_to_bf16 copies of the named fp32 weights (row-major, same
  * shapes).  Wuv/Wr/Wn[0] are unused (layer 0 multiplies the raw fp32 features).
  * Supported shapes: C = 64, Cin0 <= 16, F, C*n_blocks_out, H1, H2 multiples of 64, N <= 2^23, E <= 2^29;
- * else YOLAT_E_UNSUPPORTED.  base->norm must be YOLAT_NORM_BATCH (else YOLAT_E_UNSUPPORTED).
+ * else YOLAT_E_UNSUPPORTED.
+ * base->norm: YOLAT_NORM_BATCH, or YOLAT_NORM_LAYER / YOLAT_NORM_INSTANCE with YOLAT_RN_ROUTE_BF16 set in base->rn_route (a
+ * row-norm base without the bit: YOLAT_E_UNSUPPORTED).  A row-norm base needs act = YOLAT_ACT_RELU and, for LAYER, the four
+ * rn_gamma / rn_beta (else YOLAT_E_INVALID before anything is enqueued); rn_gamma / rn_beta / rn_eps are read by address from
+ * the base.  Its fusion pair runs k_hfusion_rows8_rn (csrc/fusion_h8_rn.hip: GEMM + row norm + ReLU + per-proposal max in one
+ * launch) for C*n_blocks_out in {64, 128} with the four *_fold pointers given and rn_route not MATERIALISE; every other
+ * shape materialises row ranges of <= 64 MiB fp32 (bf16 tile GEMM -> yolat_rownorm_act -> range maximum) in
+ * yolat_fusion_pair_eval_rn_work_elems(N, F) floats of extra workspace.  The classifier's two hidden layers are a bf16 tile
+ * GEMM into fp32 followed by one row-norm launch that writes bf16 (P * (H1 + H2) bf16 of extra workspace).  A BatchNorm
+ * base takes none of these branches: same launches, same workspace layout and size, same logits.
  * base->act: YOLAT_ACT_RELU, or YOLAT_ACT_LEAKYRELU / YOLAT_ACT_PRELU with the four base->act_slope[] set — the activation
  * is applied in fp32, per element before the per-proposal maximum and before the bf16 store of the classifier's hidden
  * activations, the slope read from device memory by every launch; the forward is one launch longer and, off the
@@ -873,7 +888,10 @@ typedef struct {
   const uint16_t *Wf, *Wfs, *Wc1, *Wc2, *Wc3; /* bf16 of the fusion / classifier weights        */
   const float* t2f[YOLAT_MAX_LAYERS];         /* fp32 [C]: s2*b2 + t2, the shift that goes with the folded W2 (ABI 4) */
   /* fusion_block / fusion_block_super with their BatchNorm folded (ABI 4, optional: NULL keeps the unfolded kernels):
-   * Wf_fold = bf16(diag(sf) Wf) [F, D], tf_fold = sf*bf + tf [F] fp32; same for the super block */
+   * Wf_fold = bf16(diag(sf) Wf) [F, D], tf_fold = sf*bf + tf [F] fp32; same for the super block.
+   * Under a ROW-NORM base (no BatchNorm to fold): Wf_fold = bf16(Wf - mean over the F rows of Wf), the weight centred over
+   * its outputs in float64 before the rounding, and tf_fold = bf - mean(bf) in fp32 — the product is then the deviation of a
+   * row from its own mean, which is all the row norm needs (csrc/fusion_h8_rn.hip); same for the super block */
   const uint16_t *Wf_fold, *Wfs_fold;
   const float *tf_fold, *tfs_fold;
   /* ABI 5, optional (NULL keeps the per-layer launches): the conv stack's weights in the register-fragment order of the

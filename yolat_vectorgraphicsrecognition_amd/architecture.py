@@ -213,7 +213,8 @@ class SparseCADGCN(nn.Module):
             plan = plans.get(sid)
             if plan is None:
                 from .plan import EvalPlan
-                plan = plans[sid] = EvalPlan(self, self.__dict__.get("_yolat_precision", "fp32"))
+                plan = plans[sid] = EvalPlan(self, self.__dict__.get("_yolat_precision", "fp32"),
+                                             row_norm=self.__dict__.get("_yolat_row_norm", False))
             ug = self.__dict__.get("_yolat_use_graph")
             if ug is not None:
                 plan.use_graph = ug
@@ -326,10 +327,14 @@ class SparseCADGCN(nn.Module):
         pred_bbox = torch.stack([cx - w / 2, cy - h / 2, cx + w / 2, cy + h / 2], dim=1)
         return pred_cls, pred_bbox, None, slice_bbox, slice_image_bbox, None
 
-    def set_eval_precision(self, precision="fp32", leaky_act=False):
+    def set_eval_precision(self, precision="fp32", leaky_act=False, row_norm=False):
         """Storage precision of the eval fast path: "fp32" (default, 1e-4 parity with the reference) or "bf16"
         (bf16 node activations / weights, fp32 accumulation — csrc/bf16_eval.hip; ~1e-2 of the logits' scale).
-        "bf16" covers norm = batch only.  A model built with act = leakyrelu / prelu runs in "bf16" when the caller says so
+        A model built with norm = layer / instance runs in "bf16" when the caller says so with row_norm=True (DESIGN.md 3i
+        "bf16 eval storage": csrc/fusion_h8_rn.hip); without it the call declines such a model as it always did: the bf16
+        numerics contract is measured for norm = batch models, a row-norm model has measured figures of its own
+        (INTEGRATION.md).  row_norm has no effect on a norm = batch model.
+        A model built with act = leakyrelu / prelu runs in "bf16" when the caller says so
         with leaky_act=True (DESIGN.md 3h "bf16 eval storage"); without it the call declines such a model as it always
         did: the arg-max part of the bf16 numerics contract is measured for ReLU models and does not carry over to every
         leaky one.  leaky_act has no effect on a ReLU model.  Training always runs in fp32."""
@@ -338,11 +343,13 @@ class SparseCADGCN(nn.Module):
         if precision != "fp32" and not leaky_act and not engine.model_is_relu(self):
             raise ValueError("eval precision %r runs act = %r only when asked to: set_eval_precision(%r, leaky_act=True) "
                              "(fp32 runs it as it is)" % (precision, self.act, precision))
-        if precision != "fp32" and engine.model_norm(self) != "batch":
-            raise ValueError("eval precision %r covers norm = batch only; this model was built with norm = %r "
-                             "(fp32 runs it)" % (precision, engine.model_norm(self)))
-        if self.__dict__.get("_yolat_precision", "fp32") != precision:
+        if precision != "fp32" and not row_norm and engine.model_norm(self) != "batch":
+            raise ValueError("eval precision %r runs norm = %r only when asked to: set_eval_precision(%r, row_norm=True) "
+                             "(fp32 runs it as it is)" % (precision, engine.model_norm(self), precision))
+        row_norm = bool(row_norm) and precision != "fp32" and engine.model_norm(self) != "batch"
+        if (self.__dict__.get("_yolat_precision", "fp32"), self.__dict__.get("_yolat_row_norm", False)) != (precision, row_norm):
             self.__dict__["_yolat_precision"] = precision
+            self.__dict__["_yolat_row_norm"] = row_norm
             self.__dict__.pop("_yolat_plans", None)
         return self
 

@@ -15,6 +15,8 @@
 // Here: the fusion kernels, the node side of a conv layer > 0, the pooling prologue, the forward with its four entry points
 // and the dense stages as ops.  The tile GEMM is hgemm.hpp (every k_hgemm instance of the library is instantiated HERE:
 // yl_launch_hgemm serves bf16_linear.hip); edge stage: edge_chain.hip, rows8 fusion: fusion_h8.hip, conv stack: conv_local.hip.
+// A row-norm base (--norm layer / instance, opted in by YOLAT_RN_ROUTE_BF16): the fusion pair and the classifier's two hidden
+// layers take the branches of fusion_stage_rn / the forward's classifier block; kernels: fusion_h8_rn.hip, rownorm.hip.
 #include "hgemm.hpp"
 #include "gemm_nt.hpp"
 #include "internal.hpp"
@@ -334,6 +336,8 @@ struct PlanH {
   u16* feats; u16* fsup; float* Z; float* c1; float* c2;
   int* local_flag; int* eptr;
   float* act_work;      // leaky model off the rows8 route: a column range of the fusion block's BatchNorm output, fp32
+  u16* rn_h1; u16* rn_h2;   // row-norm model: the classifier's normalised hidden activations, bf16 (c1 / c2 hold the fp32 GEMMs)
+  float* rn_work;       // row-norm model on the materialising route: a row range of the fusion block's output, fp32
   size_t bytes;
 };
 // weights of the fusion pair: Wf / Wfs bf16 with their fp32 bias and BatchNorm scale / shift, the BatchNorm-folded forms
@@ -341,17 +345,31 @@ struct PlanH {
 struct FusionStageH {
   const u16 *Wf, *Wfs; const float *bf, *sf, *tf, *bfs, *sfs, *tfs;
   const u16 *Wf_fold; const float* tf_fold; const u16* Wfs_fold; const float* tfs_fold; const float *slope_f, *slope_s;
+  // a row-norm base (norm != YOLAT_NORM_BATCH): the *_fold weights are CENTRED, sf / tf are not read; gamma / beta of the two
+  // sites by address (NULL: instance norm), eps and the descriptor's route
+  int norm; int rn_route; const float *gamma_f, *beta_f, *gamma_s, *beta_s; float rn_eps;
 };
 FusionStageH fusion_weights(const yolat_model_eval_bf16* mh) {
   const yolat_model_eval* m = mh->base;
   const bool leaky = m->act != YOLAT_ACT_RELU;
-  return FusionStageH{mh->Wf, mh->Wfs, m->bf, m->sf, m->tf, m->bfs, m->sfs, m->tfs, mh->Wf_fold, mh->tf_fold, mh->Wfs_fold,
-                      mh->tfs_fold, leaky ? m->act_slope[0] : nullptr, leaky ? m->act_slope[1] : nullptr};
+  FusionStageH w{mh->Wf, mh->Wfs, m->bf, m->sf, m->tf, m->bfs, m->sfs, m->tfs, mh->Wf_fold, mh->tf_fold, mh->Wfs_fold,
+                 mh->tfs_fold, leaky ? m->act_slope[0] : nullptr, leaky ? m->act_slope[1] : nullptr};
+  if (m->norm != YOLAT_NORM_BATCH) {
+    w.norm = m->norm; w.rn_route = m->rn_route; w.rn_eps = m->rn_eps;
+    w.gamma_f = m->rn_gamma[0]; w.beta_f = m->rn_beta[0]; w.gamma_s = m->rn_gamma[1]; w.beta_s = m->rn_beta[1];
+  }
+  return w;
 }
 // does the fusion pair run on the A-in-registers rows kernel (fusion_h8.hip)?  A function of the weights and D alone, so
 // the workspace sizing, the descriptor check and the stage agree
 bool h8_route(const FusionStageH& w, long D) {
   return (D == 64 || D == 128) && w.Wf_fold && w.Wfs_fold && w.tf_fold && w.tfs_fold;
+}
+// a row-norm base: the fused kernel (fusion_h8_rn.hip) or the materialising route?  A function of the descriptor alone — AUTO
+// is the fused kernel wherever the shape fits it (the faster route at both sizes measured, N = 10 k and 200 k: DESIGN.md 6,
+// so there is no row threshold as on the fp32 path) — so the workspace sizing and the stage agree
+bool rn_fused_h(const FusionStageH& w, long D, long F) {
+  return (w.rn_route & 3) != YOLAT_RN_ROUTE_MATERIALISE && h8_route(w, D) && F % 64 == 0;
 }
 PlanH carve_h(const yolat_model_eval_bf16* mh, long N, long E, long P, void* ws) {
   const yolat_model_eval* m = mh->base;
@@ -375,6 +393,12 @@ PlanH carve_h(const yolat_model_eval_bf16* mh, long N, long E, long P, void* ws)
   p.act_work = nullptr;
   if (m->act != YOLAT_ACT_RELU && !h8_route(fusion_weights(mh), D))
     p.act_work = c.take<float>((long)yolat_fusion_pair_eval_act_work_elems(N, F));
+  // (the same for a row-norm descriptor: the bf16 hidden activations, then the row range of the materialising route)
+  p.rn_h1 = nullptr; p.rn_h2 = nullptr; p.rn_work = nullptr;
+  if (m->norm != YOLAT_NORM_BATCH) {
+    p.rn_h1 = c.take<u16>(P * m->H1); p.rn_h2 = c.take<u16>(P * m->H2);
+    if (!rn_fused_h(fusion_weights(mh), D, F)) p.rn_work = c.take<float>((long)yolat_fusion_pair_eval_rn_work_elems(N, F));
+  }
   p.bytes = c.off + 256;
   return p;
 }
@@ -384,7 +408,18 @@ int model_ok(const yolat_model_eval_bf16* mh) {
   const yolat_model_eval* m = mh->base;
   if (m->n_blocks < 1 || m->n_blocks > YOLAT_MAX_LAYERS || m->n_blocks_out < 1 || m->n_blocks_out > m->n_blocks)
     return YOLAT_E_INVALID;
-  if (m->norm != YOLAT_NORM_BATCH) return YOLAT_E_UNSUPPORTED;     // a row-norm base (rownorm.hip) runs on the fp32 forward only
+  // a row-norm base (rownorm.hip, fusion_h8_rn.hip) runs here when its author opted in (YOLAT_RN_ROUTE_BF16): ReLU only
+  if (m->norm != YOLAT_NORM_BATCH) {
+    if (m->norm != YOLAT_NORM_LAYER && m->norm != YOLAT_NORM_INSTANCE) return YOLAT_E_INVALID;
+    if ((m->rn_route & YOLAT_RN_ROUTE_BF16) == 0) return YOLAT_E_UNSUPPORTED;
+    const int route = m->rn_route & ~YOLAT_RN_ROUTE_BF16;
+    if (route < YOLAT_RN_ROUTE_AUTO || route > YOLAT_RN_ROUTE_MATERIALISE || !(m->rn_eps >= 0.f)) return YOLAT_E_INVALID;
+    if (m->act != YOLAT_ACT_RELU) return YOLAT_E_INVALID;
+    for (int i = 0; i < 4; ++i) {
+      if ((m->rn_gamma[i] == nullptr) != (m->rn_beta[i] == nullptr)) return YOLAT_E_INVALID;
+      if (m->norm == YOLAT_NORM_LAYER && !m->rn_gamma[i]) return YOLAT_E_INVALID;
+    }
+  }
   // the activation of the four sites behind the conv stack (act.hip): every launch reads its slope through the address
   if (m->act != YOLAT_ACT_RELU && m->act != YOLAT_ACT_LEAKYRELU && m->act != YOLAT_ACT_PRELU) return YOLAT_E_INVALID;
   if (m->act != YOLAT_ACT_RELU)
@@ -402,6 +437,10 @@ int model_ok(const yolat_model_eval_bf16* mh) {
   if (!mh->Wf || !mh->Wfs || !mh->Wc1 || !mh->Wc2 || !mh->Wc3) return YOLAT_E_INVALID;
   // (a leaky forward writes the pooled start values before the rows kernel: what that launch would decline is declined here)
   if (m->act != YOLAT_ACT_RELU && h8_route(fusion_weights(mh), D) && (!yl_aligned16(mh->Wf_fold) || !yl_aligned16(mh->Wfs_fold)))
+    return YOLAT_E_UNSUPPORTED;
+  // (the same for the fused row-norm launch, which comes after the conv stack's launches)
+  if (m->norm != YOLAT_NORM_BATCH && rn_fused_h(fusion_weights(mh), D, m->F) &&
+      (!yl_aligned16(mh->Wf_fold) || !yl_aligned16(mh->Wfs_fold)))
     return YOLAT_E_UNSUPPORTED;
   return 0;
 }
@@ -422,7 +461,38 @@ struct FusionIoH {
   float* work;         // leaky off the rows8 route: yolat_fusion_pair_eval_act_work_elems(N, F) floats
 };
 struct FusionProbe { int force_groups; int* route; int* groups_ng; };
+// ---- the pair behind a row norm (w.norm != YOLAT_NORM_BATCH; ReLU): Z[:, 0:F] zero before the call.
+//   route 6  k_hfusion_rows8_rn on the centred *_fold weights (fusion_h8_rn.hip)                        1 launch
+//   route 7  every other shape, per row range (<= 64 MiB of `work`): the bf16 tile GEMM with the bias into fp32, the row norm
+//            + ReLU in place (yolat_rownorm_act), the range maximum into the pool (k_rn_range_max); the super block as a
+//            tile GEMM into its fp32 slot of Z and the row norm in place                                3 x ranges + 2
+int fusion_stage_rn(const FusionStageH& w, const FusionIoH& io, hipStream_t st, const FusionProbe& probe) {
+  const long ld = io.ld, N = io.N, D = io.D, ZW = io.ZW, P = io.P, F = io.F;
+  float* const Z = io.Z;
+  if (rn_fused_h(w, D, F)) {
+    if (probe.route != nullptr) *probe.route = 6;
+    return yl_hfusion_rows8_rn(io.feats, ld, N, D, w.Wf_fold, w.tf_fold, w.gamma_f, w.beta_f, io.node_seg, Z, ZW, F, Z + 2 * F + D,
+                               ZW, P, w.Wfs_fold, w.tfs_fold, w.gamma_s, w.beta_s, Z + F + D, ZW, w.rn_eps, st);
+  }
+  if (io.work == nullptr) return YOLAT_E_INVALID;
+  if (probe.route != nullptr) *probe.route = 7;
+  const long rc = (long)(yolat_fusion_pair_eval_rn_work_elems(N, F) / (size_t)F);
+  if (probe.groups_ng != nullptr) { probe.groups_ng[0] = (int)yl_cdiv(N, rc); probe.groups_ng[1] = (int)yl_cdiv(F, 64); }
+  for (long r0 = 0; r0 < N; r0 += rc) {
+    const long n = N - r0 < rc ? N - r0 : rc;
+    Epilogue e = plain_epilogue();
+    e.bias = w.bf; e.Y = io.work; e.ldy = F;
+    YL_TRY(launch_hgemm(HOp{io.feats + r0 * ld, ld, (int)n}, HOp{w.Wf, D, (int)F}, e, n, F, D, st));
+    YL_TRY(yolat_rownorm_act(io.work, F, n, F, w.gamma_f, w.beta_f, w.rn_eps, 1, io.work, F, nullptr, nullptr, (yolat_stream_t)st));
+    YL_TRY(yl_rn_range_max(io.work, F, n, F, io.node_seg + r0, P, Z, ZW, st));
+  }
+  Epilogue e1 = plain_epilogue();
+  e1.bias = w.bfs; e1.Y = Z + F + D; e1.ldy = ZW;
+  YL_TRY(launch_hgemm(FOp{Z + 2 * F + D, ZW, (int)P}, HOp{w.Wfs, D, (int)F}, e1, P, F, D, st));
+  return yolat_rownorm_act(Z + F + D, ZW, P, F, w.gamma_s, w.beta_s, w.rn_eps, 1, Z + F + D, ZW, nullptr, nullptr, (yolat_stream_t)st);
+}
 int yl_fusion_stage_bf16(const FusionStageH& w, const FusionIoH& io, hipStream_t st, const FusionProbe& probe = {}) {
+  if (w.norm != YOLAT_NORM_BATCH) return fusion_stage_rn(w, io, st, probe);
   const u16* feats = io.feats;
   const long ld = io.ld, N = io.N, D = io.D, ZW = io.ZW, P = io.P, F = io.F;
   const int *node_seg = io.node_seg, force_groups = probe.force_groups;
@@ -708,10 +778,33 @@ static int forward_eval_bf16_impl(const ForwardArgsH& args) {
   });
   snprintf(nm, sizeof nm, "fusion_gemm_bf16+segmax[N x %ld -> %ld -> P] | super[P x %ld -> %ld]", D, F, D, F);
   YL_HSTAGE(nm, 2.0 * (N + P) * D * F, 2.0 * (N * D + 2.0 * D * F) + 4.0 * (2.0 * P * F + N + P * D), {
-    YL_TRY(yl_fusion_stage_bf16(fusion_weights(mh), FusionIoH{p.feats, D, N, D, p.node_seg, p.seg_ptr, p.Z, ZW, P, F, p.act_work},
-                                st));
+    YL_TRY(yl_fusion_stage_bf16(fusion_weights(mh), FusionIoH{p.feats, D, N, D, p.node_seg, p.seg_ptr, p.Z, ZW, P, F,
+                                                              m->norm != YOLAT_NORM_BATCH ? p.rn_work : p.act_work}, st));
   });
-  {
+  if (m->norm != YOLAT_NORM_BATCH) {
+    // a row norm does not fold into its Linear: layers 1 and 2 are the tile GEMM with the bias into the fp32 buffers c1 / c2,
+    // then ONE row-norm launch each that reads fp32 and writes the normalised, ReLU'd row as bf16 into a buffer of its own
+    // (in place would be a race: bf16 row r overlaps fp32 row r / 2, which belongs to another wave).  Layer 3 as ever.
+    Epilogue e = plain_epilogue();
+    e.bias = m->bc1; e.Y = p.c1; e.ldy = m->H1;
+    snprintf(nm, sizeof nm, "cls1_bf16[P x %ld -> %ld] + rownorm", ZW, (long)m->H1);
+    YL_HSTAGE(nm, 2.0 * P * ZW * m->H1, 4.0 * P * ZW + 10.0 * P * m->H1 + 2.0 * ZW * m->H1, {
+      YL_TRY(launch_hgemm(FOp{p.Z, ZW, (int)P}, HOp{mh->Wc1, ZW, (int)m->H1}, e, P, m->H1, ZW, st));
+      YL_TRY(yl_rownorm_act_h(p.c1, m->H1, P, m->H1, m->rn_gamma[2], m->rn_beta[2], m->rn_eps, p.rn_h1, m->H1, st));
+    });
+    e.bias = m->bc2; e.Y = p.c2; e.ldy = m->H2;
+    snprintf(nm, sizeof nm, "cls2_bf16[P x %ld -> %ld] + rownorm", (long)m->H1, (long)m->H2);
+    YL_HSTAGE(nm, 2.0 * P * m->H1 * m->H2, 2.0 * P * m->H1 + 10.0 * P * m->H2 + 2.0 * m->H1 * m->H2, {
+      YL_TRY(launch_hgemm(HOp{p.rn_h1, m->H1, (int)P}, HOp{mh->Wc2, m->H1, (int)m->H2}, e, P, m->H2, m->H1, st));
+      YL_TRY(yl_rownorm_act_h(p.c2, m->H2, P, m->H2, m->rn_gamma[3], m->rn_beta[3], m->rn_eps, p.rn_h2, m->H2, st));
+    });
+    e = plain_epilogue();
+    e.bias = m->bc3; e.Y = logits; e.ldy = args.ld_logits;
+    snprintf(nm, sizeof nm, "cls3_bf16[P x %ld -> %d]", (long)m->H2, (int)m->n_classes);
+    YL_HSTAGE(nm, 2.0 * P * m->H2 * m->n_classes, 2.0 * P * m->H2 + 4.0 * P * m->n_classes + 2.0 * m->H2 * m->n_classes, {
+      YL_TRY(launch_hgemm(HOp{p.rn_h2, m->H2, (int)P}, HOp{mh->Wc3, m->H2, (int)m->n_classes}, e, P, m->n_classes, m->H2, st));
+    });
+  } else {
     Epilogue e = plain_epilogue();
     // the hidden activations of the classifier cross HBM as bf16 (in the fp32-sized buffers c1 / c2): the next Linear rounds
     // its rows to bf16 while staging anyway (FOp::pack — the same round-to-nearest-even), so the logits are the same bits
@@ -782,6 +875,36 @@ extern "C" int yolat_debug_fusion_pair_eval_bf16_act(const uint16_t* feats, int6
   const FusionStageH w{Wf, Wfs, bf, sf, tf, bfs, sfs, tfs, Wf_fold, tf_fold, Wfs_fold, tfs_fold, slope_f, slope_s};
   return debug_fusion_pair(w, FusionIoH{feats, ld, N, D, node_seg, seg_ptr, Z, ldz, P, F, work}, true,
                            FusionProbe{force_groups, route, groups_ng}, stream);
+}
+
+// the pair behind a row norm, launched as the forward launches it (routes 6 and 7 of fusion_stage_rn); rn_route: YOLAT_RN_ROUTE_*
+extern "C" int yolat_debug_fusion_pair_eval_bf16_rn(const uint16_t* feats, int64_t ld, int64_t N, int64_t D,
+                                                    const int32_t* node_seg, float* Z, int64_t ldz, int64_t P, int64_t F,
+                                                    const uint16_t* Wf, const uint16_t* Wfs, const float* bf, const float* bfs,
+                                                    const uint16_t* Wf_fold, const float* tf_fold, const uint16_t* Wfs_fold,
+                                                    const float* tfs_fold, const float* gamma_f, const float* beta_f,
+                                                    const float* gamma_s, const float* beta_s, float eps, int rn_route,
+                                                    float* work, int* route, int* groups_ng, yolat_stream_t stream) {
+  FusionStageH w{Wf, Wfs, bf, nullptr, nullptr, bfs, nullptr, nullptr, Wf_fold, tf_fold, Wfs_fold, tfs_fold, nullptr, nullptr};
+  w.norm = gamma_f != nullptr ? YOLAT_NORM_LAYER : YOLAT_NORM_INSTANCE;
+  w.rn_route = rn_route; w.gamma_f = gamma_f; w.beta_f = beta_f; w.gamma_s = gamma_s; w.beta_s = beta_s; w.rn_eps = eps;
+  if (!feats || !node_seg || !Z || !Wf || !Wfs || N <= 0 || P <= 0 || F <= 0 || D <= 0 || !(eps >= 0.f) || rn_route < 0 ||
+      rn_route > YOLAT_RN_ROUTE_MATERIALISE || (gamma_f == nullptr) != (beta_f == nullptr) ||
+      (gamma_s == nullptr) != (beta_s == nullptr) || (gamma_f == nullptr) != (gamma_s == nullptr))
+    return YOLAT_E_INVALID;
+  if (N >= (1LL << 31) - 512 || P >= (1LL << 31) - 512 || ld < D || ldz < 2 * (F + D)) return YOLAT_E_INVALID;
+  if (P * ldz >= (1LL << 32)) return YOLAT_E_UNSUPPORTED;                     // 32-bit element offsets into the pooled matrix
+  if (D % 64 != 0 || F % 64 != 0 || ld % 8 != 0 || ldz % 4 != 0 || !yl_aligned16(feats) || !yl_aligned16(Z) || !yl_aligned16(Wf) ||
+      !yl_aligned16(Wfs) || (Wf_fold && !yl_aligned16(Wf_fold)) || (Wfs_fold && !yl_aligned16(Wfs_fold)) ||
+      (work && !yl_aligned16(work)))
+    return YOLAT_E_UNSUPPORTED;
+  return yl_fusion_stage_bf16(w, FusionIoH{feats, ld, N, D, node_seg, nullptr, Z, ldz, P, F, work}, (hipStream_t)stream,
+                              FusionProbe{0, route, groups_ng});
+}
+// the classifier's row norm: fp32 rows in, relu(rownorm(Y) gamma + beta) out as bf16 (k_rownorm_act_h, fusion_h8_rn.hip)
+extern "C" int yolat_debug_rownorm_act_bf16(const float* Y, int64_t ldy, int64_t M, int64_t C, const float* gamma,
+                                            const float* beta, float eps, uint16_t* Z, int64_t ldz, yolat_stream_t stream) {
+  return yl_rownorm_act_h(Y, ldy, M, C, gamma, beta, eps, Z, ldz, (hipStream_t)stream);
 }
 
 extern "C" int yolat_debug_pool_prepare_bf16(const uint16_t* feats, const uint16_t* fsup, int64_t ld, int64_t D, int64_t F,

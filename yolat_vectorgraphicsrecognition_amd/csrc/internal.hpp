@@ -191,6 +191,21 @@ int yl_hfusion_rows8(const uint16_t* A, int64_t lda, int64_t N, int64_t D, const
                      const uint16_t* Wfs, const float* tfs, float* sup_out, int64_t ld_sup, hipStream_t st,
                      int force_groups = 0, int* groups_ng = nullptr, const float* slope_f = nullptr,
                      const float* slope_s = nullptr);
+// the same pair behind a ROW norm (fusion_h8_rn.hip, k_hfusion_rows8_rn): Wf / Wfs centred over their F outputs before the
+// bf16 rounding, tf / tfs the centred bias, gamma / beta both NULL for the instance norm; `pool` starts from zeros.
+// yl_hfusion_rows8_rn_ok: the shapes and alignments the launch takes (everything else is declined before anything is written)
+bool yl_hfusion_rows8_rn_ok(const void* A, int64_t lda, int64_t N, int64_t D, const void* Wf, int64_t F, const void* As,
+                            int64_t lda_s, int64_t P, const void* Wfs);
+int yl_hfusion_rows8_rn(const uint16_t* A, int64_t lda, int64_t N, int64_t D, const uint16_t* Wf, const float* tf,
+                        const float* gamma_f, const float* beta_f, const int32_t* seg, float* pool, int64_t ld_pool, int64_t F,
+                        const float* As, int64_t lda_s, int64_t P, const uint16_t* Wfs, const float* tfs, const float* gamma_s,
+                        const float* beta_s, float* sup_out, int64_t ld_sup, float eps, hipStream_t st);
+// Z (bf16, a buffer of its own) = relu(rownorm(Y) * gamma + beta) of fp32 rows, one rounding (fusion_h8_rn.hip)
+int yl_rownorm_act_h(const float* Y, int64_t ldy, int64_t M, int64_t C, const float* gamma, const float* beta, float eps,
+                     uint16_t* Z, int64_t ldz, hipStream_t st);
+// per-proposal maximum of <= 2^20 materialised ReLU'd rows merged into the zero-started pool (rownorm.hip, k_rn_range_max)
+int yl_rn_range_max(const float* Zr, int64_t ldz, int64_t rows, int64_t F, const int32_t* node_seg, int64_t P, float* pool,
+                    int64_t ldpool, hipStream_t st);
 // the weight gradient of a wide Linear on the bf16x6 GEMM: worthwhile?, its workspace, the launch (gemm_x6.hip)
 bool yl_bwd_w_x6_ok(int64_t M, int64_t Nout, int64_t K);
 size_t yl_bwd_w_x6_work_elems(int64_t M, int64_t Nout, int64_t K);
@@ -279,3 +294,18 @@ extern "C" int yolat_debug_hgemm_eval_bf16_act(const void* A, int a_f32, int64_t
                                                int64_t ldw, int64_t Nout, const float* bias, const float* scale,
                                                const float* shift, const float* slope, void* Y, int y_bf16, int64_t ldy,
                                                int* tile_form, yolat_stream_t stream);
+//   the fusion pair and the classifier norm behind a ROW norm (--norm layer / instance; fusion_stage_rn, fusion_h8_rn.hip).
+//     Fusion pair: Z as above, the pooled max zero before the call; gamma / beta [F] of the two sites, all four NULL for the
+//     instance norm; rn_route YOLAT_RN_ROUTE_*.  *route: 6 = k_hfusion_rows8_rn on the CENTRED fold weights (D in {64, 128}, the
+//     four fold pointers given, rn_route not MATERIALISE), 7 = the materialising form on `work`
+//     (yolat_fusion_pair_eval_rn_work_elems(N, F) floats; groups_ng = (row ranges, column tiles)) with the plain Wf / Wfs and
+//     bf / bfs.  Row norm: Z [M, ldz] bf16 = relu(rownorm(Y) gamma + beta) of fp32 rows, one rounding; Z must not overlap Y
+extern "C" int yolat_debug_fusion_pair_eval_bf16_rn(const uint16_t* feats, int64_t ld, int64_t N, int64_t D,
+                                                    const int32_t* node_seg, float* Z, int64_t ldz, int64_t P, int64_t F,
+                                                    const uint16_t* Wf, const uint16_t* Wfs, const float* bf, const float* bfs,
+                                                    const uint16_t* Wf_fold, const float* tf_fold, const uint16_t* Wfs_fold,
+                                                    const float* tfs_fold, const float* gamma_f, const float* beta_f,
+                                                    const float* gamma_s, const float* beta_s, float eps, int rn_route,
+                                                    float* work, int* route, int* groups_ng, yolat_stream_t stream);
+extern "C" int yolat_debug_rownorm_act_bf16(const float* Y, int64_t ldy, int64_t M, int64_t C, const float* gamma,
+                                            const float* beta, float eps, uint16_t* Z, int64_t ldz, yolat_stream_t stream);

@@ -516,3 +516,16 @@ extern "C" int yolat_fusion_pair_eval_rn(const float* A, int64_t lda, int64_t N,
   }
   return 0;
 }
+
+// the range maximum of the generic route for a caller in another file (bf16_eval.hip: the bf16 forward's materialising route):
+// rows <= 2^20 rows of the ReLU'd Zr [rows, ldz] with their proposal ids, merged into the zero-started pool
+int yl_rn_range_max(const float* Zr, int64_t ldz, int64_t rows, int64_t F, const int32_t* node_seg, int64_t P, float* pool,
+                    int64_t ldpool, hipStream_t st) {
+  if (!Zr || !node_seg || !pool || rows <= 0 || rows > (1LL << 20) || F <= 0 || F >= (1LL << 31) || P <= 0 || P >= (1LL << 31) ||
+      ldz < F || ldpool < F)
+    return YOLAT_E_INVALID;
+  hipLaunchKernelGGL(k_rn_range_max, dim3(yl_cdiv(F, 256), yl_cdiv(rows, 16)), dim3(256), 0, st, Zr, (long)ldz, (int)rows, (int)F,
+                     node_seg, (int)P, pool, (long)ldpool);
+  YL_LAUNCH_CHECK();
+  return 0;
+}

@@ -692,6 +692,7 @@ def fusion_pair_eval_act(A, lin_f, fold_f, slope_f, g, pool, S=None, lin_s=None,
 NORM_BATCH, NORM_LAYER, NORM_INSTANCE = 0, 1, 2
 RN_ROWS = 128          # YOLAT_RN_ROWS: rows per workgroup of the fused eval kernel
 RN_ROUTE_AUTO, RN_ROUTE_FUSED, RN_ROUTE_MATERIALISE = 0, 1, 2       # YOLAT_RN_ROUTE_*
+RN_ROUTE_BF16 = 0x100  # YOLAT_RN_ROUTE_BF16: or-ed into rn_route, the opt-in of a row-norm base for the bf16-storage forward
 
 
 def is_rownorm(mod):

@@ -84,16 +84,25 @@ def _split3(w, row_scale, packed, keep):
 _VERSION_OF = operator.attrgetter("_version")
 
 
+def rownorm_bf16_operands(lin):
+    """What the bf16 plan hands k_hfusion_rows8_rn (csrc/fusion_h8_rn.hip) for a Linear [F, D] behind a row norm: the weight
+    centred over its F outputs in float64, Wc = W - mean_rows(W), rounded to bf16 (round to nearest even), and the centred bias
+    in fp32 (ops.rownorm_center).  Pure torch: runs wherever the weight lives."""
+    wc, bc = ops.rownorm_center(lin.weight, lin.bias)
+    return wc.to(torch.bfloat16).contiguous(), bc
+
+
 class EvalPlan(object):
     """precision: "fp32" (default) or "bf16" — bf16 STORAGE of the node activations / weights with fp32
-    accumulation (csrc/bf16_eval.hip, yolat_forward_eval_bf16), the mode of the large-graph configuration."""
+    accumulation (csrc/bf16_eval.hip, yolat_forward_eval_bf16), the mode of the large-graph configuration.
+    row_norm: the opt-in of the bf16 plan for a norm = layer / instance model (SparseCADGCN.set_eval_precision)."""
 
-    def __init__(self, model, precision="fp32"):
+    def __init__(self, model, precision="fp32", row_norm=False):
         if precision not in ("fp32", "bf16"):
             raise ValueError("precision must be 'fp32' or 'bf16'")
         from .engine import model_norm
-        if precision != "fp32" and model_norm(model) != "batch":
-            raise ValueError("the %s eval plan covers norm = batch only (this model's norm is %s)"
+        if precision != "fp32" and not row_norm and model_norm(model) != "batch":
+            raise ValueError("the %s eval plan runs norm = %s only when asked to (row_norm=True)"
                              % (precision, model_norm(model)))
         self.precision = precision
         self._desc_h = None
@@ -248,7 +257,8 @@ class EvalPlan(object):
         """_build_head for norm = layer / instance (csrc/rownorm.hip): a row norm does not fold into its Linear, so the
         descriptor carries plain weights and biases (the BatchNorm scale / shift fields stay NULL and are not read), the
         LayerNorm weight / bias of each site by ADDRESS, and for the fused fusion kernel the split of the weights centred over
-        their outputs (ops.rownorm_center) with the centred bias."""
+        their outputs (ops.rownorm_center) with the centred bias.  As the base of a bf16 plan (row_norm=True) it carries the
+        addresses, gamma / beta / eps and the route with the opt-in bit; the centred bf16 weights are _build_bf16's."""
         m, net = self.model, self.model.cls_net
         if leaky:
             raise NotImplementedError("norm = layer / instance with act = leakyrelu / prelu has no MI355X kernel")
@@ -272,7 +282,12 @@ class EvalPlan(object):
                                                                                    ops.RN_ROUTE_AUTO)
         d.Wf, d.bf = _ptr(fb[0].weight), _ptr(fb[0].bias)
         d.Wfs, d.bfs = _ptr(fs[0].weight), _ptr(fs[0].bias)
-        if _x6_on() and fb[0].in_features in (64, 128) and d.F % 64 == 0:
+        fp32 = self.precision == "fp32"
+        if not fp32:
+            # the base of a bf16 descriptor: the opt-in travels in rn_route (YOLAT_RN_ROUTE_BF16); the bf16x6 operand forms
+            # below are the fp32 forward's and are not made (_build_bf16 makes the bf16 ones)
+            d.rn_route |= ops.RN_ROUTE_BF16
+        if fp32 and _x6_on() and fb[0].in_features in (64, 128) and d.F % 64 == 0:
             for lin, names in ((fb[0], ("Wf_hi", "Wf_mid", "Wf_lo", "tf_fold")), (fs[0], ("Wfs_hi", "Wfs_mid", "Wfs_lo", "tfs_fold"))):
                 wc, bc = ops.rownorm_center(lin.weight, lin.bias)
                 keep += [wc, bc]
@@ -284,7 +299,7 @@ class EvalPlan(object):
         d.Wc2, d.bc2 = _ptr(m2[0].weight), _ptr(m2[0].bias)
         d.Wc3, d.bc3 = _ptr(m3[0].weight), _ptr(m3[0].bias)
         # prediction_cls.0 on the LDS-tiled bf16x6 GEMM (yolat_gemm_x6): packed without a row scale, shift = bias
-        if _x6_on() and m1[0].in_features % 16 == 0:
+        if fp32 and _x6_on() and m1[0].in_features % 16 == 0:
             rows, cols = m1[0].out_features, m1[0].in_features
             packed = torch.empty(lib.yolat_gemm_x6_packed_elems(rows, cols), dtype=torch.bfloat16, device=dev)
             check(lib.yolat_gemm_x6_pack(_ptr(m1[0].weight), cols, rows, cols, None, packed.data_ptr(), ops._stream()),
@@ -321,9 +336,18 @@ class EvalPlan(object):
                 h.Wuv[l], h.Wr[l], h.Wn[l] = half(wuv), half(cv.lin_r.weight), half(cv.mlp_node[0].weight)
         fb, fs = net.fusion_block, net.fusion_block_super
         h.Wf, h.Wfs = half(fb[0].weight), half(fs[0].weight)
-        # the two fusion blocks with their BatchNorm folded: the A-in-registers rows kernel, csrc/fusion_h8.hip
-        h.Wf_fold, h.tf_fold = half_folded(fb[0], ff)
-        h.Wfs_fold, h.tfs_fold = half_folded(fs[0], ffs)
+        if d.norm != ops.NORM_BATCH:
+            # a row norm has nothing to fold: the fold slots carry the weights CENTRED over their outputs and the centred bias,
+            # the operands of the fused row-norm kernel (csrc/fusion_h8_rn.hip); the plain Wf / Wfs serve the materialising route
+            for lin, wname, tname in ((fb[0], "Wf_fold", "tf_fold"), (fs[0], "Wfs_fold", "tfs_fold")):
+                wc, bc = rownorm_bf16_operands(lin)
+                keep += [wc, bc]
+                setattr(h, wname, wc.data_ptr())
+                setattr(h, tname, bc.data_ptr())
+        else:
+            # the two fusion blocks with their BatchNorm folded: the A-in-registers rows kernel, csrc/fusion_h8.hip
+            h.Wf_fold, h.tf_fold = half_folded(fb[0], ff)
+            h.Wfs_fold, h.tfs_fold = half_folded(fs[0], ffs)
         h.Wc1, h.Wc2, h.Wc3 = (half(m.prediction_cls[i][0].weight) for i in range(3))
         # the conv stack's weights in the fragment order of the one-launch proposal-local kernel (csrc/conv_local.hip);
         # models outside its shapes (C != 64, in_channels > 8) keep the per-layer launches
