@@ -1061,9 +1061,14 @@ int yolat_train_step(const yolat_train_model* m, const float* x, int64_t ldx, co
  *     for the children; image_root_ptr [B + 1] = first root of every image.
  *   yolat_predict_select: out[0] = rows of the result, out[1] = 0 when the tree's ranges ARE its proposals' node / edge
  *     ranges and no edge leaves its proposal (else != 0: the one-forward shortcut does not apply — duplicated or foreign
- *     ranges, the reference's KeyError cases — and the caller runs the two-pass extraction), out[4 .. 4 + B] =
+ *     ranges, the reference's KeyError cases — and the caller runs the two-pass extraction; bit 0 (value 1): a root or
+ *     child row outside [0, P) or a range that is not its proposal's, bit 1 (value 2): an edge list that is not grouped
+ *     by proposal, an edge between two proposals, or malformed ids), out[4 .. 4 + B] =
  *     slice_image_bbox, out[4 + B + 1 ..] = the proposal row of every output row (slice_bbox): per image the roots, then
- *     the children of the roots whose arg-max (first maximum) is class K - 1.  out: 4 + B + 1 + R + Ctot int32.
+ *     the children of the roots whose arg-max is class K - 1.  The arg-max is `pred_cls.max(1)[1]` of the reference and
+ *     of the two-pass path: the FIRST index of the row maximum, a NaN counting as the maximum (the first NaN of a row
+ *     that holds one) — one function, yl_argmax_row of csrc/sel_record.hpp, shared with the top-1 of yolat_eval_rows.
+ *     out: 4 + B + 1 + R + Ctot int32; rows behind out[0] are not written.
  *   yolat_predict_gather: out_cls [total, K] = logits[rows], out_bbox [total, 4] = the rows' boxes enlarged by 5 % about
  *     their centre with the reference's fp32 steps (:341-346).                                                           */
 typedef struct yolat_predict_tree {

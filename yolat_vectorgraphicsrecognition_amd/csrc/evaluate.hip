@@ -47,13 +47,7 @@ static __global__ void __launch_bounds__(256) k_eval_rows(const float* logits, l
     } else {
       YL_BCE_ROW_LOSS(EVAL_KMAX, false, z, K, labels, row, 0.f, no_grad, 0l, no_grad, 0l, row_loss)
     }
-    // torch's max(1)[1]: the first index of the row maximum, a NaN counting as the maximum
-    float best = z[0];
-    int arg = 0;
-    for (int c = 1; c < K; ++c) {
-      const float x = z[c];
-      if (best == best && (x > best || x != x)) { best = x; arg = c; }
-    }
+    const int arg = yl_argmax_row(z, K);      // torch's max(1)[1] (sel_record.hpp)
     const int64_t label = labels[row];
     y_pred[r] = arg;
     y_true[r] = label < INT32_MIN ? INT32_MIN : (label > INT32_MAX ? INT32_MAX : (int)label);

@@ -219,7 +219,8 @@ extern "C" int yolat_fixup_offsets(int64_t* edge, int64_t E, const int64_t* edge
 //                       eptr of yl_local_prep) and no edge may leave its proposal — otherwise the sub-batches of the
 //                       reference are NOT the proposals of the batch (duplicates, foreign edges -> its KeyError) and the
 //                       caller falls back to the two-pass extraction (flag in out[1])
-//   k_predict_select    has_object per root (first maximum), exclusive scan of the selected children, per image offsets
+//   k_predict_select    has_object per root (yl_argmax_row == K - 1: torch's max(1)[1], the rule of the two-pass path),
+//                       exclusive scan of the selected children, per image offsets
 //                       (slice_image_bbox), and the proposal row of every output row (slice_bbox) in the reference's order
 //   k_predict_gather    logits / boxes of those rows, boxes enlarged by 5 % about their centre (:341-346, same fp32 steps)
 // One host read (out[]: total, flag, slice_image_bbox, rows) ends the call.
@@ -260,14 +261,7 @@ static __global__ void __launch_bounds__(1024) k_predict_select(yolat_predict_tr
     if (r < R) {
       const int row = t.root_row[r];
       if (row >= 0 && row < P) {
-        const float* z = logits + (long)row * ld;
-        float best = z[0];
-        int arg = 0;
-        for (int k = 1; k < K; ++k) {
-          const float v = z[k];
-          if (v > best) { best = v; arg = k; }
-        }
-        if (arg == K - 1) n = t.child_ptr[r + 1] - t.child_ptr[r];
+        if (yl_argmax_row(logits + (long)row * ld, K) == K - 1) n = t.child_ptr[r + 1] - t.child_ptr[r];
       }
     }
     int incl = n;
